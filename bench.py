@@ -2,9 +2,24 @@
 """
 bench.py -- grid-cells x timesteps / second of fit() on MI355X (BASELINE.json metric), one JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c4_evidence|c4_both_axes|c4_rows1024|c4_wide|c4_laplace|c3|c2|c5|fwd2048|coal_breakpoints|c1_hyper|coal_hyper1000] [--no-extra] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c4_evidence|c4_both_axes|c4_rows1024|c4_wide|c4_laplace|c3|c2|c5|fwd2048|coal_breakpoints|c1_hyper|coal_hyper1000] [--dump-outputs DIR] [--full [--no-extra] [--no-cpu] [--no-pmc] [--no-e2e]]
 
 A "step" is one complete pass of the hot path over one batch of synthetic input: one whole ``fit()`` of the workload.
+
+A plain run sets up, runs W warm-up steps, times K steps, and prints the line: the headline (`value`, `ms_per_step`) and the
+log-evidence of the last step.  ``--full`` adds everything else, as measured before it became an option: the roofline of the step
+kernels (bandwidth probe, two rocprofv3 PMC passes), the end-to-end fit with the posterior read back, the other workloads (the
+extras), the cold first fit, the CPU baseline, the log-evidence against the reference's for each workload (exit status 1 above the
+registered bound), the exchange diagnostic at N > 1, and the full record bench_detail.json.  ``--no-extra`` / ``--no-cpu`` /
+``--no-pmc`` / ``--no-e2e`` leave parts of it out.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed fit() handed its caller as DIR/<name>.npy (float64):
+logEvidence, localEvidence, posteriorMeanValues, logEvidenceList and hyperParameterDistribution whole, the posterior sequence
+(tens to hundreds of MB) as a fixed sample of DUMP_SAMPLE entries (posteriorSequence_sample.npy, the flat indices of
+dump_sample_index).  Every file holds finite values only: an output with a NaN or an infinity is left out, with a note on stderr
+-- the localEvidence of a full fit of a Gaussian model is NaN throughout, as in the reference (the backward pass's 0 / 0 where a
+likelihood underflows; the C4 golden holds the same), and cannot be compared value for value.  The inputs are seeded: the same
+arguments give the same inputs in every run.
 
 Multi-GPU (one process per GPU, RCCL over xGMI through libblhip.so's blhip_comm_* entry points, no PyTorch in the process):
   * under a launcher that exports RANK / LOCAL_RANK / WORLD_SIZE (the driver's ``python -m torch.distributed.run --nnodes=1
@@ -452,6 +467,47 @@ def end_to_end(bl, S, kw, units):
                          'second and later read-backs of a size), cold_ms: the first one, into a pageable array')
 
 
+DUMP_LIMIT = 64 * 2 ** 20     # bytes --dump-outputs may write in all
+DUMP_SAMPLE = 1 << 21         # entries of an output written as a sample (16 MB of float64)
+DUMP_OUTPUTS = ('logEvidence', 'localEvidence', 'posteriorMeanValues', 'logEvidenceList', 'hyperParameterDistribution', 'posteriorSequence')
+
+
+def dump_sample_index(size):
+    """Flat indices of the sample --dump-outputs writes of an output with more than DUMP_SAMPLE entries: a fixed function of the size
+    (the legacy RandomState stream does not change across numpy releases)."""
+    return np.unique(np.random.RandomState(20261016).randint(0, size, DUMP_SAMPLE))
+
+
+def dump_outputs(S, desc, where):
+    """--dump-outputs: what the last timed fit() handed its caller, as <where>/<name>.npy in float64 (see the module docstring)."""
+    os.makedirs(where, exist_ok=True)
+    total, left_out = 0, []
+    for name in DUMP_OUTPUTS:
+        if name == 'posteriorSequence' and desc.get('mode') == 'evidenceOnly':
+            continue                     # (an evidence-only fit computes no posterior sequence)
+        v = getattr(S, name, None)
+        if v is None:
+            continue
+        try:
+            a = np.atleast_1d(np.asarray(v, dtype=np.float64))
+        except (TypeError, ValueError):
+            continue
+        if a.size == 0:
+            continue
+        if a.size > DUMP_SAMPLE:
+            a, name = a.reshape(-1)[dump_sample_index(a.size)], name + '_sample'
+        bad = int(np.sum(~np.isfinite(a)))
+        if bad:
+            left_out.append('%s (%d of %d entries not finite)' % (name, bad, a.size))
+            continue
+        total += a.nbytes
+        assert total <= DUMP_LIMIT, (name, total)
+        np.save(os.path.join(where, name + '.npy'), a)
+    S.posteriorSequence = None           # (the host copy the sample was taken from)
+    if left_out:
+        sys.stderr.write('bench.py: --dump-outputs left out %s\n' % ', '.join(left_out))
+
+
 def cold_first_fit(workload='c4', timeout=300):
     """Wall time of the FIRST fit of a workload in a fresh process (library load + code-object load of ~1500 kernels + buffer
     allocation + the fit) and of the second one: what a user's first call pays.  -> dict or None."""
@@ -551,10 +607,10 @@ def _kernel_brief(rf):
     return out
 
 
-def compact_line(out):
+def compact_line(out, detail=True):
     """The ONE stdout line: the contract fields, `roofline` and `cpu_baseline` in full meaning but short form, one small record per
     extra workload.  Everything else (per-pass kernel records, configs of the extras, the exchange diagnostic's detail) is in
-    bench_detail.json.  Always < LINE_LIMIT characters (asserted; tests/test_bench_contract.py)."""
+    bench_detail.json (`detail`: it was written).  Always < LINE_LIMIT characters (asserted; tests/test_bench_contract.py)."""
     keep = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',
             'dtype', 'data', 'config', 'log_evidence', 'log_evidence_reference', 'log_evidence_rel_err', 'resident_fallbacks', 'device')
     line = {k: out[k] for k in keep if k in out}
@@ -603,7 +659,8 @@ def compact_line(out):
         line['extra'] = ex
     if isinstance(out.get('cold_first_fit'), dict) and 'first_fit_ms' in out['cold_first_fit']:
         line['cold_first_fit_ms'] = out['cold_first_fit']['first_fit_ms']
-    line['detail'] = 'bench_detail.json'
+    if detail:
+        line['detail'] = 'bench_detail.json'
     line = _sig(line)
     # full-precision where the driver or the parity gate reads it
     for k in ('value', 'ms_per_step', 'log_evidence', 'log_evidence_reference', 'log_evidence_rel_err'):
@@ -613,7 +670,7 @@ def compact_line(out):
     if len(text) >= LINE_LIMIT:                # never lose the headline: drop the side records, largest first
         for k in ('extra', 'exchange', 'end_to_end', 'kernels'):
             if k in line:
-                line[k] = 'see ' + line['detail']
+                line[k] = 'see bench_detail.json'
                 text = json.dumps(line, separators=(',', ':'))
                 if len(text) < LINE_LIMIT:
                     break
@@ -690,13 +747,19 @@ def main():
     ap.add_argument('--steps', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--workload', default='c4')
-    ap.add_argument('--no-extra', action='store_true')
-    ap.add_argument('--no-cpu', action='store_true')
-    ap.add_argument('--no-pmc', action='store_true', help='do not run the two rocprofv3 PMC passes for roofline.traffic')
-    ap.add_argument('--no-e2e', action='store_true', help='skip the end-to-end (PCIe-inclusive) fit')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: roofline, end-to-end fit, extras, cold first fit, CPU baseline, parity against the '
+                         'reference, exchange diagnostic, bench_detail.json (see the module docstring)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed as DIR/<name>.npy')
+    ap.add_argument('--no-extra', action='store_true', help='with --full: no other workloads, no cold first fit')
+    ap.add_argument('--no-cpu', action='store_true', help='with --full: no CPU baseline')
+    ap.add_argument('--no-pmc', action='store_true', help='with --full: do not run the two rocprofv3 PMC passes for roofline.traffic')
+    ap.add_argument('--no-e2e', action='store_true', help='with --full: skip the end-to-end (PCIe-inclusive) fit')
     ap.add_argument('--opt', action='append', default=[], metavar='KEY=VALUE',
                     help='engine option for an experiment (blhip_set_option), e.g. --opt max_batch=32; recorded in config.engine_options')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         self_launch(args)
@@ -734,11 +797,13 @@ def main():
     for kv in os.environ.get('BLHIP_OPTS', '').split(','):      # tuning experiments: BLHIP_OPTS=key=value,key=value
         if '=' in kv:
             eng.set_option(kv.split('=')[0], float(kv.split('=')[1]))
-    peak_cal = eng.bandwidth_probe() if rank == 0 else None
+    peak_cal = eng.bandwidth_probe() if rank == 0 and args.full else None
     S, units, desc, dt = run_workload(bl, args.workload, args.steps, args.warmup, comm, barrier)
     if comm is not None:
         dt = comm.allreduce_max(dt)
     timing = dict(S.lastTiming)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(S, desc, args.dump_outputs)
 
     out = None
     if rank == 0:
@@ -748,17 +813,17 @@ def main():
         # HBM traffic of the kernels from the PMC counters: collected now (two rocprofv3 passes over a one-fit child run) when the
         # profiler is installed, else the committed passes of the newest round under profiles/
         pmc = None
-        if world == 1 and not args.no_pmc:
+        if args.full and world == 1 and not args.no_pmc:
             nb = max(1, int(timing.get('batches', 1)))
             per_dir = {k: nb * desc['T'] for k in ('forward', 'backward')}
             pmc = pmc_traffic_in_run(args.workload, per_dir)
-        if pmc is None and world == 1 and args.workload in ('c4', 'fwd2048'):
+        if args.full and pmc is None and world == 1 and args.workload in ('c4', 'fwd2048'):
             pmc = {}
             for key in ('forward', 'backward'):
                 v, src = measured_traffic(args.workload, key)
                 if v is not None and (args.workload == 'c4' or key == 'forward'):
                     pmc[key] = dict(bytes=v, source='committed PMC passes: ' + src)
-        rf = roofline_of(timing, my_units, peak_cal, pmc)
+        rf = roofline_of(timing, my_units, peak_cal, pmc) if args.full else {}
         dom = max(rf.values(), key=lambda r: r['avg_launch_us'] * r['launches']) if rf else None
         roof = None
         if dom:
@@ -781,17 +846,17 @@ def main():
                         algorithmic=dict(dom['streaming_equiv'], note='SURVEY 8(d) accounting: the bytes a kernel that streams the state through '
                                          'HBM would move, divided by this kernel\'s time -- an equivalent rate, may exceed the peak'),
                         kernel=dom['kernel'], avg_launch_us=dom['avg_launch_us'], cells_per_launch=dom['cells_per_launch'])
-        gold = golden_log_evidence(args.workload)
         out = dict(metric='grid-cells*timesteps/sec (fit())', value=value, unit='grid-cells*timesteps/s',
                    n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=ms_per_step, higher_is_better=True,
                    scaling='strong', vs_baseline=None, dtype='f64', data='synthetic',
                    config=dict(desc, parallelism='hyper-grid points dealt round-robin to %d GPU(s), one RCCL gather + one reduce' % world,
-                               cpu_baseline='sampled (bounded subset of this workload, see cpu_baseline.sample)',
                                **({'engine_options': list(args.opt)} if args.opt else {})),
-                   log_evidence=float(S.logEvidence), log_evidence_reference=gold,
-                   log_evidence_rel_err=rel_err(float(S.logEvidence), gold), roofline=roof, kernels=rf, device=eng.device_name(),
-                   resident_fallbacks=int(timing.get('resident_fallbacks', 0)))
-    if rank == 0 and world == 1 and not args.no_e2e:
+                   log_evidence=float(S.logEvidence), device=eng.device_name(), resident_fallbacks=int(timing.get('resident_fallbacks', 0)))
+        if args.full:
+            gold = golden_log_evidence(args.workload)
+            out['config']['cpu_baseline'] = 'sampled (bounded subset of this workload, see cpu_baseline.sample)'
+            out.update(log_evidence_reference=gold, log_evidence_rel_err=rel_err(float(S.logEvidence), gold), roofline=roof, kernels=rf)
+    if rank == 0 and world == 1 and args.full and not args.no_e2e:
         kw = dict(silent=True, evidenceOnly=True) if args.workload in ('c4_evidence', 'fwd2048') else dict(silent=True)
         try:
             out['end_to_end'] = end_to_end(bl, S, kw, units)
@@ -800,7 +865,7 @@ def main():
     S._posterior_pending = None      # results stay on the device; nothing more is copied back
     eng.release_posterior()
     wedged = False
-    if comm is not None and not TEST_DOUBLE and desc.get('mode') == 'full':
+    if args.full and comm is not None and not TEST_DOUBLE and desc.get('mode') == 'full':
         # the accumulator merge on its own, both ways (every rank takes part; zero-filled accumulators of the workload's shape):
         # what the exchange costs next to one rank's share of the chains -- measured only when the driver runs N > 1.  A diagnostic:
         # it runs under a watchdog and whatever happens in it, the line with the timed result is still printed.
@@ -837,7 +902,7 @@ def main():
     if rank == 0 and world > 1:
         out['per_rank'] = dict(note='this rank (0) only: device time of its share', total_ms=timing.get('total_ms'),
                                forward_ms=timing.get('forward_ms'), backward_ms=timing.get('backward_ms'))
-    if rank == 0:
+    if rank == 0 and args.full:
         if not args.no_extra and world == 1:
             extra = {}
             for name in ('c4_evidence', 'fwd2048', 'c3', 'c2', 'c5', 'c4_both_axes', 'c4_rows1024', 'c4_wide', 'c4_laplace', 'coal_breakpoints', 'c1_hyper', 'coal_hyper1000'):
@@ -919,9 +984,10 @@ def main():
                if isinstance(v, dict) and v.get('log_evidence_rel_err') is not None and v['log_evidence_rel_err'] > registered_bound(k)]
         bad += [k + ' (per chain)' for k, v in out.get('extra', {}).items()
                 if isinstance(v, dict) and v.get('log_evidence_rel_err_per_chain') is not None and v['log_evidence_rel_err_per_chain'] > 1e-9]
-        write_detail(out)
+        if args.full:
+            write_detail(out)
         sys.stdout.flush()
-        print(compact_line(out), flush=True)     # the ONE JSON line, last on stdout, < LINE_LIMIT characters
+        print(compact_line(out, detail=args.full), flush=True)     # the ONE JSON line, last on stdout, < LINE_LIMIT characters
         if bad:
             sys.exit('bench.py: log-evidence differs from the reference by more than 1e-9 relative: %s' % bad)
     if wedged:                                   # a helper thread sits in a collective that will never return: leave without joining it

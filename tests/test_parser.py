@@ -1,16 +1,15 @@
 """bl.Parser / Study.eval (reference bayesloop/parser.py, tests/test_parser.py): the reference's known answers through this
-package's own parser, plus -- where the reference is mounted -- random queries against the reference's parser."""
+package's own parser, plus random queries against the reference's parser (its answers recorded in tests/golden/reference_parser.npz
+by tests/golden/gen_reference_random.py)."""
 import contextlib
 import io
-import math
-import os
-import sys
 import warnings
 
 import numpy as np
 import pytest
 
 import bayesloop_amd as bl
+import reference_fixtures
 from oracle_engine import OracleEngine
 
 D15 = np.array([1, 2, 3, 4, 5])
@@ -90,7 +89,6 @@ def test_errors():
         P('nonsense@1 > 1', silent=True)
 
 
-REFERENCE = '/root/reference'
 QUERIES = [
     ('rate@2 > 1.5', None), ('rate@0 + rate@4 < 6', None), ('rate2@1 - rate2@3 > 0', None), ('rate@1*rate2@1 >= 4', None),
     ('sqrt(rate@3) + exp(-rate2@0) < 2.1', None), ('rate^2 - 2*rate2 > 1', 2), ('-rate + 3 > 0', 1), ('rate/rate2 <= 1', 4),
@@ -100,40 +98,27 @@ QUERIES = [
 DISTRIBUTIONS = ['rate@1 + rate2@2', 'log(rate2@1*2*1.2)+ 4 + rate@2^2', 'rate@0*rate@3', 'exp(rate@1/3) - rate2@0']
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, 'bayesloop')), reason='reference not mounted')
 def test_random_queries_against_the_reference_parser():
-    pytest.importorskip('pyparsing')
-    sys.path.insert(0, REFERENCE)
-    np.math = math
-    try:
-        with warnings.catch_warnings():
-            warnings.simplefilter('ignore')
-            import bayesloop as ref
-        Sr, S2r = two_studies(ref)
-        S, S2 = two_studies(bl)
-        Pr, P = ref.Parser(Sr, S2r), bl.Parser(S, S2)
-        compared = 0
-        for q, t in QUERIES:
-            try:
-                with contextlib.redirect_stdout(io.StringIO()), np.errstate(all='ignore'):
-                    want = Pr(q, t=t, silent=True)
-            except (ValueError, TypeError, IndexError):
-                P(q, t=t, silent=True)                     # e.g. a sign in front of a parameter: the reference's evaluator trips, this one must not
-                continue
-            got = P(q, t=t, silent=True)
-            assert abs(got - want) <= 1e-9 + 1e-9 * abs(want), (q, got, want)
-            compared += 1
-        assert compared >= 11
-        x, p = P('sqrt(rate2@4)', silent=True)              # a bare function call (the reference's evaluator cannot do this one)
-        assert abs(p.sum() - 1.0) < 0.05 and np.all(np.diff(x) > 0)
-        for q in DISTRIBUTIONS:
-            with contextlib.redirect_stdout(io.StringIO()), np.errstate(all='ignore'):
-                xr, pr = Pr(q, silent=True)
-            x, p = P(q, silent=True)
-            np.testing.assert_allclose(x, xr, rtol=1e-12, atol=0)
-            np.testing.assert_allclose(p, pr, rtol=1e-9, atol=1e-15)
-    finally:
-        sys.path.remove(REFERENCE)
+    ref = reference_fixtures.load('parser')
+    S, S2 = two_studies(bl)
+    P = bl.Parser(S, S2)
+    compared = 0
+    for j, (q, t) in enumerate(QUERIES):
+        if 'query%d_raises' % j in ref:
+            P(q, t=t, silent=True)                         # e.g. a sign in front of a parameter: the reference's evaluator trips, this one must not
+            continue
+        want = float(ref['query%d' % j])
+        got = P(q, t=t, silent=True)
+        assert abs(got - want) <= 1e-9 + 1e-9 * abs(want), (q, got, want)
+        compared += 1
+    assert compared >= 11
+    x, p = P('sqrt(rate2@4)', silent=True)                  # a bare function call (the reference's evaluator cannot do this one)
+    assert abs(p.sum() - 1.0) < 0.05 and np.all(np.diff(x) > 0)
+    for j, q in enumerate(DISTRIBUTIONS):
+        xr, pr = ref['distribution%d/x' % j], ref['distribution%d/p' % j]
+        x, p = P(q, silent=True)
+        np.testing.assert_allclose(x, xr, rtol=1e-12, atol=0)
+        np.testing.assert_allclose(p, pr, rtol=1e-9, atol=1e-15)
 
 
 def hyper_studies(b):
@@ -165,29 +150,18 @@ HYPER_QUERIES = [
 ]
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, 'bayesloop')), reason='reference not mounted')
 def test_hyper_parameter_queries_against_the_reference_parser():
-    pytest.importorskip('pyparsing')
-    sys.path.insert(0, REFERENCE)
-    np.math = math
-    try:
-        with warnings.catch_warnings():
-            warnings.simplefilter('ignore')
-            import bayesloop as ref
-        with np.errstate(all='ignore'), warnings.catch_warnings():
-            warnings.simplefilter('ignore')
-            Pr, P = ref.Parser(*hyper_studies(ref)), bl.Parser(*hyper_studies(bl))
-        compared = 0
-        for q, t in HYPER_QUERIES:
-            try:
-                with contextlib.redirect_stdout(io.StringIO()), np.errstate(all='ignore'):
-                    want = Pr(q, t=t, silent=True)
-            except (ValueError, TypeError, IndexError):
-                P(q, t=t, silent=True)
-                continue
-            got = P(q, t=t, silent=True)
-            assert abs(got - want) <= 1e-9 + 1e-9 * abs(want), (q, got, want)
-            compared += 1
-        assert compared >= 10
-    finally:
-        sys.path.remove(REFERENCE)
+    ref = reference_fixtures.load('parser')
+    with np.errstate(all='ignore'), warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        P = bl.Parser(*hyper_studies(bl))
+    compared = 0
+    for j, (q, t) in enumerate(HYPER_QUERIES):
+        if 'hyper_query%d_raises' % j in ref:
+            P(q, t=t, silent=True)
+            continue
+        want = float(ref['hyper_query%d' % j])
+        got = P(q, t=t, silent=True)
+        assert abs(got - want) <= 1e-9 + 1e-9 * abs(want), (q, got, want)
+        compared += 1
+    assert compared >= 10
