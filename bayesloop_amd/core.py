@@ -1041,6 +1041,8 @@ class HyperStudy(Study):
             self.averagePosteriorSequence = None
             self._posteriorSequence = None
             self._posterior_pending = out['posterior']          # callable or None (non-root ranks)
+            if not out.get('contributed', True):                # no chain contributed: the reference's average is all NaN
+                self._posteriorSequence = np.full([len(self.formattedData)] + list(self.gridSize), np.nan)
             if not silent:
                 print('    + Computed average posterior sequence')
 
@@ -1073,7 +1075,7 @@ class HyperStudy(Study):
         self.logEvidenceList, localList = [], []
         eng = _engine_mod.get_engine()
         want_post = not evidenceOnly
-        n_fold, begun = 0, False
+        n_fold, begun, done = 0, False, False
         try:
             for k, row in enumerate(self.hyperGridValues):
                 self._setAllHyperParameters(row)
@@ -1088,16 +1090,24 @@ class HyperStudy(Study):
                     with np.errstate(divide='ignore'):
                         eng.accum_fold_host(seq, self.logEvidence + np.log(prior_values[k]))
                     n_fold += 1 if prior_values[k] > 0 else 0
+            done = True
         finally:
             self._setAllHyperParameters(self.flatHyperParameters)
+            if begun and (not done or n_fold == 0):      # (an accumulator nothing went into, or a loop that raised: closed, owned by nobody)
+                eng.accum_end()
+                if hasattr(eng, 'accum_set_owner'):
+                    eng.accum_set_owner(None)
         if want_post:
-            self._posteriorSequence = None
+            T = len(self.formattedData)
             self._posterior_pending = None
             self.averagePosteriorSequence = None
-            self.posteriorMeanValues = []
+            # no chain contributed (every logEvidence non-finite or every hyper-prior value 0): the reference's average is
+            # exp(-inf - -inf) = NaN everywhere, and so are its means (core.py:1375-1382, :1416-1419)
+            self._posteriorSequence = np.full([T] + list(self.gridSize), np.nan)
+            self.posteriorMeanValues = np.full((len(self.gridSize), T), np.nan)
             if n_fold > 0:
                 # (marginal grids and lattice are all accum_finalize reads of the problem: per-step normalisation and the means of the average)
-                T = len(self.formattedData)
+                self._posteriorSequence = None
                 shell = FitProblem(obs_model=device_code(self.observationModel), marginal=self.marginalGrid, lattice=self.latticeConstant,
                                    data=np.zeros((T, 1)), timestamps=np.zeros(T), prior=np.ones(int(np.prod(self.gridSize))), ops=[])
                 self.posteriorMeanValues = eng.accum_finalize(shell)

@@ -175,6 +175,11 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
     struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } builder_guard{builder};      // (also when a batch throws)
     const bool build_ahead = nbatch > 1;
     int64_t fallback_until = -1;                   // batches up to this one repeat on the launch-per-step kernels (poisoned carried slots, below)
+    // per batch of the call: its contribution went into the carried partial accumulators (a fused fold with a finite reference), not
+    // into the accumulator itself.  The repeat after poisoned slots folds only such batches again: a batch that was folded directly
+    // (not chain-resident, or repeated in place after its forward check) is in the accumulator already.
+    std::vector<char> in_slots((size_t)nbatch, 0);
+    int64_t refold_before = -1;                    // batches below this one that a repeat re-runs are folded again only if in_slots
     for (int64_t bi = 0; bi < nbatch; ++bi) {
         const int64_t c0 = batch_start[bi], B = batch_start[bi + 1] - c0;
         tr.mark("batch setup");
@@ -713,9 +718,12 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
                 ctx->timing.resident_fallbacks += 1;
                 ctx->timing.resident_fallback_reason = ctx->resident_last_reason ? ctx->resident_last_reason : BLHIP_FALLBACK_RANGE;
                 if (CR.on && CR.touched_parts && !CR.part_fresh0) {
-                    // the failed backward pass has added to partial accumulators that carry earlier batches of this call: none of them is in
-                    // the average posterior yet -- those batches and this one are repeated on the launch-per-step kernels
+                    // the failed backward pass has added to partial accumulators that carry earlier batches of this call: the slots are
+                    // dropped, and the batches since the first one they carry and this one are repeated on the launch-per-step kernels.
+                    // Batches of that range that were folded directly into the accumulator (in_slots = 0: not chain-resident, or repeated
+                    // in place) are in the average posterior already: their repeat skips the fold
                     const int64_t from = ctx->part.live ? ctx->part.first_batch : bi;
+                    refold_before = bi;
                     ctx->part = blhip_ctx::PartState{};
                     ctx->timing.forward_ms = ctx->timing.backward_ms = 0.0;
                     ctx->timing.fwd_hbm_bytes = ctx->timing.bwd_hbm_bytes = ctx->timing.fwd_flops = ctx->timing.bwd_flops = 0.0;
@@ -752,8 +760,11 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
             else { fin = fused1d ? d_pp[((T - 1) / usedK) & 1] : d_pp[(T - 1) & 1]; fstr = G; }
             store_carry(ctx, p, B, G, redF, fin, fstr, d_w, prog.has_clamp);
         }
-        if (accumulate && CR.fold_done) {
-            // (the backward kernel folded this batch)
+        // (a repeat after poisoned carried slots: a batch before the failed one that did not fold into the slots is in the accumulator already)
+        const bool refold_skip = bi < refold_before && !in_slots[bi];
+        in_slots[bi] = CR.on && !resident_failed && CR.fused && CR.fold_done && std::isfinite(CR.fold_ref);
+        if (accumulate && (CR.fold_done || refold_skip)) {
+            // (the backward kernel folded this batch, or it was folded before)
         } else if (accumulate && overlap_acc) {
             // private copies of the weights, host (page-locked: the copies must not block the host) and device: the batch metadata
             // buffers are rewritten by the next batch while the fold is pending / running
@@ -984,7 +995,7 @@ int blhip_set_option(blhip_ctx *ctx, const char *key, double value) {
     // (a key the library never reads is an error, not a silent no-op: an A/B run over a removed option measured nothing -- ADVICE r05)
     static const char *const known[] = {
         "accum_overlap", "carry_partials", "chain1d", "chain1d_clamp", "chain1d_shift", "chain_ax1", "chain_depad", "chain_prof", "chain_resident", "chain_resident_lag",
-        "chain_table", "chain_wide", "comm_reduce_mode", "fast", "fast_S", "fold2", "fold2_cp", "fold_force_fail_batch", "fuse1d", "fuse_accumulate", "late_sums", "max_batch",
+        "chain_force_fail_batch", "chain_force_fail_stage", "chain_table", "chain_wide", "comm_reduce_mode", "fast", "fast_S", "fold2", "fold2_cp", "fold_force_fail_batch", "fuse1d", "fuse_accumulate", "late_sums", "max_batch",
         "mem_budget_bytes", "mfma", "mfma_S", "mfma_h", "mfma_h_max_cells", "peer_copy_mode", "persist1d", "quiet", "recurrence", "resident",
         "resident_force_abort", "resident_lag", "resident_probe", "resident_probe_force_busy", "resident_probe_interval_s", "resident_probe_timeout_s",
         "resident_table", "resident_timeout_s", "share_prefix", "short_first_batch", "skip_prefix", "trace", "wide_h",

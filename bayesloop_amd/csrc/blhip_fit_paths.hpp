@@ -37,13 +37,14 @@ inline double resident_timeout_s(blhip_ctx *ctx, int64_t T) {
 }
 
 // did a block of a resident launch time out waiting for a peer (not every block co-resident)?  -> the context stops using the paths
-bool resident_gave_up(blhip_ctx *ctx, hipStream_t st, const unsigned *d_abort) {
+// (force: a test pretends that a block gave up -- chain_force_fail_stage 3; the same side effects as a real give-up)
+bool resident_gave_up(blhip_ctx *ctx, hipStream_t st, const unsigned *d_abort, bool force = false) {
     ctx->pinS.ensure(64);
     unsigned *h = reinterpret_cast<unsigned *>(ctx->pinS.as<char>());
     HIPCHECK(hipMemcpyAsync(h, d_abort, 4, hipMemcpyDeviceToHost, st));
     sync_stream(ctx, st);
     // (option resident_force_abort: the tests of the fall-back pretend that a block gave up)
-    if (*h != 0u || ctx->option("resident_force_abort", 0.0) != 0.0) {
+    if (*h != 0u || force || ctx->option("resident_force_abort", 0.0) != 0.0) {
         ctx->resident_last_reason = *h != 0u ? BLHIP_FALLBACK_GAVE_UP : BLHIP_FALLBACK_FORCED;
         if (ctx->resident_ok && ctx->option("quiet", 0.0) == 0.0)
             std::fprintf(stderr, "[blhip] a resident launch gave up waiting for a peer block (its blocks were not all co-resident: a shared or "
@@ -290,6 +291,13 @@ void flush_partials(blhip_ctx *ctx, hipStream_t st, std::vector<hipEvent_t> *lat
     ctx->timing.accumulate_launches += 1;
     ctx->acc_logref = newref; ctx->acc_first = false; ctx->acc_folded += ps.nfold;
     ps = blhip_ctx::PartState{};
+}
+
+// Tests of the fall-backs of a mixed call: options chain_force_fail_batch (a batch index of the call; -1 off) and chain_force_fail_stage
+// pretend that ONE batch's host check failed -- 1: forward_ok (range), 2: backward_ok (range), 3: a give-up seen after the backward pass.
+// Only what the check returns changes: no kernel argument, no in-kernel time-out.
+inline bool chain_forced_fail(const BatchEnv &E, int stage) {
+    return (int64_t)E.ctx->option("chain_force_fail_batch", -1.0) == E.bi && (int)E.ctx->option("chain_force_fail_stage", 0.0) == stage;
 }
 
 struct ChainRun {
@@ -647,6 +655,7 @@ struct ChainRun {
     // after the forward pass: every strip made it, and the sums of every chain allow the scales to be undone
     bool forward_ok(const BatchEnv &E, double *redF) {
         if (resident_gave_up(E.ctx, E.st, d_abort)) return false;
+        if (chain_forced_fail(E, 1)) { E.ctx->resident_last_reason = BLHIP_FALLBACK_RANGE; return false; }
         redF_keep = redF;
         if (skip_prefix)               // the steps a chain did not compute: the providing chain's sums (raw: before anybody's scales are undone)
             for (int64_t b = 0; b < E.B; ++b)
@@ -704,7 +713,8 @@ struct ChainRun {
 
     // after the backward pass: every strip made it and the lagged scale of the backward state stayed in range
     bool backward_ok(const BatchEnv &E, const double *redB) {
-        if (resident_gave_up(E.ctx, E.st, d_abort)) return false;
+        if (resident_gave_up(E.ctx, E.st, d_abort, chain_forced_fail(E, 3))) return false;
+        if (chain_forced_fail(E, 2)) { E.ctx->resident_last_reason = BLHIP_FALLBACK_RANGE; return false; }
         const size_t n = (size_t)E.T * E.B;             // (every record of the pass, in memory order)
         for (size_t q = 0; q < n; ++q) {
             const double *r = &redB[q * NRED];

@@ -338,7 +338,7 @@ def sharded_hyper_fit(engine, problem, op_values, prior_values, comm, forward_on
                 gstats = sum(scale[r] * parts[r][width * (T + 2) + 1:].reshape(T, 1 + ndim) for r in range(size)
                              if scale[r] > 0.0)
 
-    means, posterior = None, None
+    means, posterior, ok = None, None, False
     if want_post:
         ok = bool(np.isfinite(gref))
         if ok and comm is not None:
@@ -365,9 +365,16 @@ def sharded_hyper_fit(engine, problem, op_values, prior_values, comm, forward_on
             posterior = DevicePosterior(engine, 1, T, grid_size)     # lazy D2H / device-side reductions of the average
         elif ok:
             means = (gstats[:, 1:] / gstats[:, :1]).T                # core.py:1416-1419 from the gathered per-step sums
+        else:
+            # no chain contributed (every logEvidence non-finite or every hyper-prior value 0): the reference's average is
+            # exp(-inf - -inf) = NaN everywhere (core.py:1375-1382), and so are its means; nothing lives in the accumulator
+            engine.accum_end()
+            if hasattr(engine, 'accum_set_owner'):
+                engine.accum_set_owner(None)
+            means = np.full((ndim, T), np.nan)
 
     return dict(log_evidence=np.asarray(logE), local_evidence=np.asarray(local), abort_step=np.asarray(astep),
-                posterior_mean=means, posterior=posterior, timing=timing)
+                posterior_mean=means, posterior=posterior, timing=timing, contributed=ok)
 
 
 # ---- several GPUs driven by ONE process: HyperStudy.fit(nJobs = N) ------------------------------------------------------------

@@ -173,6 +173,9 @@ class OracleEngine:
         self.acc_log = np.zeros((T, G)) - np.inf
         self.acc_lin = None
 
+    def accum_set_owner(self, owner):
+        self._accum_owner = owner
+
     def accum_fold_host(self, posterior, log_weight):
         """as HipEngine.accum_fold_host: one chain whose posterior sequence the caller holds (log_weight = logEvidence + log prior value)"""
         if np.isfinite(log_weight):

@@ -488,3 +488,73 @@ def test_online_study_refuses_user_defined_transition_models():
             O.add('m', tm)
             with pytest.raises(ConfigurationError, match='user-defined'):
                 O.step(1.0)
+
+
+# ---- a hyper-study to which no chain contributes (every logEvidence -inf): the reference's average posterior and its means are all NaN
+#      (core.py:1375-1382, :1416-1419), the hyper-parameter distribution NaN, the evidence -inf -- on the device path (dist.sharded_hyper_fit)
+#      and on the host-transition path (HyperStudy._fitHostTransitionHyper); the accumulator is closed and owned by nobody afterwards
+
+def no_chain_case():
+    # a zero normaliser at step 2 in every chain (500 lies ~1000 standard deviations off the grid)
+    return dict(study='HyperStudy', data=np.array([0.2, 0.1, 500.0, 0.3, -0.1]),
+                om=('Gaussian', [('mean', ('cint', -2, 2, 32)), ('std', ('oint', 0, 0.5, 32))], 'default'),
+                tm=('GRW', 'sigma', [0.05, 0.1, 0.2], 'mean', None))
+
+
+def host_walk(values):
+    """A user-defined random walk (plain NumPy / SciPy, reference plug-in interface): HyperStudy.fit takes the host-transition path."""
+    import plugin_models
+    return plugin_models.make(bl.tm)['LeakyRandomWalk']('sigma', values, 'leak', 0.0, target='mean')
+
+
+def check_no_chain_result(S, want):
+    assert S.logEvidence == want['logEvidence'] == -np.inf
+    wp = np.asarray(want['posteriorSequence'])
+    assert np.all(np.isnan(wp)) and np.all(np.isnan(want['posteriorMeanValues']))
+    for post in (np.asarray(S.posteriorSequence), np.asarray(S.averagePosteriorSequence)):
+        assert post.shape == wp.shape and np.all(np.isnan(post))
+    means = np.asarray(S.posteriorMeanValues, dtype=float)
+    assert means.shape == np.asarray(want['posteriorMeanValues']).shape and np.all(np.isnan(means))
+    np.testing.assert_array_equal(np.isnan(S.hyperParameterDistribution), np.isnan(want['hyperParameterDistribution']))
+    assert np.all(np.isneginf(S.logEvidenceList)) and np.all(np.isneginf(want['logEvidenceList']))
+
+
+@pytest.mark.parametrize('host_transition', [False, True])
+def test_hyper_study_without_a_contributing_chain(host_transition):
+    from bayesloop_amd import transitionModels as tmm
+    c = no_chain_case()
+    with np.errstate(all='ignore'):
+        want = oa.run(c)
+    S = cases.build(bl, c)
+    if host_transition:
+        S.set(host_walk([0.05, 0.1, 0.2]), silent=True)
+    assert tmm.needs_host_transition(S.transitionModel) == host_transition
+    with np.errstate(all='ignore'):
+        S.fit(silent=True)
+    check_no_chain_result(S, want)
+    assert getattr(bl.get_engine(), '_accum_owner', None) is None
+
+
+def test_host_transition_hyper_study_closes_the_accumulator_when_a_fit_raises():
+    """An exception inside the per-point loop of the host-transition path leaves no accumulator open and owned by the study."""
+    eng = bl.get_engine()
+    ended = []
+    orig_end = eng.accum_end
+    eng.accum_end = lambda: (ended.append(1), orig_end())[1]
+
+    walk = host_walk([0.05, 0.1, 0.2])
+    forward = walk.computeForwardPrior
+
+    def failing(posterior, t):
+        if walk.hyperParameterValues[0] > 0.15:
+            raise RuntimeError('user model failed')
+        return forward(posterior, t)
+    walk.computeForwardPrior = failing
+
+    S = bl.HyperStudy(silent=True)
+    S.loadData(cases.series(5, 12), silent=True)
+    S.set(bl.om.Gaussian('mean', bl.cint(-4, 4, 24), 'std', bl.oint(0, 3, 16)), walk, silent=True)
+    with pytest.raises(RuntimeError, match='user model failed'):
+        S.fit(silent=True)
+    assert ended == [1]
+    assert getattr(eng, '_accum_owner', None) is None
