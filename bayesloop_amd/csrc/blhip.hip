@@ -748,8 +748,10 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
         }
 
         if (CR.on && CR.depad && !resident_failed && !evidence_only) {
-            BL_LAUNCH(depad_kernel, dim3((unsigned)((G + NTHREADS - 1) / NTHREADS), (unsigned)(B * T)), dim3(NTHREADS), 0, st, d_post,
-                               ctx->postpad.as<double>(), g.n0, g.n1, CR.cp.n0p, CR.Gk, (int)T, CR.ax1 ? 1 : 0);
+            for_grid_y(ctx, (long long)B * T, [&](long long y0, unsigned ny) {
+                BL_LAUNCH(depad_kernel, dim3((unsigned)((G + NTHREADS - 1) / NTHREADS), ny), dim3(NTHREADS), 0, st, d_post,
+                                   ctx->postpad.as<double>(), g.n0, g.n1, CR.cp.n0p, CR.Gk, (int)T, CR.ax1 ? 1 : 0, y0);
+            });
             HIPCHECK(hipGetLastError());
         }
 
@@ -922,6 +924,7 @@ blhip_ctx *blhip_create(int device) {
         hipDeviceProp_t prop;
         HIPCHECK(hipGetDeviceProperties(&prop, device));
         ctx->num_cus = prop.multiProcessorCount;
+        if (prop.maxGridSize[1] > 0) ctx->max_grid_y = prop.maxGridSize[1];
         std::string marketing = prop.name;
         if (marketing.find_first_not_of(' ') == std::string::npos) marketing = "AMD Instinct (name not reported by the driver)";
         ctx->name = marketing + " (" + prop.gcnArchName + ")";
@@ -1196,10 +1199,14 @@ int blhip_posterior_marginal(blhip_ctx *ctx, int source, int64_t chain, int keep
         if (one_d) {
             HIPCHECK(hipMemcpyAsync(d_out, v.p, (size_t)v.T * nk * 8, hipMemcpyDeviceToDevice, st));
         } else if (keep_axis == 0) {
-            BL_LAUNCH(marginal_rows_kernel, dim3(v.n0, (unsigned)v.T), dim3(NTHREADS), 0, st, v.p, d_out, v.n0, v.n1);
+            for_grid_y(ctx, v.T, [&](long long t0, unsigned nt) {
+                BL_LAUNCH(marginal_rows_kernel, dim3(v.n0, nt), dim3(NTHREADS), 0, st, v.p + (size_t)t0 * v.n0 * v.n1, d_out + (size_t)t0 * nk, v.n0, v.n1);
+            });
         } else {
-            BL_LAUNCH(marginal_cols_kernel, dim3((v.n1 + NTHREADS - 1) / NTHREADS, (unsigned)v.T), dim3(NTHREADS), 0, st,
-                               v.p, d_out, v.n0, v.n1);
+            for_grid_y(ctx, v.T, [&](long long t0, unsigned nt) {
+                BL_LAUNCH(marginal_cols_kernel, dim3((v.n1 + NTHREADS - 1) / NTHREADS, nt), dim3(NTHREADS), 0, st,
+                                   v.p + (size_t)t0 * v.n0 * v.n1, d_out + (size_t)t0 * nk, v.n0, v.n1);
+            });
         }
         HIPCHECK(hipMemcpyAsync(host_out, d_out, (size_t)v.T * nk * 8, hipMemcpyDeviceToHost, st));
         sync_stream(ctx, st);
@@ -1397,7 +1404,9 @@ RowStats accum_row_stats(blhip_ctx *ctx, const blhip_problem *p) {
         HIPCHECK(hipMemcpyAsync(dm, p->marginal[k], 8 * (size_t)p->n[k], hipMemcpyHostToDevice, st));
         ng.m[k] = dm;
     }
-    BL_LAUNCH(bln::row_stats_kernel, dim3(gx, (unsigned)T), dim3(NTHREADS), 0, st, ctx->acc, ng, d_part);
+    for_grid_y(ctx, T, [&](long long t0, unsigned nt) {
+        BL_LAUNCH(bln::row_stats_kernel, dim3(gx, nt), dim3(NTHREADS), 0, st, ctx->acc + (size_t)t0 * G, ng, d_part + (size_t)t0 * 5 * gx);
+    });
     BL_LAUNCH(reduce_partials_kernel, dim3((unsigned)(T * RS_W)), dim3(NTHREADS), 0, st, d_part, d_red, (int)gx, 0);
     ctx->pinS.ensure((size_t)T * (RS_W + 1) * 8);
     double *red = ctx->pinS.as<double>();
@@ -1439,7 +1448,9 @@ int blhip_accum_finalize(blhip_ctx *ctx, const blhip_problem *p, double *posteri
         }
         HIPCHECK(hipMemcpyAsync(d_inv, inv, T * 8, hipMemcpyHostToDevice, st));
         const unsigned gs = (unsigned)std::min<long long>((G + NTHREADS - 1) / NTHREADS, 4096);
-        BL_LAUNCH(scale_rows_kernel, dim3(gs, (unsigned)T), dim3(NTHREADS), 0, st, ctx->acc, (long long)G, d_inv);
+        for_grid_y(ctx, T, [&](long long t0, unsigned nt) {
+            BL_LAUNCH(scale_rows_kernel, dim3(gs, nt), dim3(NTHREADS), 0, st, ctx->acc + (size_t)t0 * G, (long long)G, d_inv + t0);
+        });
         sync_stream(ctx, st);
         ctx->acc_final = true;
     });

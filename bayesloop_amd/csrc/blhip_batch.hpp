@@ -12,8 +12,10 @@ void ensure_post_scaled(blhip_ctx *ctx) {
     // (rows [post_row0, post_row1) only: the time-resident kernel has normalised the others itself)
     const int64_t r0 = ctx->post_row0, nrows = ctx->post_row1 - ctx->post_row0;
     for (int64_t b = 0; b < ctx->post_chains && nrows > 0; ++b)
-        BL_LAUNCH(scale_rows_kernel, dim3(gx, (unsigned)nrows), dim3(NTHREADS), 0, ctx->stream,
-                           ctx->post.as<double>() + ((size_t)b * ctx->post_T + r0) * G, G, ctx->postinv.as<double>() + b * ctx->post_T + r0);
+        for_grid_y(ctx, nrows, [&](long long y0, unsigned ny) {
+            BL_LAUNCH(scale_rows_kernel, dim3(gx, ny), dim3(NTHREADS), 0, ctx->stream,
+                               ctx->post.as<double>() + ((size_t)b * ctx->post_T + r0 + y0) * G, G, ctx->postinv.as<double>() + b * ctx->post_T + r0 + y0);
+        });
     HIPCHECK(hipGetLastError());
     ctx->post_scaled = true;
 }
@@ -185,8 +187,10 @@ DeviceTables upload_tables(blhip_ctx *ctx, const blhip_problem *p, const Geometr
             ctx->databuf.ensure(nd * 8);
             HIPCHECK(hipMemcpyAsync(ctx->databuf.p, p->data, nd * 8, hipMemcpyHostToDevice, st));
             const unsigned gx = (unsigned)std::min<long long>((G + NTHREADS - 1) / NTHREADS, 2048);
-            BL_LAUNCH(lik_table_kernel, dim3(gx, (unsigned)T), dim3(NTHREADS), 0, st, table_model, D.lik, (long long)G, g.n1,
-                               p->ndim, D.m0, D.m1, ctx->databuf.as<double>(), p->seg_len, p->data_dim);
+            for_grid_y(ctx, T, [&](long long t0, unsigned nt) {
+                BL_LAUNCH(lik_table_kernel, dim3(gx, nt), dim3(NTHREADS), 0, st, table_model, D.lik + (size_t)t0 * G, (long long)G, g.n1,
+                                   p->ndim, D.m0, D.m1, ctx->databuf.as<double>() + (size_t)t0 * p->seg_len * p->data_dim, p->seg_len, p->data_dim);
+            });
             HIPCHECK(hipGetLastError());
         } else {
             HIPCHECK(hipMemcpyAsync(D.lik, p->lik, sizeof(double) * T * G, hipMemcpyHostToDevice, st));
@@ -575,22 +579,31 @@ void launch_fold(blhip_ctx *ctx, int64_t T, long long G, const FoldJob &job, hip
     HIPCHECK(hipMemcpyAsync(job.d_w, job.h_w, B * 8, hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(job.d_invN, job.h_invN, (size_t)T * B * 8, hipMemcpyHostToDevice, st));
     HIPCHECK(hipEventRecord(ev0, st));
+    // (steps [t0, t0 + nt) per launch: the accumulator, the sequences and the row normalisers invN[b * T + t] all move by t0 steps)
     if (job.pad_n0p > 0) {
-        BL_LAUNCH(accumulate_pad_kernel, dim3((unsigned)((G + NTHREADS - 1) / NTHREADS), (unsigned)T), dim3(NTHREADS), 0, st, ctx->acc,
-                           job.d_post, (long long)T * job.pad_step, (int)B, job.pad_n0, job.pad_n1, (int)T, job.d_w, job.d_invN, job.r, job.first,
-                           job.pad_n0p, job.pad_step, job.pad_ax);
+        for_grid_y(ctx, T, [&](long long t0, unsigned nt) {
+            BL_LAUNCH(accumulate_pad_kernel, dim3((unsigned)((G + NTHREADS - 1) / NTHREADS), nt), dim3(NTHREADS), 0, st, ctx->acc,
+                               job.d_post, (long long)T * job.pad_step, (int)B, job.pad_n0, job.pad_n1, (int)T, job.d_w, job.d_invN, job.r, job.first,
+                               job.pad_n0p, job.pad_step, job.pad_ax, (int)t0);
+        });
     } else if (job.sm_n0 == 0 && B >= 16 && ((G / 2 + NTHREADS - 1) / NTHREADS) * T < 1024) {        // small grids: too few blocks with a thread per cell
-        BL_LAUNCH(accumulate_small_kernel, dim3((unsigned)((G + 63) / 64), (unsigned)T), dim3(NTHREADS), 0, st, ctx->acc, job.d_post,
-                           (long long)T * G, (int)B, G, (int)T, job.d_w, job.d_invN, job.r, job.first);
+        for_grid_y(ctx, T, [&](long long t0, unsigned nt) {
+            BL_LAUNCH(accumulate_small_kernel, dim3((unsigned)((G + 63) / 64), nt), dim3(NTHREADS), 0, st, ctx->acc + (size_t)t0 * G, job.d_post + (size_t)t0 * G,
+                               (long long)T * G, (int)B, G, (int)T, job.d_w, job.d_invN + t0, job.r, job.first);
+        });
     } else if ((G & 1) == 0 && ((uintptr_t)ctx->acc & 15) == 0) {
         const unsigned gx2 = (unsigned)((G / 2 + NTHREADS - 1) / NTHREADS);
-        BL_LAUNCH(accumulate2_kernel, dim3(gx2, (unsigned)T), dim3(NTHREADS), 0, st, ctx->acc, job.d_post,
-                           (long long)T * G, (int)B, G, (int)T, job.d_w, job.d_invN, job.r, job.first, job.sm_n0);
+        for_grid_y(ctx, T, [&](long long t0, unsigned nt) {
+            BL_LAUNCH(accumulate2_kernel, dim3(gx2, nt), dim3(NTHREADS), 0, st, ctx->acc + (size_t)t0 * G, job.d_post + (size_t)t0 * G,
+                               (long long)T * G, (int)B, G, (int)T, job.d_w, job.d_invN + t0, job.r, job.first, job.sm_n0);
+        });
     } else {
         if (job.sm_n0 > 0) fail("internal: strip-major sequences need an even number of cells and a 16-byte aligned accumulator");
         const unsigned gx = (unsigned)std::min<long long>((G + NTHREADS - 1) / NTHREADS, 4096);
-        BL_LAUNCH(accumulate_kernel, dim3(gx, (unsigned)T), dim3(NTHREADS), 0, st, ctx->acc, job.d_post,
-                           (long long)T * G, (int)B, G, (int)T, job.d_w, job.d_invN, job.r, job.first);
+        for_grid_y(ctx, T, [&](long long t0, unsigned nt) {
+            BL_LAUNCH(accumulate_kernel, dim3(gx, nt), dim3(NTHREADS), 0, st, ctx->acc + (size_t)t0 * G, job.d_post + (size_t)t0 * G,
+                               (long long)T * G, (int)B, G, (int)T, job.d_w, job.d_invN + t0, job.r, job.first);
+        });
     }
     HIPCHECK(hipEventRecord(ev1, st));
 }

@@ -283,9 +283,11 @@ void flush_partials(blhip_ctx *ctx, hipStream_t st, std::vector<hipEvent_t> *lat
         later_ev->push_back(e0); later_ev->push_back(e1);
         HIPCHECK(hipEventRecord(e0, st));
     }
-    BL_LAUNCH(fold_parts_kernel, dim3((unsigned)(((G + 1) / 2 + NTHREADS - 1) / NTHREADS), (unsigned)ps.T), dim3(NTHREADS), 0, st, ctx->acc,
-                       ctx->accpart.as<double>(), (long long)ps.T * ps.Gk, ps.slots_init, ps.n0, ps.n1, ps.T, r, rb,
-                       ctx->acc_first ? 1 : 0, ps.n0p, ps.Gk, ps.ax1);
+    for_grid_y(ctx, ps.T, [&](long long t0, unsigned nt) {
+        BL_LAUNCH(fold_parts_kernel, dim3((unsigned)(((G + 1) / 2 + NTHREADS - 1) / NTHREADS), nt), dim3(NTHREADS), 0, st, ctx->acc,
+                           ctx->accpart.as<double>(), (long long)ps.T * ps.Gk, ps.slots_init, ps.n0, ps.n1, ps.T, r, rb,
+                           ctx->acc_first ? 1 : 0, ps.n0p, ps.Gk, ps.ax1, (int)t0);
+    });
     HIPCHECK(hipGetLastError());
     if (later_ev) HIPCHECK(hipEventRecord(e1, st));
     ctx->timing.accumulate_launches += 1;

@@ -73,6 +73,7 @@ thread_local std::string g_create_error;
 
 struct blhip_ctx {
     int device = 0;
+    long long max_grid_y = 65535;        // hipDeviceProp_t::maxGridSize[1] of the device (blhip_create); see for_grid_y
     hipStream_t stream = nullptr;
     hipEvent_t ev[8] = {};
     // radius buckets of a batch are independent pipelines: one stream per bucket key, joined with events
@@ -178,6 +179,14 @@ struct Trace {
         t0 = t1;
     }
 };
+
+// A launch whose gridDim.y counts time steps, rows of a sequence or chains x steps: the device takes at most max_grid_y (65 536 on gfx950)
+// per launch, a long 1-D series or a kept batch of many chains has more -- launch(y0, ny) once per piece of at most that many.
+template <class F>
+void for_grid_y(const blhip_ctx *ctx, long long ny, F &&launch) {
+    const long long lim = std::max<long long>(1, ctx->max_grid_y);
+    for (long long y0 = 0; y0 < ny; y0 += lim) launch(y0, (unsigned)std::min<long long>(lim, ny - y0));
+}
 
 void sync_stream(blhip_ctx *ctx, hipStream_t st) {
     HIPCHECK(hipEventRecord(ctx->sync_ev, st));

@@ -647,9 +647,9 @@ static __global__ __launch_bounds__(NTHREADS) void accumulate_small_kernel(doubl
 // (n0p: rows per strip of the partials -- the kernel's padded row count when the grid's is not 128 / 256 / 512; pstep: doubles per time
 //  step of a partial accumulator on that padded geometry)
 static __global__ __launch_bounds__(NTHREADS) void fold_parts_kernel(double *A, const double *part, long long part_stride, int nslots, int n0, int n1,
-                                                               int T, double r, double rb, int first, int n0p, long long pstep, int ax) {
+                                                               int T, double r, double rb, int first, int n0p, long long pstep, int ax, int t0) {
     const long long G = (long long)n0 * n1;
-    const int t = blockIdx.y;
+    const int t = t0 + (int)blockIdx.y;          // (t0: launches of more steps than gridDim.y holds go in pieces, for_grid_y)
     if (ax && ax_layout_b(t)) {            // the transposed layout of the both-axes kernels: one cell per lane
         for (int h = 0; h < 2; ++h) {
             const long long c = ((long long)blockIdx.x * NTHREADS + threadIdx.x) * 2 + h;
@@ -664,7 +664,9 @@ static __global__ __launch_bounds__(NTHREADS) void fold_parts_kernel(double *A, 
         }
         return;
     }
-    if (n1 & 1) {                          // an odd number of columns: pairs of cells would straddle rows -- one cell per lane
+    // an odd number of columns: pairs of cells would straddle rows; a caller-owned accumulator (blhip_accum_begin: external_devptr) that is
+    // not 16-byte aligned: no double2 access to it (the condition launch_fold makes for accumulate2_kernel) -- one cell per lane
+    if ((n1 & 1) || (reinterpret_cast<uintptr_t>(A) & 15)) {
         for (int h = 0; h < 2; ++h) {
             const long long c = ((long long)blockIdx.x * NTHREADS + threadIdx.x) * 2 + h;
             if (c >= G) return;
@@ -699,9 +701,9 @@ static __global__ __launch_bounds__(NTHREADS) void fold_parts_kernel(double *A, 
 // ([t][column / 16][row of n0p][16], pstep doubles per time step, chain_stride per chain): one cell per lane (any number of columns).
 static __global__ __launch_bounds__(NTHREADS) void accumulate_pad_kernel(double *A, const double *post, long long chain_stride, int B, int n0, int n1,
                                                                   int T, const double *w, const double *invN, double r, int first,
-                                                                  int n0p, long long pstep, int ax) {
+                                                                  int n0p, long long pstep, int ax, int t0) {
     const long long G = (long long)n0 * n1;
-    const long long t = blockIdx.y;
+    const long long t = (long long)t0 + blockIdx.y;
     const long long c = (long long)blockIdx.x * NTHREADS + threadIdx.x;
     if (c >= G) return;
     const int row = (int)(c / n1), col = (int)(c - (long long)row * n1);
@@ -807,13 +809,15 @@ static __global__ __launch_bounds__(NTHREADS) void marginal_cols_kernel(const do
 
 // A sequence the chain-resident kernels left in their strip-major layout on a PADDED geometry ([t][column / 16][row of n0p][16], pstep
 // doubles per time step) -> the row-major sequence of the grid itself ([t][n0][n1]) that every consumer outside the fit reads.
-// blockIdx.y = chain * T + t; lanes run along the destination (coalesced stores, 128-byte runs of the source).
-static __global__ __launch_bounds__(NTHREADS) void depad_kernel(double *dst, const double *src, int n0, int n1, int n0p, long long pstep, int T, int ax) {
+// y0 + blockIdx.y = chain * T + t; lanes run along the destination (coalesced stores, 128-byte runs of the source).
+static __global__ __launch_bounds__(NTHREADS) void depad_kernel(double *dst, const double *src, int n0, int n1, int n0p, long long pstep, int T, int ax,
+                                                         long long y0) {
     const long long G = (long long)n0 * n1;
     const long long c = (long long)blockIdx.x * NTHREADS + threadIdx.x;
     if (c >= G) return;
+    const long long y = y0 + blockIdx.y;
     const int row = (int)(c / n1), col = (int)(c - (long long)row * n1);
-    dst[(long long)blockIdx.y * G + c] = __builtin_nontemporal_load(src + (long long)blockIdx.y * pstep + strip_major_index(row, col, n0p, (int)(blockIdx.y % (unsigned)T), ax));
+    dst[y * G + c] = __builtin_nontemporal_load(src + y * pstep + strip_major_index(row, col, n0p, (int)(y % T), ax));
 }
 
 // out[c] = (1/T) sum_t p[t][c]
