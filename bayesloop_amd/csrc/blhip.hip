@@ -209,6 +209,8 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
         // --- device metadata ---
         DeviceMeta M;
         upload_metadata(ctx, p, prog, taps, B, full, fast, tile.nblk, M, gp.wideH, gp.wideV, gp.hSplit, gp.hFusedMax);
+        StageMeta SM;                            // (composed transitions only: the stages in front of the fused step kernel)
+        if (prog.multi) upload_stages(ctx, prog, B, G, tile.nblk, full, SM);
         unsigned char *const d_kindF = M.kindF, *const d_kindB = M.kindB, *const d_cmodeF = M.cmodeF, *const d_cmodeB = M.cmodeB;
         double *const d_limitF = M.limitF, *const d_limitB = M.limitB;
         int *const d_tapF0 = M.tapF0, *const d_tapF1 = M.tapF1, *const d_tapB0 = M.tapB0, *const d_tapB1 = M.tapB1;
@@ -432,6 +434,24 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
                 Q.limit = prog.has_clamp ? (mode == MODE_FWD ? d_limitF : d_limitB) + t * B : nullptr;
                 Q.psum_prev = ps_prev; Q.prev_slot = prev_slot; Q.psum_out = ps_out;
                 Q.rec = d_rec + t * rec_len; Q.lik = d_lik ? d_lik + (size_t)t * G : nullptr;
+                // composed transitions: the stages in front of the last one, each reading the one before (the first: the step's source), then
+                // the fused kernel reads the last stage's output and partials the way it reads a state's (DESIGN.md "Composed transitions")
+                const bool bws = mode != MODE_FWD;
+                const int nst = prog.multi ? (bws ? prog.nstB : prog.nstF)[t] : 0;
+                for (int s2 = 0; s2 < nst; ++s2) {
+                    StepParams S = Q;
+                    const size_t e = (bws ? prog.offB : prog.offF)[t] + (size_t)s2 * B;
+                    S.src = s2 == 0 ? srcp : SM.out[(s2 - 1) & 1]; S.src_stride = s2 == 0 ? src_stride : G;
+                    S.dst = SM.out[s2 & 1]; S.dst_stride = G; S.post = nullptr; S.post_stride = 0;
+                    S.srckind = (bws ? SM.kindB : SM.kindF) + e;
+                    S.tap0 = (bws ? SM.tapB0 : SM.tapF0) + e; S.tap1 = (bws ? SM.tapB1 : SM.tapF1) + e;
+                    S.cmode = (bws ? SM.cmodeB : SM.cmodeF) + e; S.limit = (bws ? SM.limitB : SM.limitF) + e;
+                    S.psum_prev = s2 == 0 ? ps_prev : SM.ps[(s2 - 1) & 1]; S.psum_out = SM.ps[s2 & 1];
+                    S.rec = nullptr; S.lik = nullptr;
+                    launch_stage(st, S, tile, (int)B, bws);
+                    account(ctx, bws, (double)B * G * 16.0, (double)B * G * (valu_stencil_flop(prog.LW0) + valu_stencil_flop(prog.LW1)));
+                }
+                if (nst > 0) { Q.src = SM.out[(nst - 1) & 1]; Q.src_stride = G; Q.psum_prev = SM.ps[(nst - 1) & 1]; }
                 launch_step(st, p->obs_model, Q, tile, (int)B, mode, means);
                 const bool bw = mode != MODE_FWD;
                 account(ctx, bw, (double)B * G * ((bw ? 32.0 : 16.0) + (d_lik ? 8.0 : 0.0)),

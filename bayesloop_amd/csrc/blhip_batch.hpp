@@ -304,9 +304,11 @@ GeometryPlan plan_geometry(blhip_ctx *ctx, const blhip_problem *p, const Geometr
     //  -- bl1c::chain1d_kernel SHIFT --, the K-steps-per-launch and persistent kernels have not: chain1d or the generic kernel)
     // (round 6: ... and the one with the clamps of RegimeSwitch / NotEqual -- bl1c::chain1d_kernel CL = 2; the dense zero-boundary kernels of
     //  the AlphaStable walk keep the generic kernel)
+    // (composed transitions -- ChainProgram::multi -- run on the launch-per-step generic kernel only: has_clamp keeps them off the fast paths,
+    //  the condition below off the 1-D ones)
     const bool shift1d = p->ndim == 1 && prog.has_clamp && !prog.dense_clamp && ctx->option("chain1d_shift", 1.0) != 0.0 &&
                          (!prog.other_clamp || ctx->option("chain1d_clamp", 1.0) != 0.0);
-    if (p->ndim == 1 && !gp.fast && (!prog.has_clamp || shift1d) && ctx->option("fuse1d", 8.0) >= 1.0 &&
+    if (p->ndim == 1 && !gp.fast && !prog.multi && (!prog.has_clamp || shift1d) && ctx->option("fuse1d", 8.0) >= 1.0 &&
         (p->obs_model == BLHIP_OM_POISSON || p->obs_model == BLHIP_OM_GAUSSIAN_MEAN || p->obs_model == BLHIP_OM_TABLE)) {
         gp.f1_TJ = 128;
         gp.fusedK = std::max<int64_t>(1, std::min<int64_t>((int64_t)ctx->option("fuse1d", 8.0), T));
@@ -499,6 +501,45 @@ void upload_metadata(blhip_ctx *ctx, const blhip_problem *p, const ChainProgram 
         HIPCHECK(hipMemcpyAsync(M.lw, taps.lw.data(), taps.lw.size() * 4, hipMemcpyHostToDevice, st));
         HIPCHECK(hipMemcpyAsync(M.lw2, taps.lw2.data(), taps.lw2.size() * 4, hipMemcpyHostToDevice, st));
     }
+}
+
+// the stages of composed transitions (ChainProgram::multi) in HBM: per direction, per (step, stage, chain) source kind, tap ids, clamp mode
+// and level (pre[off[t] + s B + b]); plus the two ping-pong stage outputs of a step (B x G each) and their partials (B x NRED x nblk each)
+struct StageMeta {
+    unsigned char *kindF = nullptr, *kindB = nullptr, *cmodeF = nullptr, *cmodeB = nullptr;
+    int *tapF0 = nullptr, *tapF1 = nullptr, *tapB0 = nullptr, *tapB1 = nullptr;
+    double *limitF = nullptr, *limitB = nullptr;
+    double *out[2] = {nullptr, nullptr}, *ps[2] = {nullptr, nullptr};
+};
+
+void upload_stages(blhip_ctx *ctx, const ChainProgram &prog, int64_t B, long long G, int nblk, bool full, StageMeta &S) {
+    hipStream_t st = ctx->stream;
+    const size_t nF = prog.preF.size(), nB = full ? prog.preB.size() : 0;
+    const size_t n1 = std::max<size_t>(std::max(nF, nB), 1);
+    const size_t mb = 2 * (2 * carve_size(n1) + 2 * carve_size(n1 * 4) + carve_size(n1 * 8));
+    ctx->stagemeta.ensure(mb);
+    char *cur = ctx->stagemeta.as<char>();
+    auto put = [&](const std::vector<StepProg> &v, size_t n, unsigned char *&kind, unsigned char *&cmode, int *&t0, int *&t1, double *&lim) {
+        kind = carve<unsigned char>(cur, std::max<size_t>(n, 1)); cmode = carve<unsigned char>(cur, std::max<size_t>(n, 1));
+        t0 = carve<int>(cur, std::max<size_t>(n, 1)); t1 = carve<int>(cur, std::max<size_t>(n, 1)); lim = carve<double>(cur, std::max<size_t>(n, 1));
+        if (n == 0) return;
+        std::vector<unsigned char> hk(n), hc(n);
+        std::vector<int> h0(n), h1(n);
+        std::vector<double> hl(n);
+        for (size_t e = 0; e < n; ++e) { hk[e] = v[e].kind; hc[e] = v[e].cmode; h0[e] = v[e].t0; h1[e] = v[e].t1; hl[e] = v[e].limit; }
+        HIPCHECK(hipMemcpyAsync(kind, hk.data(), n, hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(cmode, hc.data(), n, hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(t0, h0.data(), n * 4, hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(t1, h1.data(), n * 4, hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(lim, hl.data(), n * 8, hipMemcpyHostToDevice, st));
+        sync_stream(ctx, st);                     // (the host vectors go out of scope)
+    };
+    put(prog.preF, nF, S.kindF, S.cmodeF, S.tapF0, S.tapF1, S.limitF);
+    put(prog.preB, nB, S.kindB, S.cmodeB, S.tapB0, S.tapB1, S.limitB);
+    const size_t outd = (size_t)B * G, psd = (size_t)B * NRED * nblk;
+    ctx->stagebuf.ensure(2 * (outd + psd) * 8);
+    double *base = ctx->stagebuf.as<double>();
+    S.out[0] = base; S.out[1] = base + outd; S.ps[0] = base + 2 * outd; S.ps[1] = base + 2 * outd + psd;
 }
 
 // host-side results of one batch of chains

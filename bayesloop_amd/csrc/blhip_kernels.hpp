@@ -19,7 +19,8 @@ constexpr int NTHREADS = 256;
 constexpr int NRED = 7;          // partial slots per (step, chain): 0 N  1 S(p/L) [fwd: U]  2 C  3 M0  4 M1  5 B (clamp only)
                                  //                                  6 MAX of the new state (clamp batches only: NotEqual)
 
-enum Mode { MODE_FWD = 0, MODE_BWD = 1, MODE_FILTER = 2 };
+// MODE_STAGE_FWD / _BWD: the transition alone, one stage of a composed transition (ChainProgram::multi, blhip_program.hpp) -- the stage kernel
+enum Mode { MODE_FWD = 0, MODE_BWD = 1, MODE_STAGE_FWD = 2, MODE_STAGE_BWD = 3 };
 enum SrcKind { SRC_PREV = 0, SRC_PRIOR = 1, SRC_RESET = 2, SRC_UNIFORM = 3, SRC_INDEP = 4 };
 
 struct StepParams {
@@ -310,8 +311,19 @@ __device__ __forceinline__ double likelihood(const StepParams &P, int i, int j, 
 
 // One fused step for a batch of chains.  grid = (nblk, B), block = 256, dynamic LDS:
 //   in_tile [(TI + 2 LW0)][pitch]  +  v_tile [TI][pitch]  + scratch,  pitch = TJ + 2 LW1
+//
+// MODE_STAGE_*: the stage kernel -- one stage of a composed transition in front of the fused step (DESIGN.md "Composed transitions").  It
+// reads its input (a state, a shared distribution or the previous stage's output) in the scale the fused kernel would (the lazy normaliser
+// of the producer; backward with the clamp bookkeeping's slot 5), applies the stage, and writes u = its output IN THE REFERENCE'S SCALE
+// before the stage's own renormalisation.  Partials [B][NRED][nblk]: slot 0 and 5 = D, the divisor that renormalises u (sum u for
+// RegimeSwitch / NotEqual / Deterministic / AlphaStable / Bivariate stages -- the clamped source's mass for modes 1 and 3 as in the fused
+// kernel --, exactly 1 for walks, which the reference does not renormalise; sum u when a NotEqual stage follows, which inverts around the
+// maximum and the sum of what it reads); slot 2 = sum u; slot 6 = max u.  Its consumer reads slot 0 forward (prev_slot 0), slot 2 and
+// slot 5 backward (prev_slot 2) exactly as it reads a step's partials.
 template <int OM, int MODE, bool MEANS>
 __global__ __launch_bounds__(NTHREADS) void step_kernel(const StepParams P) {
+    constexpr bool STAGE = MODE == MODE_STAGE_FWD || MODE == MODE_STAGE_BWD;
+    constexpr bool BWDLIKE = MODE == MODE_BWD || MODE == MODE_STAGE_BWD;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int b = blockIdx.y;
     const int blk = blockIdx.x;
@@ -324,7 +336,8 @@ __global__ __launch_bounds__(NTHREADS) void step_kernel(const StepParams P) {
     double *red = v_tile + (size_t)P.TI * pitch;
 
     const int kind = P.srckind[b];
-    const int cm = P.cmode ? P.cmode[b] : 0;
+    const int cm_raw = P.cmode ? P.cmode[b] : 0;
+    const int cm = STAGE ? (cm_raw & 15) : cm_raw;        // (a stage's cmode may carry STAGE_NEXT_NE = 16)
     const double lim = P.cmode ? P.limit[b] : 0.0;
     const bool dense = cm == 4;                    // BivariateRandomWalk: tap0 is a dense (2 lw0 + 1) x (2 lw1 + 1) kernel
     // asymmetric tap sets (tap_lw2 == -1: full 2 lw + 1 weights, Deterministic spline shift) and the boundary rule per axis
@@ -349,7 +362,7 @@ __global__ __launch_bounds__(NTHREADS) void step_kernel(const StepParams P) {
     // lazy normaliser of the producing step (every block sums the same partials in the same order)
     double scale = 1.0, kappa = 1.0;
     double ne_max = 0.0, ne_inv = 0.0;             // NotEqual: (max - x) / (G max - sum x) of the producing step's state
-    if (MODE != MODE_FILTER && kind == SRC_PREV) {
+    if (kind == SRC_PREV) {
         const double s = sum_partials(P.psum_prev + ((long long)b * NRED + P.prev_slot) * P.prev_nblk, P.prev_nblk, red);
         scale = 1.0 / s;
         if (cm == 3) {
@@ -359,7 +372,7 @@ __global__ __launch_bounds__(NTHREADS) void step_kernel(const StepParams P) {
             ne_max = block_max(m, red);
             ne_inv = 1.0 / ((double)P.n0 * (double)P.n1 * ne_max - s);     // transitionModels.py:465-466 (0/0 -> NaN as numpy)
         }
-        if (MODE == MODE_BWD && P.cmode) {
+        if (BWDLIKE && P.cmode) {
             // RegimeSwitch clamps F(beta_norm * L) (transitionModels.py:405-407): that needs 1 / sum(beta) of the producing
             // step (slot 5); products keep the well-scaled normaliser 1 / sum(c) (slot 2):  beta_used = u * kappa
             const double sb = sum_partials(P.psum_prev + ((long long)b * NRED + 5) * P.prev_nblk, P.prev_nblk, red);
@@ -423,7 +436,7 @@ __global__ __launch_bounds__(NTHREADS) void step_kernel(const StepParams P) {
     for (int c = x; c < tw; c += XW) {
         const int gj = j0 + c;
         double cA = 0.0, cB = 0.0, g1 = 0.0;
-        if (MODE != MODE_FILTER) {
+        if (!STAGE) {
             if (OM == OM_GAUSSIAN) { cA = P.colA[gj]; cB = P.colB[gj]; }
             if (OM == OM_POISSON) cA = P.colA[gj];
             g1 = P.m1[gj];
@@ -462,8 +475,13 @@ __global__ __launch_bounds__(NTHREADS) void step_kernel(const StepParams P) {
             }
             const int gi = i0 + r;
             const long long cell = (long long)gi * P.n1 + gj;
-            if (MODE == MODE_FILTER) {
-                P.dst[(long long)b * P.dst_stride + cell] = o;
+            if (STAGE) {
+                double u = o * scale;                                    // the stage's output in the reference's scale
+                if (cm == 2) u = u < lim ? lim : u;
+                P.dst[(long long)b * P.dst_stride + cell] = u;
+                sU += (cm == 1 || cm == 3) ? in_tile[(size_t)(r + P.LW0) * pitch + P.LW1 + c] : u;
+                sN += u;
+                sMax = fmax(sMax, u);
             } else {
                 const double L = likelihood<OM>(P, gi, gj, cA, cB, g1);
                 double u = o * scale;                                    // the (normalised) prior of this step
@@ -494,9 +512,19 @@ __global__ __launch_bounds__(NTHREADS) void step_kernel(const StepParams P) {
             }
         }
     }
-    if (MODE == MODE_FILTER) return;
-
     double *out = P.psum_out + (long long)b * NRED * P.nblk + blk;
+    if constexpr (STAGE) {
+        const bool renorm = cm != 0 || (cm_raw & 16);
+        double v[2] = {sN, (cm_raw & 16) ? sN : sU};
+        block_sums<2, NTHREADS / 64>(v, red);
+        if (threadIdx.x == 0) {
+            const double D = renorm ? v[1] : (blk == 0 ? 1.0 : 0.0);
+            out[0] = D; out[2 * P.nblk] = v[0]; out[5 * P.nblk] = D;
+        }
+        const double mx = block_max(sMax, red);
+        if (threadIdx.x == 0) out[6 * P.nblk] = mx;
+        return;
+    }
     // all sums of the block with two barriers (red holds 6 * NTHREADS/64 doubles)
     double v[6] = {sN, sS, sC, sM0, sM1, MODE == MODE_BWD ? sU * kappa : sU};
     block_sums<6, NTHREADS / 64>(v, red);

@@ -61,10 +61,15 @@ void launch_step_om(hipStream_t s, const StepParams &P, const Tile &t, int B, in
     } else if (mode == MODE_BWD) {
         launch_step_t<OM, MODE_BWD, true>(s, P, t, B);
     } else {
-        // (blk::MODE_FILTER -- the transition alone -- has no caller: the models' plug-in calls run a resumed forward step with a flat
-        //  likelihood; its four instantiations were pruned in round 6)
-        fail("internal: generic step kernel launched in mode %d", mode);
+        fail("internal: generic step kernel launched in mode %d", mode);      // (the stage modes: launch_stage)
     }
+}
+
+// one stage of composed transitions (ChainProgram::multi): the transition alone, no likelihood -- one instantiation per direction
+void launch_stage(hipStream_t s, const StepParams &P, const Tile &t, int B, bool bwd) {
+    if (bwd) launch_step_t<OM_TABLE, MODE_STAGE_BWD, false>(s, P, t, B);
+    else launch_step_t<OM_TABLE, MODE_STAGE_FWD, false>(s, P, t, B);
+    HIPCHECK(hipGetLastError());
 }
 
 void launch_step(hipStream_t s, int om, const StepParams &P, const Tile &t, int B, int mode, bool means) {

@@ -264,6 +264,13 @@ void build_records(const blhip_problem *p, std::vector<double> &rec, int &rec_le
     }
 }
 
+struct StepProg {
+    unsigned char kind = SRC_PREV, cmode = 0;   // cmode: 0 none, 1 clamp the source (before the stencil), 2 clamp after it
+    int t0 = -1, t1 = -1;
+    double limit = 0.0;
+};
+constexpr unsigned char STAGE_NEXT_NE = 16;     // (a pre-stage's cmode bit: the stage after it is a NotEqual model)
+
 struct ChainProgram {
     // per (step, chain): source kind, tap ids per internal axis, clamp mode/limit (RegimeSwitch); forward and backward
     std::vector<unsigned char> kindF, kindB, cmodeF, cmodeB;
@@ -275,12 +282,16 @@ struct ChainProgram {
     bool other_clamp = false;    // has_clamp for another reason than a Deterministic model's shift (mode 6)
     bool dense_clamp = false;    // ... than a shift or the clamps of RegimeSwitch / NotEqual: AlphaStable- / BivariateRandomWalk (modes 5 / 4: zero boundary, dense kernels)
     bool has_shift = false;      // a Deterministic model
-};
-
-struct StepProg {
-    unsigned char kind = SRC_PREV, cmode = 0;   // cmode: 0 none, 1 clamp the source (before the stencil), 2 clamp after it
-    int t0 = -1, t1 = -1;
-    double limit = 0.0;
+    // Composed transitions (a CombinedTransitionModel whose sub-models do not fit into ONE step of the generic kernel, transitionModels.py:
+    // 632-662): the transition of a (step, chain) is a list of stages applied in list order.  The fused step kernel applies the LAST one,
+    // blk::step_kernel<.., MODE_STAGE_*> (the stage kernel) the ones in front of it.  Step t (per direction) runs nst[t] stages in front of
+    // the fused kernel for EVERY chain of the batch -- a chain with fewer gets identity stages (copies) at the front -- and the fused kernel
+    // then reads the last stage's output (kind SRC_PREV).  Stage s of step t, chain b: pre[off[t] + s B + b]; its cmode may carry
+    // STAGE_NEXT_NE.  Empty unless `multi`, which sets has_clamp too (the kernels' clamp bookkeeping carries the stages' scales).
+    bool multi = false;
+    std::vector<int> nstF, nstB;
+    std::vector<size_t> offF, offB;
+    std::vector<StepProg> preF, preB;
 };
 
 void build_program(const blhip_problem *p, const Geometry &g, int64_t c0, int64_t B, const double *op_values,
@@ -299,6 +310,8 @@ void build_program(const blhip_problem *p, const Geometry &g, int64_t c0, int64_
     prog.other_clamp = false;
     prog.dense_clamp = false;
     prog.has_shift = false;
+    prog.multi = false;
+    prog.nstF.clear(); prog.nstB.clear(); prog.offF.clear(); prog.offB.clear(); prog.preF.clear(); prog.preB.clear();
     double dV = 1.0;
     for (int k = 0; k < p->ndim; ++k) dV *= p->lattice[k];
     // the ops a step's program is made of (the *_ARG ops only carry values of the op in front of them: a Deterministic model has 2 T of
@@ -332,7 +345,13 @@ void build_program(const blhip_problem *p, const Geometry &g, int64_t c0, int64_
     for (int k : real_ops)
         if (p->ops[k].kind == BLHIP_OP_BREAKPOINT || p->ops[k].kind == BLHIP_OP_CHANGEPOINT) bound_ops.push_back(k);
     std::vector<StepProg> seg_prog(bound_ops.size() + 1);
+    std::vector<std::vector<StepProg>> seg_pre(bound_ops.size() + 1);       // (the stages in front of seg_prog's: see ChainProgram::multi)
     std::vector<char> seg_cached(bound_ops.size() + 1, 0), det_in_seg(bound_ops.size() + 1, 0);
+    // (step, chain) transitions with stages in front of the last one, collected here (composed batches only) and laid out after the walk
+    struct PreRec { int64_t t, b; std::vector<StepProg> st; };
+    std::vector<PreRec> recF, recB;
+    std::vector<StepProg> stat_pre, scratch_pre, resume_pre;
+    const std::vector<StepProg> no_pre;
     for (int64_t b = 0; b < B; ++b) {
         const double *val = op_values ? op_values + (c0 + b) * nops : nullptr;
         // tap ids of this chain's GRW ops
@@ -371,8 +390,10 @@ void build_program(const blhip_problem *p, const Geometry &g, int64_t c0, int64_
             }
         }
         // the transition from one step to the next, evaluated at time stamp tau (list order, transitionModels.py:645-649)
-        auto run = [&](double tau, bool have_tau, int64_t step = -1, bool fwd = true) {
+        // -> the last stage; `pre` receives the stages in front of it (a composition the current stage cannot absorb closes it: `close`)
+        auto run = [&](std::vector<StepProg> &pre, double tau, bool have_tau, int64_t step = -1, bool fwd = true) {
             StepProg sp;
+            pre.clear();
             int seg = 0;                                                   // active sub-model of a serial model (:768)
             if (have_tau)
                 for (int k : real_ops) {
@@ -380,31 +401,27 @@ void build_program(const blhip_problem *p, const Geometry &g, int64_t c0, int64_
                     if ((op.kind == BLHIP_OP_BREAKPOINT || (op.kind == BLHIP_OP_CHANGEPOINT && (op.flags & 1))) && val[k] <= tau) seg++;
                 }
             bool filtered = false;
+            auto close = [&]() { pre.push_back(sp); sp = StepProg(); filtered = false; };      // the next stage reads this one's output
             for (int k : real_ops) {
                 const blhip_op &op = p->ops[k];
                 if (op.segment >= 0 && op.segment != seg) continue;
                 switch (op.kind) {
                     case BLHIP_OP_GRW: {
                         if (op_tap[k] < 0) break;
-                        if (sp.cmode == 2) fail("a GaussianRandomWalk after a RegimeSwitch in one combined model is not supported");
-                        if (sp.cmode == 4 || sp.cmode == 5)
-                            fail("a GaussianRandomWalk combined with a Bivariate- / AlphaStableRandomWalk is not supported");
-                        if (sp.cmode == 6 && (op_axis[k] == 0 ? sp.t0 : sp.t1) >= 0)
-                            fail("a GaussianRandomWalk and a Deterministic model on the same parameter are not supported");
-                        int &slot = op_axis[k] == 0 ? sp.t0 : sp.t1;
-                        if (slot >= 0)
-                            fail("two GaussianRandomWalk ops on the same parameter in one combined model are not supported");
-                        slot = op_tap[k];
+                        // (after a RegimeSwitch that clamps a filtered distribution, a Bivariate- / AlphaStableRandomWalk, a Deterministic
+                        //  model or another walk on the same parameter: a new stage)
+                        if (sp.cmode == 2 || sp.cmode == 4 || sp.cmode == 5 || (op_axis[k] == 0 ? sp.t0 : sp.t1) >= 0) close();
+                        (op_axis[k] == 0 ? sp.t0 : sp.t1) = op_tap[k];
                         filtered = true;
                         break;
                     }
                     case BLHIP_OP_CHANGEPOINT:
-                        if (!(op.flags & 1) && have_tau && tau == val[k]) {      // transitionModels.py:300-312
-                            sp = StepProg(); sp.kind = SRC_RESET; filtered = false;
+                        if (!(op.flags & 1) && have_tau && tau == val[k]) {      // transitionModels.py:300-312 (drops the stages before it)
+                            sp = StepProg(); sp.kind = SRC_RESET; filtered = false; pre.clear();
                         }
                         break;
                     case BLHIP_OP_INDEPENDENT:                                    // transitionModels.py:351-360
-                        sp = StepProg(); sp.kind = SRC_INDEP; filtered = false;
+                        sp = StepProg(); sp.kind = SRC_INDEP; filtered = false; pre.clear();
                         break;
                     case BLHIP_OP_DETERMINISTIC: {                                // transitionModels.py:571-583, :585-602
                         if (step < 0) break;                                      // (the time-independent template program)
@@ -412,12 +429,11 @@ void build_program(const blhip_problem *p, const Geometry &g, int64_t c0, int64_
                         if (std::isnan(dd)) fail("chain %lld: Deterministic shift of step %lld is NaN", (long long)(c0 + b), (long long)step);
                         if (std::fabs(dd) > 12.0 && (g.n0 != 1 || (double)g.n1 > 16000.0))
                             fail("chain %lld, step %lld: Deterministic model shifts by %.3g grid cells in one time step; on grids with two "
-                                 "parameters (and 1-D grids beyond 16000 points) the fused kernel supports up to 12 (SciPy's pre-padding)",
+                                 "parameters (and 1-D grids beyond 16000 points) the step and stage kernels support up to 12 (SciPy's pre-padding)",
                                  (long long)(c0 + b), (long long)step, dd);
-                        int &slot = op_axis[k] == 0 ? sp.t0 : sp.t1;
-                        if (slot >= 0 || (sp.cmode != 0 && sp.cmode != 6))
-                            fail("a Deterministic model combined with another model acting on the same parameter / a clamp is not supported");
                         if (dd != 0.0) {                                          // zero shift: identity (its renormalisation is a no-op)
+                            if ((op_axis[k] == 0 ? sp.t0 : sp.t1) >= 0 || (sp.cmode != 0 && sp.cmode != 6)) close();
+                            int &slot = op_axis[k] == 0 ? sp.t0 : sp.t1;
                             if (std::fabs(dd) > 12.0) { slot = taps.get_bigshift(dd); prog.whole_row = true; }
                             else slot = taps.get_shift(op_axis[k], dd);
                             sp.cmode = 6;
@@ -426,29 +442,27 @@ void build_program(const blhip_problem *p, const Geometry &g, int64_t c0, int64_
                         break;
                     }
                     case BLHIP_OP_ALPHASTABLE: {                                  // transitionModels.py:167-187
-                        if (sp.cmode != 0 || filtered)
-                            fail("an AlphaStableRandomWalk combined with another model acting on the same step is not supported");
+                        if (sp.cmode != 0 || filtered) close();
                         sp.cmode = 5;
                         (op_axis[k] == 0 ? sp.t0 : sp.t1) = op_tap[k];
                         filtered = true;
                         break;
                     }
                     case BLHIP_OP_BIVARIATE:                                      // transitionModels.py:880-891
-                        if (sp.cmode != 0 || filtered)
-                            fail("a BivariateRandomWalk combined with another model acting on the same step is not supported");
+                        if (sp.cmode != 0 || filtered) close();
                         sp.cmode = 4;
                         sp.t0 = op_tap[k];
                         filtered = true;
                         break;
                     case BLHIP_OP_NOTEQUAL:                                       // transitionModels.py:462-471
-                        if (sp.cmode != 0 || filtered)
-                            fail("a NotEqual model after another model acting on the same step is not supported");
-                        if (sp.kind != SRC_PREV) fail("a NotEqual model right after a change-point / independent restart is not supported");
+                        // (it inverts around the maximum and the sum of its input, which the kernels know of a state or a stage's
+                        //  output: after a restart the shared distribution is copied by an identity stage first)
+                        if (sp.cmode != 0 || filtered || sp.kind != SRC_PREV) close();
                         sp.cmode = 3;
                         sp.limit = std::pow(10.0, val[k]) * dV;
                         break;
                     case BLHIP_OP_REGIMESWITCH:                                   // transitionModels.py:405-410
-                        if (sp.cmode != 0) fail("two RegimeSwitch models acting at the same time are not supported");
+                        if (sp.cmode != 0) close();
                         sp.cmode = filtered ? 2 : 1;
                         sp.limit = std::pow(10.0, val[k]) * dV;
                         break;
@@ -458,18 +472,23 @@ void build_program(const blhip_problem *p, const Geometry &g, int64_t c0, int64_
             if (have_tau)
                 for (int k : real_ops) {                                          // serial change-points, :801-813
                     const blhip_op &op = p->ops[k];
-                    if (op.kind == BLHIP_OP_CHANGEPOINT && (op.flags & 1) && tau == val[k]) { sp = StepProg(); sp.kind = SRC_RESET; }
+                    if (op.kind == BLHIP_OP_CHANGEPOINT && (op.flags & 1) && tau == val[k]) { sp = StepProg(); sp.kind = SRC_RESET; pre.clear(); }
                 }
-            if (sp.t0 >= 0) prog.LW0 = std::max(prog.LW0, taps.lw[sp.t0]);
-            if (sp.cmode == 4) prog.LW1 = std::max(prog.LW1, taps.lw2[sp.t0]);
-            if (sp.t1 >= 0) prog.LW1 = std::max(prog.LW1, taps.lw[sp.t1]);
+            auto radii = [&](const StepProg &q) {
+                if (q.t0 >= 0) prog.LW0 = std::max(prog.LW0, taps.lw[q.t0]);
+                if (q.cmode == 4) prog.LW1 = std::max(prog.LW1, taps.lw2[q.t0]);
+                if (q.t1 >= 0) prog.LW1 = std::max(prog.LW1, taps.lw[q.t1]);
+            };
+            radii(sp);
+            for (const StepProg &q : pre) radii(q);
             return sp;
         };
-        const StepProg stat = run(0.0, false);       // the program when nothing depends on the time stamp
+        const StepProg stat = run(stat_pre, 0.0, false);       // the program when nothing depends on the time stamp
         // A step's program depends on its time stamp through (1) the active sub-model of a serial model = how many break- / serial
         // change-points lie at or before it, (2) a change-point AT it, (3) the step index of a Deterministic model in the active part.
         // Steps that share (1), have no (2) and no (3) share their program: it is walked once per chain and segment -- two thirds of the
         // (chain, step) pairs of the published break-point study sit in Static segments (build_program 28 -> 15 ms of a 92-ms fit).
+        const std::vector<StepProg> *pre_of = &no_pre;       // (set by `at`: the stages in front of the program it returns)
         auto at = [&](double tau, int64_t step, bool fwd) -> StepProg {
             int seg = 0;
             bool event = false;
@@ -479,8 +498,9 @@ void build_program(const blhip_problem *p, const Geometry &g, int64_t c0, int64_
                 if (serial && val[k] <= tau) seg++;
                 if (op.kind == BLHIP_OP_CHANGEPOINT && tau == val[k]) event = true;
             }
-            if (event || det_in_seg[seg]) return run(tau, true, step, fwd);
-            if (!seg_cached[seg]) { seg_prog[seg] = run(tau, true, step, fwd); seg_cached[seg] = 1; }
+            if (event || det_in_seg[seg]) { pre_of = &scratch_pre; return run(scratch_pre, tau, true, step, fwd); }
+            if (!seg_cached[seg]) { seg_prog[seg] = run(seg_pre[seg], tau, true, step, fwd); seg_cached[seg] = 1; }
+            pre_of = &seg_pre[seg];
             return seg_prog[seg];
         };
         if (time_dependent) {
@@ -494,13 +514,56 @@ void build_program(const blhip_problem *p, const Geometry &g, int64_t c0, int64_
         for (int64_t t = 0; t < T; ++t) {
             // forward step t consumes T_fwd(post_{t-1}, ts[t-1])   core.py:411
             StepProg f; f.kind = SRC_PRIOR;
-            if (t > 0) f = time_dependent ? at(p->timestamps[t - 1], t, true) : stat;
-            else if (resume) f = run(p->resume_time, true, 0, true);   // continues a carried state (OnlineStudy.step, core.py:2164-2165)
+            const std::vector<StepProg> *fpre = &no_pre, *rpre = &no_pre;
+            if (t > 0) { pre_of = &stat_pre; f = time_dependent ? at(p->timestamps[t - 1], t, true) : stat; fpre = pre_of; }
+            else if (resume) { f = run(resume_pre, p->resume_time, true, 0, true); fpre = &resume_pre; }   // continues a carried state (OnlineStudy.step, core.py:2164-2165)
+            if (!fpre->empty()) recF.push_back(PreRec{t, b, *fpre});
             // backward step t consumes T_bwd(beta_{t+1} L_{t+1}, ts[t+1]) = T_fwd(., ts[t+1] - 1)   core.py:467, transitionModels.py:316-317
             StepProg r; r.kind = SRC_UNIFORM;
-            if (t < T - 1) r = time_dependent ? at(p->timestamps[t + 1] - 1.0, t, false) : stat;
+            if (t < T - 1) { pre_of = &stat_pre; r = time_dependent ? at(p->timestamps[t + 1] - 1.0, t, false) : stat; rpre = pre_of; }
+            if (!rpre->empty()) recB.push_back(PreRec{t, b, *rpre});
             gF[(size_t)(b % GROUP) * T + t] = f; gB[(size_t)(b % GROUP) * T + t] = r;
         }
         if (b % GROUP == GROUP - 1 || b == B - 1) flush_group(b - b % GROUP, b % GROUP + 1);
     }
+    if (recF.empty() && recB.empty()) return;
+    // ---- composed transitions: the per-step stage tables (ChainProgram::multi) ----
+    prog.multi = true;
+    prog.has_clamp = true;
+    auto lay_out = [&](std::vector<PreRec> &recs, std::vector<int> &nst, std::vector<size_t> &off, std::vector<StepProg> &pre,
+                       std::vector<unsigned char> &kind, std::vector<int> &tap0, std::vector<int> &tap1, std::vector<unsigned char> &cmode,
+                       std::vector<double> &limit) {
+        nst.assign(T, 0);
+        off.assign(T + 1, 0);
+        for (const PreRec &r : recs) nst[r.t] = std::max(nst[r.t], (int)r.st.size());
+        for (int64_t t = 0; t < T; ++t) off[t + 1] = off[t] + (size_t)nst[t] * B;
+        pre.assign(off[T], StepProg());
+        std::vector<int> which(recs.empty() ? 0 : nT, -1);
+        for (size_t q = 0; q < recs.size(); ++q) which[(size_t)recs[q].t * B + recs[q].b] = (int)q;
+        std::vector<StepProg> list;
+        for (int64_t t = 0; t < T; ++t) {
+            const int n = nst[t];
+            if (n == 0) continue;
+            for (int64_t b = 0; b < B; ++b) {
+                const size_t e = (size_t)t * B + b;
+                StepProg last; last.kind = kind[e]; last.t0 = tap0[e]; last.t1 = tap1[e]; last.cmode = cmode[e]; last.limit = limit[e];
+                const int q = which[e];
+                const int np = q >= 0 ? (int)recs[q].st.size() : 0;
+                // identity stages in front (copies of the source), then the chain's own stages, then the last one (the fused kernel's)
+                list.assign((size_t)(n - np), StepProg());
+                if (q >= 0) list.insert(list.end(), recs[q].st.begin(), recs[q].st.end());
+                list.push_back(last);
+                list[0].kind = (n - np > 0) ? (np > 0 ? recs[q].st[0].kind : last.kind) : list[0].kind;
+                for (size_t k = 1; k < list.size(); ++k) list[k].kind = SRC_PREV;
+                for (int s2 = 0; s2 < n; ++s2) {
+                    StepProg st = list[s2];
+                    if ((list[s2 + 1].cmode & 15) == 3) st.cmode |= STAGE_NEXT_NE;
+                    pre[off[t] + (size_t)s2 * B + b] = st;
+                }
+                kind[e] = SRC_PREV;
+            }
+        }
+    };
+    lay_out(recF, prog.nstF, prog.offF, prog.preF, prog.kindF, prog.tapF0, prog.tapF1, prog.cmodeF, prog.limitF);
+    lay_out(recB, prog.nstB, prog.offB, prog.preB, prog.kindB, prog.tapB0, prog.tapB1, prog.cmodeB, prog.limitB);
 }
