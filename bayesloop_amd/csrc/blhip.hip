@@ -30,6 +30,7 @@
 
 #include "../../include/blhip.h"
 #include "blhip_kernels.hpp"
+#include "blhip_bigshift.hpp"
 #include "blhip_fast.hpp"
 #include "blhip_mfma.hpp"
 #include "blhip_hwide.hpp"
@@ -211,6 +212,21 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
         upload_metadata(ctx, p, prog, taps, B, full, fast, tile.nblk, M, gp.wideH, gp.wideV, gp.hSplit, gp.hFusedMax);
         StageMeta SM;                            // (composed transitions only: the stages in front of the fused step kernel)
         if (prog.multi) upload_stages(ctx, prog, B, G, tile.nblk, full, SM);
+        // per (step, stage): how many chains' stage is a large shift of a 2-D grid along axis 0 / axis 1 (blk::bigshift_kernel's chains)
+        std::vector<int> big_stageF, big_stageB;
+        if (prog.multi) {
+            auto count_big = [&](const std::vector<StepProg> &pre, std::vector<int> &cnt) {
+                cnt.assign(2 * (pre.size() / (size_t)B), 0);
+                for (size_t e = 0; e < pre.size(); ++e) {
+                    const StepProg &q = pre[e];
+                    if ((q.cmode & 15) != 6) continue;
+                    if (q.t0 >= 0 && taps.lw2[q.t0] == BIGSHIFT_LW2) ++cnt[2 * (e / (size_t)B)];
+                    else if (q.t1 >= 0 && taps.lw2[q.t1] == BIGSHIFT_LW2) ++cnt[2 * (e / (size_t)B) + 1];
+                }
+            };
+            count_big(prog.preF, big_stageF);
+            if (full) count_big(prog.preB, big_stageB);
+        }
         unsigned char *const d_kindF = M.kindF, *const d_kindB = M.kindB, *const d_cmodeF = M.cmodeF, *const d_cmodeB = M.cmodeB;
         double *const d_limitF = M.limitF, *const d_limitB = M.limitB;
         int *const d_tapF0 = M.tapF0, *const d_tapF1 = M.tapF1, *const d_tapB0 = M.tapB0, *const d_tapB1 = M.tapB1;
@@ -448,8 +464,19 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
                     S.cmode = (bws ? SM.cmodeB : SM.cmodeF) + e; S.limit = (bws ? SM.limitB : SM.limitF) + e;
                     S.psum_prev = s2 == 0 ? ps_prev : SM.ps[(s2 - 1) & 1]; S.psum_out = SM.ps[s2 & 1];
                     S.rec = nullptr; S.lik = nullptr;
-                    launch_stage(st, S, tile, (int)B, bws);
-                    account(ctx, bws, (double)B * G * 16.0, (double)B * G * (valu_stencil_flop(prog.LW0) + valu_stencil_flop(prog.LW1)));
+                    // (chains whose stage is a large shift of a 2-D grid are blk::bigshift_kernel's, one launch per shifted axis; every
+                    //  kernel skips the chains that are not its own, and a launch is issued only if some chain needs it)
+                    const int *big = &(bws ? big_stageB : big_stageF)[2 * (e / (size_t)B)];
+                    const int64_t n_other = B - big[0] - big[1];
+                    if (n_other > 0) {
+                        launch_stage(st, S, tile, (int)B, bws);
+                        account(ctx, bws, (double)n_other * G * 16.0, (double)n_other * G * (valu_stencil_flop(prog.LW0) + valu_stencil_flop(prog.LW1)));
+                    }
+                    for (int ax = 0; ax < 2; ++ax)
+                        if (big[ax] > 0) {
+                            launch_bigshift(st, S, ax, (int)B, bws);
+                            account(ctx, bws, (double)big[ax] * G * 16.0, (double)big[ax] * G * BIGSHIFT_FLOP);
+                        }
                 }
                 if (nst > 0) { Q.src = SM.out[(nst - 1) & 1]; Q.src_stride = G; Q.psum_prev = SM.ps[(nst - 1) & 1]; }
                 launch_step(st, p->obs_model, Q, tile, (int)B, mode, means);

@@ -173,6 +173,9 @@ constexpr double EPI_FWD_FLOP = 10.0, EPI_BWD_FLOP = 26.0;
 // matrix pipe (16 output rows per tile) 16 + 2 r products, zeros of the band included
 inline double valu_stencil_flop(int r) { return r > 0 ? 3.0 * r + 1.0 : 0.0; }
 inline double band_stencil_flop(int r) { return 2.0 * (16.0 + 2.0 * r); }
+// the large-shift stage per cell (blhip_bigshift.hpp): gain (1), the prefilter's initialisation sum (4), two zero-carry and two true-carry
+// sweeps of one multiply-add each (8), four B-spline weights of ~8 flop and their FMAs (40), scale, sum, max (3)
+constexpr double BIGSHIFT_FLOP = 56.0;
 inline void account(blhip_ctx *ctx, bool bwd, double bytes, double flops) {
     (bwd ? ctx->timing.bwd_hbm_bytes : ctx->timing.fwd_hbm_bytes) += bytes;
     (bwd ? ctx->timing.bwd_flops : ctx->timing.fwd_flops) += flops;

@@ -129,6 +129,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 // is exact to rounding.  Four sweeps of C dependent multiply-adds + two scans.  Call with ALL lanes of ONE wave; v holds gain x row.
 constexpr double SPLINE_POLE = -0.2679491924311227;            // SciPy's literal (sqrt(3.) - 2. in double arithmetic is two ulp away)
 constexpr double SPLINE_GAIN = (1.0 - SPLINE_POLE) * (1.0 - 1.0 / SPLINE_POLE);
+constexpr int BIGSHIFT_LW2 = -3;            // tap_lw2 of a large (|d| > 12 cells) shift on a 2-D grid: taps[off] = d, no weights -- blk::bigshift_kernel's stage
 __device__ __forceinline__ double pow_pole(int k) {           // z^k, k >= 0
     const double m = pow(-SPLINE_POLE, (double)k);
     return (k & 1) ? -m : m;
@@ -339,6 +340,10 @@ __global__ __launch_bounds__(NTHREADS) void step_kernel(const StepParams P) {
     const int cm_raw = P.cmode ? P.cmode[b] : 0;
     const int cm = STAGE ? (cm_raw & 15) : cm_raw;        // (a stage's cmode may carry STAGE_NEXT_NE = 16)
     const double lim = P.cmode ? P.limit[b] : 0.0;
+    if constexpr (STAGE) {                         // (a large shift of a 2-D grid: blk::bigshift_kernel's chain, blhip_bigshift.hpp)
+        const int tb = P.tap0[b] >= 0 ? P.tap0[b] : P.tap1[b];
+        if (cm == 6 && tb >= 0 && P.tap_lw2[tb] == BIGSHIFT_LW2) return;
+    }
     const bool dense = cm == 4;                    // BivariateRandomWalk: tap0 is a dense (2 lw0 + 1) x (2 lw1 + 1) kernel
     // asymmetric tap sets (tap_lw2 == -1: full 2 lw + 1 weights, Deterministic spline shift) and the boundary rule per axis
     const bool asym0 = cm == 6 && P.tap0[b] >= 0 && P.tap_lw2[P.tap0[b]] < 0;

@@ -72,6 +72,40 @@ void launch_stage(hipStream_t s, const StepParams &P, const Tile &t, int B, bool
     HIPCHECK(hipGetLastError());
 }
 
+// the large-shift stage of a 2-D grid (blhip_bigshift.hpp) for the chains of the launch whose stage is one along `axis`.  A block holds L
+// adjacent lines of n + 24 coefficients in LDS.  L is at least what keeps the block count within the nblk partial slots per chain that the
+// stage's consumer sums, at most what a CU's LDS holds, and otherwise 8 columns (every row access of a block is one 64-byte segment) or 4
+// rows (a line per wave)
+template <int AXIS>
+void launch_bigshift_t(hipStream_t s, const StepParams &P, int B, bool bwd) {
+    const int n = AXIS == 0 ? P.n0 : P.n1, lines = AXIS == 0 ? P.n1 : P.n0;
+    const size_t cap = (size_t)160 * 1024 - 512, scratch = 16;
+    size_t pitch = (size_t)n + 24 + 32;          // (an upper bound of bigshift_pitch, which depends on L)
+    const int Lfit = (int)std::min<size_t>((cap / 8 - scratch) / pitch, (size_t)lines);
+    const int Lmin = (lines + P.nblk - 1) / P.nblk;
+    if (Lfit < Lmin || Lfit < 1)
+        fail("Deterministic model: a shift beyond 12 grid cells along an axis of %d points needs %d lines of it in one block (%zu B of LDS)", n,
+             std::max(Lmin, 1), ((size_t)std::max(Lmin, 1) * pitch + scratch) * 8);
+    int L = std::min(std::max(Lmin, AXIS == 0 ? 8 : 4), Lfit);
+    const int nbb = (lines + L - 1) / L;
+    L = (lines + nbb - 1) / nbb;                 // (what the kernel derives from its block count)
+    pitch = (size_t)bigshift_pitch(n + 24, L, AXIS);
+    const size_t lds = ((size_t)L * pitch + scratch) * 8;
+    if (bwd) {
+        arm_kernel(reinterpret_cast<const void *>(&bigshift_kernel<AXIS, true>));
+        BL_LAUNCH((bigshift_kernel<AXIS, true>), dim3(nbb, B), dim3(NTHREADS), lds, s, P);
+    } else {
+        arm_kernel(reinterpret_cast<const void *>(&bigshift_kernel<AXIS, false>));
+        BL_LAUNCH((bigshift_kernel<AXIS, false>), dim3(nbb, B), dim3(NTHREADS), lds, s, P);
+    }
+    HIPCHECK(hipGetLastError());
+}
+
+void launch_bigshift(hipStream_t s, const StepParams &P, int axis, int B, bool bwd) {
+    if (axis == 0) launch_bigshift_t<0>(s, P, B, bwd);
+    else launch_bigshift_t<1>(s, P, B, bwd);
+}
+
 void launch_step(hipStream_t s, int om, const StepParams &P, const Tile &t, int B, int mode, bool means) {
     switch (om) {
         case BLHIP_OM_POISSON: launch_step_om<OM_POISSON>(s, P, t, B, mode, means); break;

@@ -63,6 +63,22 @@ struct TapTable {
         return id;
     }
 
+    // ... and on grids with two parameters: a stage of its own, run by blk::bigshift_kernel (blhip_bigshift.hpp), which prefilters whole lines
+    // by SciPy's recursion and needs the shift alone.  Stored as [d]; lw = 0 (no halo: the tile geometry of the other kernels does not see
+    // it), lw2 = BIGSHIFT_LW2 marks the layout.
+    std::unordered_map<double, int, DblHash> index_bigshift2;
+    int get_bigshift2(double d) {
+        auto it = index_bigshift2.find(d);
+        if (it != index_bigshift2.end()) return it->second;
+        const int id = (int)off.size();
+        off.push_back((int)w.size());
+        lw.push_back(0);
+        lw2.push_back(BIGSHIFT_LW2);
+        w.push_back(d);
+        index_bigshift2[d] = id;
+        return id;
+    }
+
     // AlphaStableRandomWalk.createKernel (transitionModels.py:196-240) for an axis of n points: k[d], d = 0 .. n-1, of the
     // inverse real DFT (numpy.fft.irfft) of exp(-|c w|^alpha) sampled at m = int(3n/2 + 1) points of [0, pi]; the reference's
     // roll + 3x zero padding + fftconvolve(mode='same') (:233-260) is out[i] = sum_j in[j] k[|i - j|] inside the grid
@@ -427,10 +443,25 @@ void build_program(const blhip_problem *p, const Geometry &g, int64_t c0, int64_
                         if (step < 0) break;                                      // (the time-independent template program)
                         const double dd = val[k + 1 + (fwd ? step : T + step)] / p->lattice[op.axis];
                         if (std::isnan(dd)) fail("chain %lld: Deterministic shift of step %lld is NaN", (long long)(c0 + b), (long long)step);
-                        if (std::fabs(dd) > 12.0 && (g.n0 != 1 || (double)g.n1 > 16000.0))
-                            fail("chain %lld, step %lld: Deterministic model shifts by %.3g grid cells in one time step; on grids with two "
-                                 "parameters (and 1-D grids beyond 16000 points) the step and stage kernels support up to 12 (SciPy's pre-padding)",
+                        if (std::fabs(dd) > 12.0 && g.n0 == 1 && (double)g.n1 > 16000.0)
+                            fail("chain %lld, step %lld: Deterministic model shifts by %.3g grid cells in one time step; on 1-D grids beyond 16000 "
+                                 "points the step and stage kernels support up to 12 (SciPy's pre-padding)",
                                  (long long)(c0 + b), (long long)step, dd);
+                        if (std::fabs(dd) > 12.0 && g.n0 != 1) {
+                            // a large shift on a 2-D grid: a stage of its own (blk::bigshift_kernel), nothing fused into it -- the stage in
+                            // front of it is closed if it holds anything, and what follows (at least the identity the fused step kernel
+                            // applies, reading 1 / D from this stage's partials) starts a new one
+                            const long long nline = op_axis[k] == 0 ? g.n0 : g.n1;
+                            if (nline > BIGSHIFT_MAX_LINE)
+                                fail("chain %lld, step %lld: Deterministic model shifts by %.3g grid cells in one time step along an axis of %lld "
+                                     "points; on grids with two parameters shifts beyond 12 cells (SciPy's pre-padding) are supported on axes of "
+                                     "up to %d points", (long long)(c0 + b), (long long)step, dd, nline, BIGSHIFT_MAX_LINE);
+                            if (sp.t0 >= 0 || sp.t1 >= 0 || sp.cmode != 0) close();
+                            (op_axis[k] == 0 ? sp.t0 : sp.t1) = taps.get_bigshift2(dd);
+                            sp.cmode = 6;
+                            close();
+                            break;
+                        }
                         if (dd != 0.0) {                                          // zero shift: identity (its renormalisation is a no-op)
                             if ((op_axis[k] == 0 ? sp.t0 : sp.t1) >= 0 || (sp.cmode != 0 && sp.cmode != 6)) close();
                             int &slot = op_axis[k] == 0 ? sp.t0 : sp.t1;

@@ -85,7 +85,8 @@ enum {
                                      transition INTO forward step i (t' = time stamp of step i-1; entry 0 is used with
                                      BLHIP_RESUME only), next T: f(t'-1) - f(t') of the backward transition into step i
                                      (t' = time stamp of step i+1; entry T-1 unused).  Cubic-spline shift as
-                                     scipy.ndimage.shift(order=3, mode='nearest'), renormalised; |shift| <= 12 grid cells */
+                                     scipy.ndimage.shift(order=3, mode='nearest'), renormalised.  Shifts beyond 12 grid cells
+                                     per step: 1-D grids of up to 16000 points, 2-D grids along axes of up to 16384 points */
     BLHIP_OP_DETERMINISTIC_ARG = 12
 };
 
