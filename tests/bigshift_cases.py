@@ -6,7 +6,8 @@ Fixtures: tests/golden/gen_bigshift_golden.py; tests: tests/test_bigshift_oracle
 The specs live here, not in cases.CASES: the existing parity tests are parametrised over that dict.  Only the drift functions are added
 to cases.FUNCS (new keys), because cases.make_tm and the oracle adapter look them up there.
 
-Every drift is slope * t, so a step shifts by slope / lattice constant cells.  The likelihood pulls the distribution back at every step:
+Every drift but those of the two crossing cases is slope * t, so a step shifts by slope / lattice constant cells.  The likelihood pulls
+the distribution back at every step:
 the mass stays inside the grid and the renormalising sum stays O(1) -- none of the ill-conditioning DETERMINISTIC_FUZZ / COAL_NOISE_CHAINS
 (tests/tolerances.py) exist for.  Every case takes the registered FFT_FLOOR (the reference's own spline round-off).
 """
@@ -49,7 +50,17 @@ def _bs_mean_direct(t, slope_m=0.7):
     return slope_m * t
 
 
-for _f in (_bs_mean, _bs_std, _bs_mean_mixed, _bs_std_ragged, _bs_mean_long, _bs_std_long, _bs_mean_small, _bs_mean_direct):
+# accel * t^2: a step from t to t + 1 shifts by accel (2 t + 1) -- fewer than 12 cells early in the series, more later
+def _bs_mean_cross(t, accel_m=0.045):
+    return accel_m * t ** 2
+
+
+def _bs_mean_cross_hyper(t, accel_m=np.array([0.03, 0.045, 0.07])):
+    return accel_m * t ** 2
+
+
+for _f in (_bs_mean, _bs_std, _bs_mean_mixed, _bs_std_ragged, _bs_mean_long, _bs_std_long, _bs_mean_small, _bs_mean_direct, _bs_mean_cross,
+           _bs_mean_cross_hyper):
     cases.FUNCS.setdefault(_f.__name__[1:], _f)
 
 # (the std axis starts at 0.1, not 0: no denormal likelihood cells, every number is held to the bar -- tests/combined_cases.py: G2)
@@ -94,7 +105,13 @@ BIGSHIFT = {
     'bigshift_long0': _case(211, ('Deterministic', 'bs_mean_long', 'mean'), om=G_LONG0, T=3, fit=dict(evidenceOnly=True)),
     'bigshift_long1': _case(212, ('Deterministic', 'bs_std_long', 'std'), om=G_LONG1, T=3, fit=dict(evidenceOnly=True), axes=(1,)),
     'bigshift_laplace': _case(213, ('Combined', [('GRW', 's', 0.3, 'mean', None), DET_MEAN]), om=G_LAPLACE),
+    # a drift that crosses 12 cells per step DURING the series: accel 0.045 on mean = 1.4925 (2 t + 1) cells, i.e. 1.5, 4.5, 7.5, 10.4,
+    # 13.4, 16.4, 19.4 -- steps of the fused kernel's stencil and steps with the large-shift stage in ONE program, forward and backward;
+    # the hyper-study's chains (0.995, 1.4925, 2.32 cells x (2 t + 1)) cross at the last step, at the fifth and at the fourth
+    'bigshift_crossing': _case(215, ('Deterministic', 'bs_mean_cross', 'mean'), T=8),
+    'bigshift_crossing_hyper': _case(216, ('Deterministic', 'bs_mean_cross_hyper', 'mean'), T=8, study='HyperStudy'),
 }
+CROSSING = ('bigshift_crossing', 'bigshift_crossing_hyper')
 
 # the control: 8.3 cells per step -- the small-shift stencil inside the fused step kernel, no stage, no large-shift kernel
 CONTROL = {'bigshift_small_control': _case(214, ('Deterministic', 'bs_mean_small', 'mean'), axes=())}

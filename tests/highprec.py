@@ -12,6 +12,9 @@ Every quantity is a sum of n terms.  For float64 terms of one sign, summed in AN
 and every further rounded operation adds one u.  The bound functions below are that count for each operation, times SLACK = 2 and nothing
 more.  The references are carried in np.longdouble (64-bit mantissa on x86: 2 ** -11 of u per operation); on a platform whose long
 double is a float64 the sums fall back to math.fsum (exact) per cell.
+
+The second half of the file restates the stages of a TRANSITION the same way (the Deterministic model's spline shift with a running bound,
+the renormalisation, RegimeSwitch, NotEqual, the random walk) for tests/test_transition_kernels.py; its recursions need the wider type.
 """
 import math
 
@@ -223,3 +226,276 @@ def worst(got, want, bound):
     if q.size == 0:
         return 0.0
     return float(np.max(np.where(np.isnan(q), LD(np.inf), q)))
+
+
+# ---- stages of a transition: the Deterministic model's spline shift and what can stand before or behind it -----------------------------
+#
+# Written from the reference (transitionModels.py:559-606: scipy.ndimage.shift(order = 3, mode = 'nearest') and the division by the sum;
+# :405-412 RegimeSwitch; :462-471 NotEqual; :107-115 the random walk as scipy.ndimage.gaussian_filter1d) and from SciPy's ni_splines.c
+# recursion as oracle/bl_oracle.py documents it (spline_prefilter_reflect, spline_shift_nearest), not from the kernels.
+#
+# Every stage function takes the stage's input v (float64 or longdouble) and the bound e >= |device input - v| the input comes with (0 or
+# None for a caller's array) and returns the output and ITS bound: the incoming bound carried through the stage's magnitudes plus the
+# stage's own rounded operations.  These `e` are first-order bounds WITHOUT the file's SLACK: a test multiplies the last one by SLACK, once.
+
+SPLINE_POLE = -0.2679491924311227          # SciPy's float64 literal (ni_splines.c: get_filter_poles, order 3)
+SPLINE_PAD = 12                            # edge samples per side (_prepad_for_spline_filter, mode 'nearest')
+REQUIRES_EXTENDED = 'the spline recursion needs a long double wider than float64 (no exact-sum fallback exists for a recursion)'
+
+# rounded float64 operations of the device per element, counted along the device's order of evaluation (blk::spline_prefilter_wave: a lane
+# owns a chunk of C = spline_chunk(N) elements; blk::bigshift_kernel samples).  Counts, not measurements:
+C_GAIN = 4        # x * gain: the product, and the float64 constant (1 - z) (1 - 1 / z) itself (a subtraction, a quotient and subtraction, a product)
+C_PASS = 20       # one first-order pass, per element: the sweep with a zero carry-in and the sweep from the true carry-in, a product and a
+#                   sum each (4); the carry that enters the chunk went through six affine_step()s, each a fused multiply-add of the carry (6)
+#                   and a product of the factors z^len (6); those factors come from pow(): within 2 ulp = 4 u.  Every one of these
+#                   acts on a value whose magnitude the running m[i] dominates, so the element collects (4 + 6 + 6 + 4) u m[i].
+C_TOP = 3         # u[N-1] = y[N-1] * (z / (z - 1)): the constant's subtraction and quotient, the product
+W_OPS = 6         # a B-spline weight in float64: |pp - k| (1), then 2/3 - a a + a a a / 2 (the constant, two products + one, two sums; the
+#                   halving is exact) or (2 - a)^3 / 6: at most 6 operations on quantities <= 1, so the weight is off by <= 6 u ABSOLUTELY
+C_SAMPLE = 5      # the four fused multiply-adds of the weighted sum and the product with the stage's input scale
+
+
+def spline_chunk(N):
+    """elements per lane of the device's prefilter for a padded line of N (its operation count enters the bound of c[0])"""
+    return ((int(N) + 63) >> 6) | 1
+
+
+def c_init(N):
+    """Rounded operations behind the causal initialisation c[0] += z / (1 - z^2N) sum_i z^i (c[i] + z^N c[N-1-i]), per term of the sum:
+    z^N from pow() (4) times c (1) plus c (1); z^i = pow() of the chunk's first index (4) times C products (C); the product with it (1);
+    the lane's running sum (C) and the six steps of the wave's sum (6); the factor z / (1 - z^2N) (a product, a subtraction, a quotient: 3)
+    and the product with it (1); the sum with c[0] (1): 22 + 2 C."""
+    return 22 + 2 * spline_chunk(N)
+
+
+def _moved(x, axis):
+    return np.moveaxis(np.asarray(x), axis, 0)
+
+
+_MEMO = {}
+
+
+def _memo(tag, arrays, make):
+    """the coefficients of a line do not depend on the shift: the last few results are kept, keyed by the content of their inputs"""
+    import hashlib
+    key = (tag,) + tuple(None if a is None else (a.shape, a.dtype.str, hashlib.sha1(np.ascontiguousarray(a).tobytes()).hexdigest()) for a in arrays)
+    if key not in _MEMO:
+        if len(_MEMO) >= 8:
+            _MEMO.clear()
+        _MEMO[key] = make()
+    return _MEMO[key]
+
+
+def _need_extended():
+    if not EXTENDED:
+        raise NotImplementedError(REQUIRES_EXTENDED)
+
+
+def _pad_index(n):
+    return np.clip(np.arange(n + 2 * SPLINE_PAD) - SPLINE_PAD, 0, n - 1)
+
+
+def _causal_init(c, z, zN):
+    """SciPy's _init_causal_reflect, in its own (in-place) order: the last term reads the running sum as c[0]."""
+    N = c.shape[0]
+    acc = c[0] + zN * c[N - 1]
+    zi = z
+    for i in range(1, N):
+        acc = acc + zi * (c[i] + zN * (c[N - 1 - i] if i < N - 1 else acc))
+        zi = zi * z
+    return acc * (z / (LD(1) - zN * zN)) + c[0]
+
+
+def spline_coefficients(xm):
+    """Cubic-spline coefficients of the lines xm (n, ...) along axis 0, padded by 12 edge samples per side -> (n + 24, ...) longdouble:
+    gain, causal initialisation, causal recursion, anti-causal initialisation and recursion (ni_splines.c: apply_filter, reflect)."""
+    _need_extended()
+    n = xm.shape[0]
+    N = n + 2 * SPLINE_PAD
+    z = LD(SPLINE_POLE)
+    with np.errstate(under='ignore'):
+        c = _ld(xm)[_pad_index(n)] * ((LD(1) - z) * (LD(1) - LD(1) / z))
+        zN = z ** N
+        c[0] = _causal_init(c, z, zN)
+        for i in range(1, N):
+            c[i] = c[i] + z * c[i - 1]
+        c[N - 1] = c[N - 1] * (z / (z - LD(1)))
+        for i in range(N - 2, -1, -1):
+            c[i] = z * (c[i + 1] - c[i])
+    return c
+
+
+def _coefficient_bound(am, e_in=None):
+    """The running bound of spline_coefficients for lines of magnitudes am = |x| (n, ...): -> (m, e), both (n + 24, ...).
+    m follows the same recursions with |z| and |x| (nothing cancels); e follows them too and collects c u m at every element:
+        causal        e[i] = |z| e[i-1] + c m[i]
+        anti-causal   e[i] = |z| (e[i+1] + e[i]) + c m[i]
+    (+ c TINY per element for products below the normal range).  e_in: a bound the input came with (n, ...), carried along."""
+    _need_extended()
+    n = am.shape[0]
+    N = n + 2 * SPLINE_PAD
+    z = LD(SPLINE_POLE)
+    az = abs(z)
+    u, tiny = LD(U), LD(TINY)
+    idx = _pad_index(n)
+    with np.errstate(under='ignore'):
+        g = abs((LD(1) - z) * (LD(1) - LD(1) / z))
+        m = _ld(am)[idx] * g
+        e = C_GAIN * (u * m + tiny)
+        if e_in is not None:
+            e = e + g * _ld(np.broadcast_to(e_in, am.shape))[idx]
+        azN = az ** N
+        m0 = _causal_init(m, az, azN)
+        e[0] = _causal_init(e, az, azN) + c_init(N) * (u * m0 + tiny)
+        m[0] = m0
+        for i in range(1, N):
+            m[i] = m[i] + az * m[i - 1]
+            e[i] = e[i] + az * e[i - 1] + C_PASS * (u * m[i] + tiny)
+        top = abs(z / (z - LD(1)))
+        m2, e2 = np.empty_like(m), np.empty_like(e)
+        m2[N - 1] = top * m[N - 1]
+        e2[N - 1] = top * e[N - 1] + C_TOP * (u * m2[N - 1] + tiny)
+        for i in range(N - 2, -1, -1):
+            m2[i] = az * (m2[i + 1] + m[i])
+            e2[i] = az * (e2[i + 1] + e[i]) + C_PASS * (u * m2[i] + tiny)
+    return m2, e2
+
+
+def _sample_points(n, d):
+    """(index k, longdouble weight w, whether the weight is a computed one) of the four coefficients behind every output cell i: the
+    coordinate is the FLOAT64 quantity fl(fl(i - d) + 12) that SciPy, the oracle and the device all form; everything after it is exact
+    (pp - k is) or longdouble."""
+    pp = (np.arange(n, dtype=np.float64) - np.float64(d)) + np.float64(SPLINE_PAD)
+    fl = np.floor(pp)
+    N = n + 2 * SPLINE_PAD
+    out = []
+    for dk in (-1, 0, 1, 2):
+        a = np.abs(_ld(pp) - (_ld(fl) + LD(dk)))
+        w = np.where(a < 1, LD(2) / LD(3) - a * a + a * a * a / LD(2), np.where(a < 2, (LD(2) - a) ** 3 / LD(6), LD(0)))
+        k = np.clip(fl + dk, 0, N - 1).astype(np.int64)              # the coefficient index clipped to [0, N - 1]
+        out.append((k, w, a < 2))
+    return out
+
+
+def _expand(w, ndim):
+    return w.reshape((-1,) + (1,) * (ndim - 1))
+
+
+def spline_shift(x, d, axis):
+    """scipy.ndimage.shift(x, d along `axis`, order = 3, mode = 'nearest') in longdouble: out[i] = sum_k beta3(pp_i - k) c[clip(k, 0, N - 1)],
+    pp_i = fl(fl(i - d) + 12), c = spline_coefficients of the lines along `axis`."""
+    xm = _moved(x, axis)
+    c = _memo('c', [xm], lambda: spline_coefficients(xm))
+    out = np.zeros(xm.shape, dtype=LD)
+    with np.errstate(under='ignore'):
+        for k, w, _ in _sample_points(xm.shape[0], d):
+            out = out + _expand(w, xm.ndim) * c[k]
+    return np.moveaxis(out, 0, axis)
+
+
+def _shift_err(x, d, axis, e_in=None):
+    """first-order bound of the device's shift against spline_shift(x, d, axis), without SLACK: the coefficients' running bound through
+    the four weights (sum_k w_k e_k), the weights' own rounding (W_OPS u m_k for every computed weight), the four fused multiply-adds and the
+    product with the input scale (C_SAMPLE u sum_k w_k m_k), one TINY per product"""
+    xm = _moved(x, axis)
+    em = None if e_in is None else _moved(np.broadcast_to(e_in, np.shape(x)), axis)
+    m, e = _memo('e', [xm, em], lambda: _coefficient_bound(np.abs(_ld(xm)), em))
+    u = LD(U)
+    out = np.zeros(xm.shape, dtype=LD)
+    with np.errstate(under='ignore'):
+        for k, w, computed in _sample_points(xm.shape[0], d):
+            wk, ck = _expand(w, xm.ndim), _expand(computed.astype(LD), xm.ndim)
+            out = out + wk * e[k] + (W_OPS * u * ck + C_SAMPLE * u * wk) * m[k] + LD(2 * TINY)
+    return np.moveaxis(out, 0, axis)
+
+
+def spline_shift_bound(x, d, axis):
+    """|device shift - spline_shift(x, d, axis)| per cell: the running bound (_coefficient_bound, _shift_err) times SLACK.  Counts per
+    element and pass: C_GAIN = 4, c_init(N) = 22 + 2 C for c[0], C_PASS = 20 for each recursion, C_TOP = 3, W_OPS = 6 per weight,
+    C_SAMPLE = 5 -- derived above, none of them fitted to a device."""
+    return SLACK * _shift_err(x, d, axis)
+
+
+def shift_stage(v, e, d, axis):
+    """the shift alone (no renormalisation): -> (spline_shift(v), bound)"""
+    return spline_shift(v, d, axis), _shift_err(v, d, axis, e)
+
+
+def normalise_stage(v, e, nblk=1):
+    """v / sum(v) (transitionModels.py:603, :410, core.py:389): -> (r, bound of r, D = sum v, bound of D).  The device sums G = v.size values
+    in nblk block partials: |D^ - D| <= sum e + (G + nblk) u sum |v|; the quotient (a reciprocal and a product): 2 u, one TINY."""
+    v = _ld(v)
+    e = np.zeros(v.shape, dtype=LD) if e is None else _ld(np.broadcast_to(e, v.shape))
+    G = v.size
+    D = v.sum() if EXTENDED else _sum(v.reshape(-1), 0)
+    eD = e.sum() + (G + nblk) * LD(U) * np.abs(v).sum()
+    r = v / D
+    er = e / abs(D) + np.abs(v) * eD / (D * D) + 2 * LD(U) * np.abs(r) + LD(TINY)
+    return r, er, D, eD
+
+
+def scale_stage(v, e, factor):
+    """v * factor for a float64 factor: one product"""
+    v = _ld(v)
+    e = np.zeros(v.shape, dtype=LD) if e is None else _ld(np.broadcast_to(e, v.shape))
+    f = LD(float(factor))
+    r = v * f
+    return r, e * abs(f) + LD(U) * np.abs(r) + LD(TINY)
+
+
+def deterministic_stage(v, e, d, axis, nblk=1):
+    """Deterministic (transitionModels.py:581-583 / :600-603): the shift, then the division by the sum -> (r, bound, D, bound of D)"""
+    o, eo = shift_stage(v, e, d, axis)
+    return normalise_stage(o, eo, nblk)
+
+
+def regime_switch_stage(v, e, limit, nblk=1):
+    """RegimeSwitch (:405-412): cells below `limit` (a float64: 10^value dV, formed with pow() and a product: 2 u) are set to it, then
+    the division by the sum.  Clamping does not enlarge a difference."""
+    v = _ld(v)
+    e = np.zeros(v.shape, dtype=LD) if e is None else _ld(np.broadcast_to(e, v.shape))
+    lim = LD(float(limit))
+    w = np.where(v < lim, lim, v)
+    return normalise_stage(w, e + 2 * LD(U) * lim, nblk)[:2]
+
+
+def not_equal_stage(v, e, limit, nblk=1):
+    """NotEqual (:462-471): (max - v) / (G max - sum v), then RegimeSwitch's clamp and division.  The maximum is off by at most max e; the
+    denominator is formed from G max (one product) and the sum (G + nblk terms), which cancel: its bound is relative to G |max| + sum |v|,
+    not to itself."""
+    v = _ld(v)
+    e = np.zeros(v.shape, dtype=LD) if e is None else _ld(np.broadcast_to(e, v.shape))
+    G, u = v.size, LD(U)
+    mx, emx = v.max(), e.max()
+    a = mx - v
+    ea = e + emx + u * np.abs(a)
+    den = a.sum()
+    eden = G * emx + e.sum() + u * (2 * G * abs(mx) + (G + nblk) * np.abs(v).sum())
+    r = a / den
+    er = ea / abs(den) + np.abs(a) * eden / (den * den) + 2 * u * np.abs(r) + LD(TINY)
+    return regime_switch_stage(r, er, limit, nblk)
+
+
+def walk_stage(v, e, weights, axis):
+    """GaussianRandomWalk (:107-115) as a reflect-boundary correlation with the float64 tap `weights` (odd count, centred), taken as DATA
+    from the oracle's program for the same model: out[i] = sum_j w[j] v[reflect(i + j - r)].  Bound: the incoming one through the same
+    weights, plus (taps + 2) u of sum_j |w_j| |v|: a product and a sum per tap, one u for a weight that the device formed itself, one spare
+    for a fused order; one TINY per tap."""
+    v = _ld(v)
+    e = np.zeros(v.shape, dtype=LD) if e is None else _ld(np.broadcast_to(e, v.shape))
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    r = len(w) // 2
+    assert len(w) == 2 * r + 1
+    vm, em = np.moveaxis(v, axis, 0), np.moveaxis(e, axis, 0)
+    n = vm.shape[0]
+    out, mag, eo = (np.zeros(vm.shape, dtype=LD) for _ in range(3))
+    for j in range(len(w)):
+        idx = np.arange(n) + j - r
+        idx = np.mod(idx, 2 * n)
+        idx = np.where(idx >= n, 2 * n - 1 - idx, idx)                 # half-sample symmetric: (d c b a | a b c d | d c b a)
+        wj = LD(w[j])
+        out = out + wj * vm[idx]
+        mag = mag + abs(wj) * np.abs(vm[idx])
+        eo = eo + abs(wj) * em[idx]
+    eo = eo + (len(w) + 2) * LD(U) * mag + len(w) * LD(TINY)
+    return np.moveaxis(out, 0, axis), np.moveaxis(eo, 0, axis)

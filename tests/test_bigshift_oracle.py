@@ -62,20 +62,28 @@ def test_oracle_matches_bigshift_direct_calls(name):
 
 
 def test_every_case_shifts_as_far_as_it_says():
-    """the non-control cases shift by more than 12 cells in some step, the control by less (what selects the kernel on the device)"""
+    """the non-control cases shift by more than 12 cells in some step -- the largest step over the case's time stamps --, the control by
+    less (what selects the kernel on the device); the crossing cases also stay below 12 cells in some step, in every chain"""
     import cases
     for name, c in ALL.items():
         S = cases.build(bl, c)
         lattice = dict(zip(S.observationModel.parameterNames, S.latticeConstant))
-        far = 0.0
+        ts = np.asarray(S.rawTimestamps, dtype=float)          # (segment length 1: the formatted time stamps are these)
+        assert len(ts) >= 2 and ts[0] == 0.0
+        steps = []                                   # per Deterministic model: |f(t + 1) - f(t)| in cells, (time stamps, chains)
 
         def walk(spec):
-            nonlocal far
             if spec[0] == 'Deterministic':
                 f = cases.FUNCS[spec[1]]
-                far = max(far, float(np.max(np.abs(np.asarray(f(1.0)) - np.asarray(f(0.0))))) / lattice[spec[2]])
+                steps.append(np.array([np.abs(np.atleast_1d(np.asarray(f(t + 1.0)) - np.asarray(f(t)))) for t in ts[:-1]]) / lattice[spec[2]])
             elif spec[0] in ('Combined', 'Serial'):
                 for s in spec[1]:
                     walk(s)
         walk(c['tm'])
+        far = max(float(s.max()) for s in steps)
+        first = max(float(s[0].max()) for s in steps)
+        assert far >= first
         assert (far < 12.0) if name in bc.CONTROL else (far > 12.0), (name, far)
+        if name in bc.CROSSING:
+            for s in steps:
+                assert np.all(s.min(axis=0) < 12.0) and np.all(s.max(axis=0) > 12.0), (name, s)
