@@ -298,6 +298,8 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
             }
             FP.step0 = step;
             FP.use_rec = (p->obs_model == BLHIP_OM_GAUSSIAN && dev <= 8.0 * 2.3e-16 * mx && ctx->option("recurrence", 1.0) != 0.0) ? 1 : 0;
+            // ... and arguments inside its envelope (exponents are added in int, exp_mn clamps): beyond it the per-cell exponential
+            if (FP.use_rec && !(rec_envelope_bound(m0h, g.n0, p->marginal[1], g.n1, p->data, T * p->seg_len, p->data_dim) <= REC_ENVELOPE)) FP.use_rec = 0;
         }
         // ---- the resident paths (single chain: blhip_resident.hpp; batches of chains: blhip_chainres.hpp); the launch-per-step kernels
         //      below are their fall-back ---------------------------------------------------------------------------------------------------
@@ -1034,6 +1036,15 @@ int blhip_host_unlag(int scheme, double *sums, int64_t T, int lag, const unsigne
     } catch (...) {
         return -1;
     }
+}
+
+int blhip_host_rec_envelope(const blhip_problem *p, double *bound_out) {
+    if (!p || p->ndim != 2 || p->obs_model != BLHIP_OM_GAUSSIAN || !p->marginal[0] || !p->marginal[1] || !p->data || p->n[0] < 2 || p->n[1] < 1 ||
+        p->T < 1 || p->seg_len < 1 || p->data_dim < 1)
+        return -1;
+    const double b = rec_envelope_bound(p->marginal[0], (int)p->n[0], p->marginal[1], (int)p->n[1], p->data, p->T * p->seg_len, p->data_dim);
+    if (bound_out) *bound_out = b;
+    return b <= REC_ENVELOPE ? 1 : 0;
 }
 
 int blhip_set_option(blhip_ctx *ctx, const char *key, double value) {

@@ -122,6 +122,42 @@ FitFlags decode_flags(blhip_ctx *ctx, const blhip_problem *p, uint32_t flags, co
     return f;
 }
 
+// ---- the envelope of the Gaussian likelihood recurrence ----------------------------------------------------------------------------------------
+// The recurrence kernels carry the likelihood as mantissa * 2^exponent and add the exponents of the anchor (a0), of the ratio (d1) and of the
+// curvature (d2) in `int`, and blmath::exp_mn clamps its argument to +-1.4e9.  Both are harmless only while every argument a kernel can
+// form stays small: this bounds |a0| + steps |d1| + steps^2 / 2 |d2| over every record, every std column and every row of the lattice
+// continued REC_PAD_ROWS rows beyond either end of the grid (the padded tiles of the resident and chain kernels run the recurrence through
+// rows outside the grid), for the longest anchor interval (REC_MAX_STEPS steps of REC_MAX_STRIDE rows).  A fit whose bound exceeds
+// REC_ENVELOPE takes the per-cell exponential flavours (exact zeros where the likelihood underflows).  1e9 log2(e) = 1.44e9 < 2^31.
+constexpr double REC_ENVELOPE = 1.0e9;
+constexpr int REC_PAD_ROWS = 256, REC_MAX_STRIDE = 4, REC_MAX_STEPS = 32;
+
+inline double rec_envelope_bound(const double *m0, int n0, const double *s, int n1, const double *data, int64_t n_rec, int dd) {
+    if (n0 < 2 || n1 < 1) return 0.0;
+    const double step = std::fabs((m0[n0 - 1] - m0[0]) / (double)(n0 - 1));
+    const double lo = std::min(m0[0], m0[n0 - 1]) - REC_PAD_ROWS * step, hi = std::max(m0[0], m0[n0 - 1]) + REC_PAD_ROWS * step;
+    double D = 0.0, dn = 0.0;
+    for (int64_t t = 0; t < n_rec; ++t) {
+        double n = 0.0;
+        for (int k = 0; k < dd; ++k) {
+            const double x = data[t * dd + k];
+            if (x == x) {
+                n += 1.0;
+                D = std::max(D, std::max(std::fabs(x - lo), std::fabs(x - hi)));
+            }
+        }
+        dn = std::max(dn, n);
+    }
+    double cA = 0.0, cB = 0.0;
+    for (int j = 0; j < n1; ++j) {
+        cA = std::max(cA, 1.0 / (2.0 * s[j] * s[j]));
+        cB = std::max(cB, std::fabs(0.5 * std::log(2.0 * M_PI * s[j] * s[j])));
+    }
+    const double H = REC_MAX_STRIDE * step;
+    const double b = dn * (D * D * cA + cB) + REC_MAX_STEPS * (2.0 * cA * H * dn * D) + 0.5 * REC_MAX_STEPS * REC_MAX_STEPS * (2.0 * cA * dn * H * H);
+    return b == b ? b : INFINITY;          // (a NaN bound -- a zero or NaN std -- is no envelope)
+}
+
 // what every chain of the call shares, resident in HBM for the duration of the call
 struct DeviceTables {
     double *m0, *m1, *colA, *colB, *rec, *prior, *reset, *uniform, *indep, *lik;

@@ -14,7 +14,11 @@
 //  * Gaussian likelihood WITHOUT an exp per cell: along a column the exponent is a quadratic in the row index, so
 //    L(row) follows a second-order multiplicative recurrence, carried as mantissa * 2^exponent (cannot overflow, and
 //    cannot lose a value to underflow on the way towards the likelihood peak); re-anchored every 16 rows with exact
-//    exponentials (error << 1e-12 relative).  p / L of the backward pass uses the reciprocal recurrence: no division.
+//    exponentials.  Counted relative error 15 rows behind an anchor (tests/highprec.py, likelihood_bound_rec): 486 u = 5.4e-14 from the
+//    exponentials and mantissa products, plus the rounded arguments, (5 + 2 dn) u |a0| + 15 (7 + dn) u cA step sum |x - mu| -- on 128 rows
+//    over [-8, 8]: 8e-14 for std 4, 6e-12 for std 0.25, 1e-10 for std 0.03.  The host admits the recurrence only while every argument
+//    stays below 1e9 (rec_envelope_bound, blhip_batch.hpp); beyond that one exp per cell.  p / L of the backward pass uses the reciprocal
+//    recurrence: no division.
 //  * lazy normalisation and deterministic per-block partial sums as in blk::step_kernel.
 //
 // Algorithmic HBM traffic per cell and step: forward 16 B (read state, write state), backward 32 B.

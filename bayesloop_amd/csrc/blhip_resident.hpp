@@ -415,8 +415,10 @@ struct Res {
     static constexpr int NT = TR * NSH;
     static_assert(TR * NSH == TC * NSV, "both passes use every thread");
     static_assert(NSH >= 2 && NSV >= 2, "edge segments need an in-tile neighbour segment on their near side");
-    // rows between exact re-anchorings of the likelihood recurrence: once per segment, at most 32 rows apart.  The recurrence's
-    // relative error grows like n^2 / 2 ulp in the worst case (n rows since the anchor): 32 rows -> 6e-14, four decades inside the bar
+    // rows between exact re-anchorings of the likelihood recurrence: once per segment, at most 32 rows apart.  The mantissa's relative
+    // error grows like (3 (1 + n + n (n - 1) / 2) + n + n (n - 1) / 2) u with the n rows since the anchor (three exponentials of 3 u each
+    // and the products, counted in tests/highprec.py): 31 rows -> 1990 u = 2.2e-13; with the rounded arguments 2.7e-13 for std 4, 1.3e-11
+    // for std 0.25 on 128 rows over [-8, 8]
     static constexpr int ANCHOR = SEG < 32 ? SEG : 32;
     static_assert(TR % SEG == 0 && TC % SEG == 0 && TR >= 2 * R && TC >= 2 * R && ANCHOR % CHK == 0 && SEG % ANCHOR == 0, "tile shape");
     static constexpr int NW = NT / 64;

@@ -302,6 +302,14 @@ int blhip_accum_row_stats(blhip_ctx *ctx, const blhip_problem *problem, double *
  * Returns 0, or 1 if a sum left (1e-150, 1e150) -- the fit then repeats the batch with the launch-per-step kernels. */
 int blhip_host_unlag(int scheme, double *sums, int64_t T, int lag, const unsigned char *kinds, double *scales_out);
 
+/* Whether a two-parameter Gaussian fit takes the likelihood RECURRENCE along the rows (1) or one exponential per cell (0); -1: not such a
+ * problem.  The recurrence carries exp() as mantissa * 2^exponent with the exponents added in int and its anchors clamped to +-1.4e9, so
+ * it is used only while  dn (D^2 cA + |cB|) + 32 |d1| + 512 |d2| <= 1e9  for the largest cA = 1 / (2 s^2), |cB| = |log(2 pi s^2)| / 2 of
+ * the std grid, the most values dn of a record, the largest distance D of a datum from the mean lattice continued 256 rows beyond either
+ * end, and first / second differences d1, d2 of the argument over 4 rows.  bound_out (may be NULL): the left-hand side.  Reads
+ * marginal[0..1], n, data, T, seg_len, data_dim of the problem. */
+int blhip_host_rec_envelope(const blhip_problem *problem, double *bound_out);
+
 /* ---- multi-GPU exchange of a sharded hyper-study (HyperStudy.fit(nJobs > 1), core.py:1307-1340, 1443-1495) -------------
  * One process per GPU, one context per process; each rank fits its share of the hyper-grid points with blhip_fit and
  * no communication, then the ranks exchange results through RCCL (xGMI inside a node), which this library binds

@@ -15,6 +15,10 @@ double is a float64 the sums fall back to math.fsum (exact) per cell.
 
 The second half of the file restates the stages of a TRANSITION the same way (the Deterministic model's spline shift with a running bound,
 the renormalisation, RegimeSwitch, NotEqual, the random walk) for tests/test_transition_kernels.py; its recursions need the wider type.
+
+The third part restates the GAUSSIAN LIKELIHOOD (observationModels.py:566-567, :49-54, :705-706), counts the rounded operations of the two
+ways the kernels evaluate it (one exp per value and cell; the multiplicative recurrence along the rows, anchored with blmath::exp_mn) and
+runs a small forward-backward pass with a running bound for tests/test_likelihood_kernels.py.
 """
 import math
 
@@ -499,3 +503,252 @@ def walk_stage(v, e, weights, axis):
         eo = eo + abs(wj) * em[idx]
     eo = eo + (len(w) + 2) * LD(U) * mag + len(w) * LD(TINY)
     return np.moveaxis(out, 0, axis), np.moveaxis(eo, 0, axis)
+
+
+# ---- the Gaussian likelihood and a small forward-backward pass ----------------------------------------------------------------------------
+#
+# Written from the reference: observationModels.py:566-567 (Gaussian.pdf: exp(-(x - mu)^2 / (2 s^2) - 0.5 log(2 pi s^2))), :49-54 (the product
+# over the values of a record, a NaN value contributing 1), :705-706 (GaussianMean: the same expression with the datum's own s), and
+# core.py:372-470 (the two passes).  The bounds are counted along the kernel sources (bayesloop_amd/csrc): blhip_fast.hpp / blhip_mfma.hpp /
+# blhip_resident.hpp / blhip_chainres.hpp / blhip_chainax.hpp (anchor terms a0, d1, d2; blmath::exp_mn and inv_m of blhip_expmn.hpp; the
+# products mE *= mR, mR *= mq) and blhip_batch.hpp (the column constants cA = 1 / (2 s s), cB = 0.5 log(2 pi s s) formed on the host).
+#
+# Per-cell exponential (REC = false, blk::step_kernel<2>, the GaussianMean kernels, and NumPy's evaluation in oracle/bl_oracle.py), per value:
+#     q = x - mu                 1 u relative, 2 u in q q
+#     q q                        1 u
+#     cA = 1 / (2 s s)           2 u (the square, the reciprocal; the oracle: the square and the division)
+#     (q q) cA  (or its fma)     1 u                                  -> C_ARG_A = 7 u A with the final subtraction, A = q^2 / (2 s^2)
+#     cB: 2 pi s s               3 u in the argument of log = 3 u absolute, log itself 1 u |cB|, the subtraction 1 u |cB|   -> 2 u |cB| + 4 u
+#     exp                        within 1 ulp = 2 u (C_EXP), one product per value.
+# Recurrence (REC = true): the anchor every `rmax + 1` steps of `stride` rows; r steps later the kernel holds
+#     exp(a0) exp(d1)^r exp(d2)^(r (r - 1) / 2)   as mantissa * 2^exponent,
+# so the argument's error is e(a0) + r e(d1) + r (r - 1) / 2 e(d2), plus what the grid's own rounding does to the model (the true row
+# coordinates are mu[0] + i step only to rounding: the anchors read the rounded ones, the second difference uses the host's step), and the
+# mantissa collects C_EXPMN u per exponential it is a product of and one u per product.  Counts:
+#     a0 = sum_k fma(-(q q), cA, a0) - cB     5 u A_k (q twice, q q, cA twice) + 2 u per partial sum (fma, subtraction) + cB's (3 + |cB|) u
+#     s1 = sum_k (x - mu0) + (x - mu1)         (2 + dn) u sum_k (|x - mu0| + |x - mu1|)
+#     d1 = cA (mu1 - mu0) s1                   cA 2 u, the difference 1 u, two products: 5 u |d1|, together (7 + dn) u cA |mu1 - mu0| sum_k (..)
+#     d2 = -2 cA dn (stride step)^2            cA 2 u, four products: 6 u |d2|
+#     blmath::exp_mn                           the two reduction fmas 1 u |r| each, |r| <= 0.35 (the first is exact for large |kn|: tests/test_highprec.py);
+#                                              the split ln 2 = hi + lo is off by 2e-26, times |kn| <= 2.02e9: 0.4 u; thirteen Horner fmas whose
+#                                              errors are damped by |r| each: 1 / (1 - 0.35) u; truncation 0.35^14 / 14! = 0.04 u   -> C_EXPMN = 3 u
+#     blmath::inv_m                            v_rcp_f64 and one Newton step (two fmas)                      -> C_INVM = 2 u
+
+C_ARG_A, C_ARG_B, C_ARG_0 = 7, 2, 4
+C_EXP = 2
+C_EXPMN = 3
+C_INVM = 2
+C_CELL = 6        # rounded products per cell and step around the likelihood: the step's (lagged) scale and its formation, the product with the
+#                   likelihood, the product of the two messages, the stored normalisation
+PI_LD = LD(4) * np.arctan(LD(1))
+LAZY_LAG = 4      # steps a kernel's normaliser may lag behind (gaussian_fit: lazy)
+
+
+def _values(record):
+    return [float(x) for x in np.asarray(record, dtype=np.float64).reshape(-1) if x == x]
+
+
+def gaussian_terms(mu, s, record):
+    """Per non-NaN value of the record: (A_k, arg_k) on the grid (n0, n1) in longdouble, A_k = (x_k - mu)^2 / (2 s^2), arg_k = -A_k - cB;
+    and cA = 1 / (2 s^2), cB = 0.5 log(2 pi s^2), both (1, n1)."""
+    mu = _ld(mu).reshape(-1, 1)
+    s = _ld(s).reshape(1, -1)
+    cA = LD(1) / (LD(2) * s * s)
+    cB = LD(0.5) * np.log(LD(2) * PI_LD * s * s)
+    out = []
+    for x in _values(record):
+        q = LD(x) - mu
+        A = q * q * cA
+        out.append((A, -A - cB))
+    return out, cA, cB
+
+
+def gaussian_likelihood(mu, s, record):
+    """prod over the non-NaN values x of exp(-(x - mu)^2 / (2 s^2) - 0.5 log(2 pi s^2)) on the grid mu (n0) x s (n1); all NaN: 1."""
+    terms, _, _ = gaussian_terms(mu, s, record)
+    L = np.ones((np.size(mu), np.size(s)), dtype=LD)
+    with np.errstate(under='ignore'):
+        for _, arg in terms:
+            L = L * np.exp(arg)
+    return L
+
+
+def gaussian_mean_likelihood(mu, x, s):
+    """GaussianMean (:705-706): the datum (x, s) on the grid of means; a NaN in either: 1."""
+    if not (x == x and s == s):
+        return np.ones(np.size(mu), dtype=LD)
+    return gaussian_likelihood(mu, [s], [x])[:, 0]
+
+
+def likelihood_bound_exp(mu, s, record, split=False, extra=0):
+    """|L^ - L| per cell for the per-value exponential (no SLACK): L sum_k (7 A_k + 2 |cB| + 4 + C_EXP + 1 + extra) u, and the subnormal step of
+    every factor through the other factors (which exceed 1 where s is small) and of every product.  split: the two parts separately."""
+    terms, _, cB = gaussian_terms(mu, s, record)
+    shape = (np.size(mu), np.size(s))
+    if not terms:
+        return (np.zeros(shape, dtype=LD),) * 2 if split else np.zeros(shape, dtype=LD)
+    u, tiny = LD(U), LD(TINY)
+    with np.errstate(under='ignore', over='ignore'):
+        Ls = [np.exp(arg) for _, arg in terms]
+        rel = np.zeros(shape, dtype=LD)
+        for A, _ in terms:
+            rel = rel + (C_ARG_A * A + C_ARG_B * np.abs(cB) + C_ARG_0 + C_EXP + 1 + extra) * u
+        L = np.ones(shape, dtype=LD)
+        for f in Ls:
+            L = L * f
+        sub = np.full(shape, tiny * len(Ls), dtype=LD)
+        for k in range(len(Ls)):
+            others = np.ones(shape, dtype=LD)
+            for j in range(len(Ls)):
+                if j != k:
+                    others = others * Ls[j]
+            sub = sub + tiny * others
+        with np.errstate(invalid='ignore'):
+            rel = np.where(L == 0, LD(0), L * np.expm1(np.minimum(rel, LD(11000))))
+        return (rel, sub) if split else rel + sub
+
+
+def host_step(mu):
+    """the row step the host hands the recurrence kernels: (mu[n - 1] - mu[0]) / (n - 1) in float64 (blhip.hip, FP.step0)"""
+    mu = np.asarray(mu, dtype=np.float64)
+    return float((mu[-1] - mu[0]) / np.float64(len(mu) - 1))
+
+
+def likelihood_bound_rec(mu, s, record, stride, rmax, dirs=(1,), split=False):
+    """|L^ - L| per cell for the recurrence (no SLACK): a cell r <= rmax steps of `stride` rows behind its anchor (in a direction of `dirs`:
+    +1 the anchor has the lower row index) -- the bound is the largest over these anchor positions, which covers every tiling."""
+    xs = _values(record)
+    shape = (np.size(mu), np.size(s))
+    if not xs:
+        return (np.zeros(shape, dtype=LD),) * 2 if split else np.zeros(shape, dtype=LD)
+    dn = len(xs)
+    u = LD(U)
+    _, cA, cB = gaussian_terms(mu, s, [])
+    mu_i = _ld(mu).reshape(-1, 1)
+    step = LD(host_step(mu))
+    lam = _ld(mu)[0] + np.arange(np.size(mu)).astype(LD) * step
+    delta = np.max(np.abs(_ld(mu) - lam))                              # how far the rounded row coordinates are from the lattice
+    H = LD(stride) * abs(step)
+    S1_i = sum(np.abs(LD(x) - mu_i) for x in xs)
+    worst_e = np.zeros(shape, dtype=LD)
+    with np.errstate(under='ignore', over='ignore'):
+        for dr in dirs:
+            for r in range(rmax + 1):
+                nu = mu_i - LD(dr * r) * H
+                A_nu = sum((LD(x) - nu) ** 2 for x in xs) * cA
+                S1_nu = sum(np.abs(LD(x) - nu) for x in xs)
+                S1_nu1 = sum(np.abs(LD(x) - (nu + LD(dr) * H)) for x in xs)
+                ea0 = u * ((5 + 2 * dn) * A_nu + dn * (3 + (1 + 2 * dn) * np.abs(cB)))
+                ed1 = u * (7 + dn) * cA * H * (S1_nu + S1_nu1)
+                ed2 = 6 * u * 2 * cA * dn * H * H
+                egrid = 2 * cA * delta * (S1_nu * (1 + 2 * r) + r * dn * H + S1_i)
+                tri = r * (r - 1) // 2
+                e = ea0 + r * ed1 + tri * ed2 + egrid + u * (C_EXPMN * (1 + r + tri) + r + tri)
+                worst_e = np.maximum(worst_e, e)
+        L = gaussian_likelihood(mu, s, record)
+        with np.errstate(invalid='ignore'):
+            rel = np.where(L == 0, LD(0), L * np.expm1(np.minimum(worst_e + (C_INVM + 1) * u, LD(11000))))      # (0 stays 0 whatever the argument's error)
+        return (rel, np.full(shape, LD(TINY), dtype=LD)) if split else rel + LD(TINY)
+
+
+def product_stage(a, ea, b, eb, ops=C_CELL):
+    """a * b for two quantities that come with bounds: -> (r, bound): first order in both, `ops` rounded operations, one TINY"""
+    a, b = _ld(a), _ld(b)
+    ea = np.zeros(a.shape, dtype=LD) if ea is None else _ld(np.broadcast_to(ea, a.shape))
+    eb = np.zeros(b.shape, dtype=LD) if eb is None else _ld(np.broadcast_to(eb, b.shape))
+    with np.errstate(under='ignore', over='ignore', invalid='ignore'):
+        r = a * b
+        e = ea * np.abs(b) + np.abs(a) * eb + ea * eb + ops * LD(U) * np.abs(r) + LD(TINY)
+    return r, e
+
+
+def gaussian_fit(prior, liks, walks, grids, lattice, nblk=1, full=True, clamp=None):
+    """core.py:372-470 in longdouble with a running bound.  prior (n0, n1) float64 (taken as given); liks: per step (L, bound of L); walks:
+    [(axis, float64 taps)] applied in list order between steps, in both directions (transitionModels.py:107-118); grids: the two marginal
+    grids; lattice: the lattice constants; clamp: log10 pMin of a RegimeSwitch behind the walks (:405-412), or None.  -> dict of (value, bound) pairs, bounds WITHOUT SLACK:
+        'alpha' [T] normalised forward states, 'norm' [T], 'local_fwd' [T] (norm dV), 'log_evidence',
+        full: 'post' [T], 'local' [T] (1 / (sum(post / L) dV); value NaN where a likelihood rounds to 0 in float64), 'means' [T] of (2,)
+        forward-only: 'means' from alpha."""
+    _need_extended()
+    T = len(liks)
+    dV = LD(float(np.prod(np.asarray(lattice, dtype=np.float64))))
+    u = LD(U)
+    g = [_ld(_grid_values(grids, k, np.shape(prior))) for k in range(2)]
+    G = int(np.size(prior))
+    out = dict(alpha=[], norm=[], local_fwd=[], post=[], local=[], means=[])
+
+    def transition(v, e):
+        for axis, taps in walks:
+            v, e = walk_stage(v, e, taps, axis)
+        if clamp is not None:
+            v, e = regime_switch_stage(v, e, float(10.0 ** clamp * float(dV)), nblk)
+        return v, e
+
+    def means_of(p, ep):
+        m, em = [], []
+        with np.errstate(under='ignore'):
+            for k in range(2):
+                m.append((p * g[k]).sum())
+                em.append((ep * np.abs(g[k])).sum() + (G + 3) * u * (np.abs(p) * np.abs(g[k])).sum())
+        return np.array(m, dtype=LD), np.array(em, dtype=LD)
+
+    def lazy(norms):
+        """>= 1: what a subnormal step of a kernel's UNNORMALISED state grows by until the row is normalised.  The kernels normalise lazily:
+        a stored state is scaled by sums up to MAXLAG = 4 steps old (blr::MAXLAG, blc::MAXLAG; the launch-per-step kernels: 1), so it sums to
+        the product of the last 1 .. 4 normalisers, not to 1 -- `norms`: those normalisers, latest first"""
+        worst_p, prod = LD(1), LD(1)
+        for N in norms[:LAZY_LAG]:
+            prod = prod * N
+            worst_p = min(worst_p, prod)
+        return LD(1) / worst_p
+
+    v, e = _ld(prior), None
+    logE, elogE = LD(0), LD(0)
+    Ns = []
+    with np.errstate(under='ignore', over='ignore', invalid='ignore', divide='ignore'):
+        for t in range(T):
+            if t > 0:
+                v, e = transition(v, e)
+            a, ea = product_stage(v, e, liks[t][0], liks[t][1])
+            ea = ea + LD(TINY) * lazy(Ns[::-1][:LAZY_LAG - 1])            # (the division by this step's own sum follows in normalise_stage)
+            r, er, N, eN = normalise_stage(a, ea, nblk)
+            Ns.append(N)
+            out['alpha'].append((r, er))
+            out['norm'].append((N, eN))
+            out['local_fwd'].append((N * dV, eN * dV + 2 * u * N * dV))
+            logE = logE + np.log(N)
+            elogE = elogE + eN / N + 2 * u * (abs(np.log(N)) + abs(logE))
+            v, e = r, er
+        logE = logE + np.log(dV)
+        out['log_evidence'] = (logE, elogE + 2 * u * abs(logE))
+        if not full:
+            out['means'] = [means_of(r, er) for r, er in out['alpha']]
+            return out
+        beta, eb = np.full(np.shape(prior), LD(1) / LD(G), dtype=LD), np.full(np.shape(prior), u / LD(G), dtype=LD)
+        post, local, means = [None] * T, [None] * T, [None] * T
+        Bs = []                                                              # the backward normalisers, latest (lowest t) last
+        for t in range(T - 1, -1, -1):
+            L, eL = _ld(liks[t][0]), _ld(liks[t][1])
+            p, ep = product_stage(out['alpha'][t][0], out['alpha'][t][1], beta, eb)
+            # the kernels multiply the STORED forward state (sums to a product of normalisers) by the lazily scaled backward message
+            ep = ep + LD(TINY) * lazy(Ns[:t + 1][::-1]) * lazy(Bs[::-1])
+            p, ep = normalise_stage(p, ep, nblk)[:2]
+            post[t] = (p, ep)
+            means[t] = means_of(p, ep)
+            if np.any(L.astype(np.float64) == 0.0):
+                local[t] = (LD(np.nan), LD(0))                           # 0 / 0 in a cell (core.py:463): the sum is NaN
+            else:
+                q = p / L
+                relL = np.where(L > eL, eL / (L - eL), LD(np.inf))
+                eq = ep / L + q * relL + 2 * u * q + LD(TINY)
+                S = q.sum()
+                eS = eq.sum() + (G + nblk) * u * S
+                val = LD(1) / (S * dV)
+                local[t] = (val, val * (eS / (S - eS) + 3 * u) + LD(TINY) if S > eS else LD(np.inf))
+            b, ebl = product_stage(beta, eb, L, eL)
+            ebl = ebl + LD(TINY) * lazy(Bs[::-1][:LAZY_LAG - 1])
+            b, ebl = transition(b, ebl)
+            beta, eb, Bt = normalise_stage(b, ebl, nblk)[:3]
+            Bs.append(Bt)
+        out['post'], out['local'], out['means'] = post, local, means
+    return out

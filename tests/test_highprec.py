@@ -359,3 +359,213 @@ def test_scipy_shift_at_the_registered_floor_only():
                 assert np.all(err <= FFT_TOL['post_atol'] + FFT_TOL['post_rtol'] * np.abs(want)), (shape, ax, kind, d, float(err.max()))
                 missed += hp.worst(got, want, hp.spline_shift_bound(x, d, ax)) > 1.0
     assert missed > 0          # (if SciPy ever met the local bound everywhere, the docstring above would be out of date)
+
+
+# ---- the Gaussian likelihood and the small forward-backward pass (tests/test_likelihood_kernels.py) ---------------------------------------
+
+def _dec(x):
+    return decimal.Decimal(x.numerator) / decimal.Decimal(x.denominator)
+
+
+def _exact_likelihood(mu, s, record):
+    """prod_k exp(-(x_k - mu)^2 / (2 s^2) - 0.5 ln(2 pi s^2)) per cell as (Fraction A = sum_k (x_k - mu)^2 / (2 s^2), Fraction L): the
+    polynomial part exactly, ln / exp / pi with the decimal module at 60 digits"""
+    out = []
+    with decimal.localcontext() as ctx:
+        ctx.prec = 60
+        ctx.Emin, ctx.Emax = -999999, 999999
+        pi = decimal.Decimal('3.14159265358979323846264338327950288419716939937510582097494')
+        for m in mu:
+            for sd in s:
+                A, arg = F(0), decimal.Decimal(0)
+                for x in record:
+                    if x == x:
+                        a = (F(float(x)) - F(float(m))) ** 2 / (2 * F(float(sd)) ** 2)
+                        A += a
+                        arg += -_dec(a) - (2 * pi * _dec(F(float(sd)) ** 2)).ln() / 2
+                out.append((A, F(arg.exp())))
+    return out
+
+
+LIK_GRID = (np.array([-8.0, -0.1, 0.3, 2.0 / 3.0, 8.0]), np.array([4.0, 0.7, 0.032, 1.6e-4]))
+LIK_RECORDS = [[0.3], [0.25, float('nan')], [-8.0, 8.0], [0.3, 0.3001, float('nan'), 0.2999], [float('nan')] * 3, [-24.0], [0.66, 0.67, 0.68, 0.69]]
+
+
+@pytest.mark.skipif(not hp.EXTENDED, reason=hp.REQUIRES_EXTENDED)
+@pytest.mark.parametrize('k', range(len(LIK_RECORDS)))
+def test_gaussian_likelihood_against_exact_arithmetic(k):
+    """the polynomial part of the argument against rational arithmetic (a few longdouble roundings), the likelihood against 60-digit exp / ln:
+    inside 1 / 8 of the bound it sets for the per-cell exponential -- and of the recurrence's bound, which is never the smaller one here"""
+    mu, s = LIK_GRID
+    rec = LIK_RECORDS[k]
+    exact = _exact_likelihood(mu, s, rec)
+    terms, _, _ = hp.gaussian_terms(mu, s, rec)
+    A = sum((a for a, _ in terms), np.zeros((len(mu), len(s)), dtype=hp.LD)).reshape(-1)
+    eps = float(np.finfo(hp.LD).eps)
+    for i, (a, (Ax, _)) in enumerate(zip(A, exact)):
+        hi = float(a)
+        got = F(hi) + F(float(a - hp.LD(hi)))
+        assert abs(got - Ax) <= 4 * (len(rec) + 1) * F(eps) * Ax, (i, a, float(Ax))
+    L = hp.gaussian_likelihood(mu, s, rec)
+    if all(x != x for x in rec):
+        assert np.all(L == 1)
+        return
+    _assert_within(L, [l for _, l in exact], hp.likelihood_bound_exp(mu, s, rec), 'likelihood')
+    assert np.all(hp.likelihood_bound_rec(mu, s, rec, 1, 0) >= 0)
+    # GaussianMean (:705-706): the same expression with the datum's own s
+    if len(rec) == 1:
+        for j, sd in enumerate(s):
+            assert np.array_equal(hp.gaussian_mean_likelihood(mu, rec[0], sd), L[:, j])
+    assert np.all(hp.gaussian_mean_likelihood(mu, float('nan'), 1.0) == 1) and np.all(hp.gaussian_mean_likelihood(mu, 1.0, float('nan')) == 1)
+
+
+def test_exp_mn_polynomial_and_reduction_counts():
+    """the constants behind C_EXPMN: the degree-13 Taylor polynomial's truncation on |r| <= ln 2 / 2 and the exactness of kn * ln2_hi"""
+    r = F(math.log(2.0)) / 2
+    trunc = r ** 14 / math.factorial(14) * F(3, 2)                # the remainder of the series, bounded by its first term times 1 / (1 - r / 15) < 3 / 2
+    assert trunc < F(hp.U) / 10
+    ln2_hi, ln2_lo = 6.93147180369123816490e-01, 1.90821492927058770002e-10
+    m, e = math.frexp(ln2_hi)
+    # ln2_hi is a multiple of 2^-33 below 1: kn ln2_hi is one too, and so is the argument wherever |kn| >= 2^21 (its ulp is coarser): their
+    # difference, below 1 / 2, has at most 33 bits -- the first fma is exact there and rounds once (u |r|) elsewhere
+    assert int(m * 2 ** 53) % 2 ** 21 == 0 and e == 0
+    with decimal.localcontext() as ctx:
+        ctx.prec = 60
+        ln2 = F(decimal.Decimal(2).ln())
+    split = abs(F(ln2_hi) + F(ln2_lo) - ln2) * F(2.02e9)           # what the split constant is off by, times the largest |kn|
+    assert split < F(hp.U) * F(4, 10)
+    # Horner's thirteen fmas, each damped by |r| <= 0.35; the two reduction fmas; truncation; the split
+    assert hp.C_EXPMN >= 1 / (1 - 0.35) + 0.35 + 0.35 + 0.1 + 0.4
+
+
+@pytest.mark.skipif(not hp.EXTENDED, reason=hp.REQUIRES_EXTENDED)
+def test_small_forward_backward_against_exact_arithmetic():
+    """hp.gaussian_fit on a 3 x 2 grid, T = 2, a Static model: core.py:372-470 in rational arithmetic from the same float64 likelihoods"""
+    rng = np.random.default_rng(5)
+    shape, T = (3, 2), 2
+    prior = rng.random(shape)
+    liks = [rng.random(shape) * 10.0 ** rng.integers(-3, 3, shape) for _ in range(T)]
+    grids, lattice = [np.array([-1.0, 0.5, 2.0]), np.array([0.1, 0.7])], [1.5, 1.0]
+    out = hp.gaussian_fit(prior, [(L, np.zeros(shape)) for L in liks], [], grids, lattice, nblk=1, full=True)
+    dV = F(1.5)
+    P = _frac(prior)
+    Ls = [_frac(L) for L in liks]
+    alpha, norms, v = [], [], P
+    for t in range(T):
+        a = [x * l for x, l in zip(v, Ls[t])]
+        N = sum(a)
+        v = [x / N for x in a]
+        alpha.append(v)
+        norms.append(N)
+    G = len(P)
+    beta = [F(1, G)] * G
+    for t in range(T - 1, -1, -1):
+        p = [x * y for x, y in zip(alpha[t], beta)]
+        sp = sum(p)
+        p = [x / sp for x in p]
+        _assert_within(out['post'][t][0], p, hp.SLACK * out['post'][t][1], 'post[%d]' % t)
+        local = 1 / (sum(x / l for x, l in zip(p, Ls[t])) * dV)
+        _assert_within([out['local'][t][0]], [local], [hp.SLACK * out['local'][t][1]], 'local[%d]' % t)
+        g0 = [F(float(grids[0][i])) for i in range(3) for _ in range(2)]
+        _assert_within([out['means'][t][0][0]], [sum(x * g for x, g in zip(p, g0))], [hp.SLACK * out['means'][t][1][0]], 'mean[%d]' % t)
+        b = [x * l for x, l in zip(beta, Ls[t])]
+        sb = sum(b)
+        beta = [x / sb for x in b]
+    for t in range(T):
+        _assert_within(out['alpha'][t][0], alpha[t], hp.SLACK * out['alpha'][t][1], 'alpha[%d]' % t)
+        _assert_within([out['local_fwd'][t][0]], [norms[t] * dV], [hp.SLACK * out['local_fwd'][t][1]], 'local_fwd[%d]' % t)
+
+
+ORACLE_WORST = {}
+
+
+def _oracle_families():
+    import test_likelihood_kernels as tl
+    return list(tl.FAMILIES)
+
+
+@pytest.mark.skipif(not hp.EXTENDED, reason=hp.REQUIRES_EXTENDED)
+@pytest.mark.parametrize('fam', _oracle_families())
+def test_float64_oracle_is_inside_the_bounds_of_the_gpu_file(fam):
+    """oracle/bl_oracle.py (NumPy float64, the reference's own order of operations) on EVERY problem of tests/test_likelihood_kernels.py,
+    held to the bound that file holds the kernels to: the bound is not tuned to the code under test.  Prints the worst error / bound."""
+    import likelihood_cases as lc
+    import test_likelihood_kernels as tl
+    from oracle import bl_oracle as bo
+    Fm = tl.FAMILIES[fam]
+    top, bad = 0.0, []
+
+    def within(got, want, bound, what):
+        nonlocal top
+        got = np.asarray(got, dtype=np.float64)
+        want, bound = np.broadcast_to(np.asarray(want), got.shape), np.broadcast_to(np.asarray(bound), got.shape)
+        nan = np.isnan(np.asarray(want, dtype=np.float64))
+        if not np.array_equal(np.isnan(got), nan):
+            bad.append('%s: NaN pattern differs' % what)
+            return
+        if nan.all():
+            return
+        q = hp.worst(got[~nan], want[~nan], hp.SLACK * bound[~nan])
+        top = max(top, q)
+        if not q <= 1.0:
+            bad.append('%s: error / bound %.3g' % (what, q))
+
+    problems = [(c, (k,), False) for c in lc.CASES for k in range(3)] + [(c, tuple(range(T)), True) for c in lc.BACKWARD_CASES for T in (2, 3)]
+    for case, steps, full in problems:
+        T = len(steps)
+        problem, values, refs, liks, rec_ok = tl.setup(fam, case, steps, full, None if T == 1 else 1e150)
+        g = bo.Grid(problem.marginal)
+        ops = [('grw', op[1]) if op[0] == tl._abi.OP_GRW else (('regimeswitch',) if op[0] == tl._abi.OP_REGIMESWITCH else ('static',)) for op in problem.ops]
+        for c, ref in enumerate(refs):
+            with np.errstate(all='ignore'):
+                r = bo.fit(g, 'gaussian', problem.data, problem.timestamps, problem.prior, ops, list(values[c]), forward_only=not full)
+            what = '%s %s chain %d' % (case, steps, c)
+            stop = tl.aborted_at(ref)
+            if stop is not None:
+                if r['abort'] != ('forward', stop):
+                    bad.append('%s: abort %r, expected forward %d' % (what, r['abort'], stop))
+                continue
+            assert r['abort'] is None, what
+            within([r['logEvidence']], [ref['log_evidence'][0]], [ref['log_evidence'][1]], what + ' logE')
+            for t in range(T):
+                want = ref['post'][t] if full else ref['alpha'][t]
+                within(r['posteriorSequence'][t], want[0], want[1], what + ' posterior[%d]' % t)
+                loc = ref['local'][t] if full else ref['local_fwd'][t]
+                within([r['localEvidence'][t]], [loc[0]], [loc[1]], what + ' localEvidence[%d]' % t)
+                within(np.asarray(r['posteriorMeanValues'])[:, t], ref['means'][t][0], ref['means'][t][1], what + ' means[%d]' % t)
+    ORACLE_WORST[fam] = top
+    print('float64 oracle, %s: worst error / bound %.3f over %d problems' % (fam, top, len(problems)))
+    assert not bad, '\n'.join(bad[:20])
+
+
+@pytest.mark.skipif(not hp.EXTENDED, reason=hp.REQUIRES_EXTENDED)
+def test_float64_oracle_is_inside_the_bounds_of_the_gaussian_mean_problems():
+    """the same for the 1-D GaussianMean problems of tests/test_likelihood_kernels.py"""
+    import test_likelihood_kernels as tl
+    from oracle import bl_oracle as bo
+    top, bad = 0.0, []
+    problems = [(c, (k,), False) for c in tl.GM_CASES for k in range(3)] + \
+               [(c, tuple(range(T)), full) for c in tl.GM_BACKWARD for T in (2, 3) for full in (False, True)]
+    for case, steps, full in problems:
+        problem, values, ref, liks = tl.gm_setup(case, steps, full)
+        g = bo.Grid(problem.marginal)
+        with np.errstate(all='ignore'):
+            r = bo.fit(g, 'gaussian_mean', problem.data, problem.timestamps, problem.prior, [('grw', 0)], [values[0, 0]], forward_only=not full)
+        stop = tl.aborted_at(ref)
+        if stop is not None:
+            assert r['abort'] == ('forward', stop), (case, steps, r['abort'])
+            continue
+        for t in range(len(steps)):
+            want = ref['post'][t] if full else ref['alpha'][t]
+            loc = ref['local'][t] if full else ref['local_fwd'][t]
+            for got, w, b, what in ((r['posteriorSequence'][t], want[0][:, 0], want[1][:, 0], 'posterior'), ([r['localEvidence'][t]], [loc[0]], [loc[1]], 'localEvidence'),
+                                    (np.asarray(r['posteriorMeanValues'])[:1, t], ref['means'][t][0][:1], ref['means'][t][1][:1], 'mean')):
+                if np.isnan(np.asarray(w, dtype=np.float64)).all():
+                    assert np.isnan(got).all()
+                    continue
+                q = hp.worst(got, w, hp.SLACK * np.asarray(b))
+                top = max(top, q)
+                if not q <= 1.0:
+                    bad.append('%s %s %s[%d]: error / bound %.3g' % (case, steps, what, t, q))
+    print('float64 oracle, GaussianMean: worst error / bound %.3f over %d problems' % (top, len(problems)))
+    assert not bad, '\n'.join(bad)

@@ -385,6 +385,66 @@ def test_host_unlag_with_restarts_and_out_of_range_sums():
     assert lib.blhip_host_unlag(1, _abi.dptr(bad), T, lag, None, None) == 1
 
 
+# ---- which Gaussian fits take the likelihood recurrence (include/blhip.h: blhip_host_rec_envelope) -- pure host code of libblhip.so ------
+
+def _rec_envelope(mean, std, recs):
+    """(accepted, bound) as the library decides it for a two-parameter Gaussian problem with these grids and records (T, d)"""
+    import ctypes
+    from bayesloop_amd import _abi
+    grids = [np.ascontiguousarray(mean, dtype=np.float64), np.ascontiguousarray(std, dtype=np.float64)]
+    recs = np.ascontiguousarray(recs, dtype=np.float64)
+    cp = _abi.Problem()                                   # (what the decision reads of a problem: grids and data; no device, no context)
+    cp.ndim, cp.obs_model, cp.T, cp.seg_len, cp.data_dim = 2, _abi.OM_GAUSSIAN, len(recs), 1, recs.shape[1]
+    for k in range(2):
+        cp.n[k] = len(grids[k])
+        cp.marginal[k] = _abi.dptr(grids[k])
+    cp.data = _abi.dptr(recs)
+    out = ctypes.c_double()
+    rc = _abi.load().blhip_host_rec_envelope(ctypes.byref(cp), ctypes.byref(out))
+    return rc, out.value
+
+
+def test_recurrence_envelope_of_the_issue_cases():
+    """x = -100 against a std column of 1e-3 on linspace(-8, 8, 128) (anchor exponent -2.02e9: two int additions from wrapping) and
+    s = 2e-4 with a datum at the grid's edge (the clamp of exp_mn bites) are refused; the benchmark-like grids are accepted"""
+    mean = np.linspace(-8, 8, 128)
+    wide = np.linspace(0, 4, 18)[1:-1]
+    assert _rec_envelope(mean, wide, [[0.3], [-1.2]])[0] == 1
+    assert _rec_envelope(mean, np.append(wide, 1e-3), [[-100.0]])[0] == 0
+    assert _rec_envelope(mean, np.append(wide, 2e-4), [[8.0]])[0] == 0
+    assert _rec_envelope(mean, wide, [[float('nan')], [0.5]])[0] == 1            # NaN values count for nothing
+    assert _rec_envelope(mean, wide, [[float('nan')]])[0] == 1
+    assert _rec_envelope(mean, np.append(wide, 0.0), [[0.5]])[0] == 0             # a zero std: no envelope
+    # the bound covers what the kernels can form: anchor argument + 32 first differences + 512 second differences over 4 rows, on the
+    # lattice continued 256 rows beyond either end -- each below exp_mn's clamp, their exponents' sum inside int
+    rc, bound = _rec_envelope(mean, [0.05], [[8.0, -8.0]])
+    step, cA = 16.0 / 127, 1.0 / (2 * 0.05 ** 2)
+    far = 8.0 + 256 * step + 8.0
+    assert bound >= 2 * far ** 2 * cA + 32 * (2 * cA * 4 * step * 2 * far) + 512 * (2 * cA * 2 * (4 * step) ** 2) and rc == 1
+    assert bound * 1.4426950408889634 < 2.0 ** 31 - 1 and bound <= 1.4e9
+
+
+def test_recurrence_envelope_matches_its_restatement():
+    """tests/likelihood_cases.py restates the decision for the census expectations of tests/test_likelihood_kernels.py: the same bound to
+    rounding and the same verdict on every grid and record of that file"""
+    import likelihood_cases as lc
+    n_ref = 0
+    for n0, n1 in ((140, 90), (128, 64), (32, 32), (48, 40), (128, 16), (100, 20), (100, 90), (24, 20)):
+        for case in lc.CASES:
+            mean, std, recs = lc.mean_grid(n0), lc.std_of(case, n1, n0), lc.records(case, n0)
+            for rows in ([0], [1], [2], [0, 1], [0, 1, 2]):
+                rc, bound = _rec_envelope(mean, std, recs[rows])
+                want = lc.envelope_bound(mean, std, recs[rows])
+                assert abs(bound - want) <= 1e-12 * want, (n0, n1, case, rows, bound, want)
+                assert rc == (1 if lc.recurrence_accepted(mean, std, recs[rows]) else 0)
+                n_ref += rc == 0
+    assert n_ref > 100                                                            # (both verdicts occur)
+    # the case just inside the envelope is admitted with its three records and sits within 2 % of the edge
+    for n0, n1 in ((140, 90), (32, 32), (128, 16)):
+        rc, bound = _rec_envelope(lc.mean_grid(n0), lc.std_of('envelope_edge', n1, n0), lc.records('envelope_edge', n0))
+        assert rc == 1 and 0.97e9 < bound <= 1e9, (n0, n1, bound)
+
+
 # ---- observation models with three parameters: the Python surface (grid, program, accessors) through the test double -------------------
 
 def test_three_parameter_models_host_logic():
