@@ -1047,6 +1047,52 @@ int blhip_host_rec_envelope(const blhip_problem *p, double *bound_out) {
     return b <= REC_ENVELOPE ? 1 : 0;
 }
 
+int64_t blhip_host_taps(int kind, int64_t n, const double *params, int n_params, double *out, int64_t cap, int *radius_out) {
+    static const int need[4] = {1, 1, 2, 3};
+    if (kind < 0 || kind > 3 || !params || n_params != need[kind]) return -1;
+    for (int k = 0; k < n_params; ++k)
+        if (!std::isfinite(params[k])) return -1;
+    try {
+        TapTable taps;
+        int id = -1;
+        if (kind == 0) {
+            if (!(params[0] > 0.0) || params[0] > 1e6) return -1;
+            id = taps.get(0, params[0]);
+        } else if (kind == 1) {
+            if (std::fabs(params[0]) > 12.0) return -1;
+            id = taps.get_shift(0, params[0]);
+        } else if (kind == 2) {
+            // (the builder is O(n^2) cosines in long double: no longer than a grid axis the kernels take; transitionModels.py:202: 0 < alpha <= 2)
+            if (n < 2 || n > 16384 || !(params[0] > 0.0) || !(params[1] > 0.0) || params[1] > 2.0) return -1;
+            id = taps.get_alphastable(0, params[0], params[1], (int)n);
+        } else {
+            if (!(params[0] > 0.0) || !(params[1] > 0.0) || !(std::fabs(params[2]) < 1.0) || params[0] > 1e3 || params[1] > 1e3) return -1;
+            id = taps.get2d(params[0], params[1], params[2]);
+        }
+        if (id < 0) {                                  // a walk of radius 0: the identity, one weight
+            if (radius_out) radius_out[0] = radius_out[1] = 0;
+            if (out && cap >= 1) out[0] = 1.0;
+            return 1;
+        }
+        const int r = taps.lw[id], r1 = kind == 3 ? taps.lw2[id] : 0;
+        if (radius_out) { radius_out[0] = r; radius_out[1] = r1; }
+        const double *w = taps.w.data() + taps.off[id];
+        std::vector<double> full;
+        if (kind == 0) {                               // stored as the half kernel w[0 .. r]
+            full.resize(2 * (size_t)r + 1);
+            for (int k = -r; k <= r; ++k) full[(size_t)(k + r)] = w[std::abs(k)];
+        } else {
+            const size_t count = kind == 1 ? 2 * (size_t)r + 1 : kind == 2 ? (size_t)n : (2 * (size_t)r + 1) * (2 * (size_t)r1 + 1);
+            full.assign(w, w + count);
+        }
+        if (out)
+            for (size_t k = 0; k < full.size() && (int64_t)k < cap; ++k) out[k] = full[k];
+        return (int64_t)full.size();
+    } catch (...) {
+        return -1;
+    }
+}
+
 int blhip_set_option(blhip_ctx *ctx, const char *key, double value) {
     if (!ctx || !key) return -1;
     // "resident_ok": the context's memory of a resident launch that gave up (its blocks were not all co-resident) -- settable so that

@@ -310,6 +310,16 @@ int blhip_host_unlag(int scheme, double *sums, int64_t T, int lag, const unsigne
  * marginal[0..1], n, data, T, seg_len, data_dim of the problem. */
 int blhip_host_rec_envelope(const blhip_problem *problem, double *bound_out);
 
+/* The weights the host builds for a transition model's kernel, as the step kernels read them (unit tests hold them to the reference's
+ * formulas without a GPU).  kind: 0 GaussianRandomWalk, params = {sigma in cells}: the 2 r + 1 weights of SciPy's gaussian_filter1d,
+ * r = int(4 sigma + 0.5) (transitionModels.py:107-115); 1 Deterministic shift of |d| <= 12 cells, params = {d}: the 2 r + 1 stencil
+ * weights K[m], m = -r .. r, r = ceil|d| + 34 (out[i] = sum_m K[m] ext[i + m]); 2 AlphaStableRandomWalk, params = {c in cells, alpha}: k[0 .. n-1]
+ * (:196-240); 3 BivariateRandomWalk, params = {sigma1, sigma2 in cells, rho}: the (2 r0 + 1) x (2 r1 + 1) kernel, row-major (:898-911).
+ * n: the axis length (kind 2 only; 2 .. 16384, c > 0, 0 < alpha <= 2).  out (may be NULL): `cap` doubles; radius_out (may be NULL): {r, r1} (r1 = 0 for 1-D sets).
+ * Returns the number of weights (nothing is written beyond `cap`: call with out = NULL to size the buffer), or -1 for arguments
+ * no builder takes. */
+int64_t blhip_host_taps(int kind, int64_t n, const double *params, int n_params, double *out, int64_t cap, int *radius_out);
+
 /* ---- multi-GPU exchange of a sharded hyper-study (HyperStudy.fit(nJobs > 1), core.py:1307-1340, 1443-1495) -------------
  * One process per GPU, one context per process; each rank fits its share of the hyper-grid points with blhip_fit and
  * no communication, then the ranks exchange results through RCCL (xGMI inside a node), which this library binds

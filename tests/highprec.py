@@ -19,6 +19,10 @@ the renormalisation, RegimeSwitch, NotEqual, the random walk) for tests/test_tra
 The third part restates the GAUSSIAN LIKELIHOOD (observationModels.py:566-567, :49-54, :705-706), counts the rounded operations of the two
 ways the kernels evaluate it (one exp per value and cell; the multiplicative recurrence along the rows, anchored with blmath::exp_mn) and
 runs a small forward-backward pass with a running bound for tests/test_likelihood_kernels.py.
+
+The fourth part restates the host's TAP TABLES (SciPy's Gaussian weights, the alpha-stable and the bivariate kernel, the cardinal-spline weights
+of a small shift) with the bound of a float64 builder, the zero-boundary, dense and small-shift stages with the stencil's truncation term, and
+generalises the small pass to a per-step stage program (transition_fit) for tests/test_step_transitions.py.
 """
 import math
 
@@ -750,5 +754,370 @@ def gaussian_fit(prior, liks, walks, grids, lattice, nblk=1, full=True, clamp=No
             b, ebl = transition(b, ebl)
             beta, eb, Bt = normalise_stage(b, ebl, nblk)[:3]
             Bs.append(Bt)
+        out['post'], out['local'], out['means'] = post, local, means
+    return out
+
+
+# ---- the host's tap tables and the transition half of the fused step kernels -----------------------------------------------------------------
+#
+# Written from the reference: scipy/ndimage/_filters.py (_gaussian_kernel1d: lw = int(4 sd + 0.5), exp(-0.5 / sd^2 x^2) / sum) behind
+# transitionModels.py:107-115; :196-240 (AlphaStableRandomWalk.createKernel: numpy.fft.irfft of exp(-|c w|^alpha) on int(3 n / 2 + 1) points of
+# [0, pi]) with :242-260 (the 3x zero-padded fftconvolve, 'same': out[i] = sum_j in[j] k[|i - j|] inside the grid); :898-911
+# (BivariateRandomWalk.createKernel; the density's constant cancels in :910) with :892-893 (scipy.signal.convolve2d, 'same', zero fill, and the
+# division by the sum); :559-606 (Deterministic: scipy.ndimage.shift, order 3, 'nearest') -- not from the kernels or the host's builders.
+# The bounds count the float64 operations of a builder that evaluates these formulas as written (one rounding per operation; pow() within
+# 2 ulp = 4 u as above, exp() and cos() within 1 ulp = 2 u).  Every function returns (weights in longdouble, bound of a float64 builder).
+
+C_POW = 4
+C_COS = 2
+C_POLE = 7        # sqrt(3) - 2 formed in float64: the root within u (1.74 u absolutely), the subtraction exact: 6.5 u of 0.268
+C_ETA_GAIN = 11   # g formed in float64 as -6 z / (1 - z^2): z (7), the square (1), 1 - z^2 (the 15 u of z^2 = 0.072 and its own u, over 0.928: 3), -6 z (1), the quotient (1):
+#                   the pole's error enters numerator and denominator with the same sign and mostly cancels; counted as if it did not
+SHIFT_STENCIL_MAX = 12      # |d| up to which the fused step kernels take the one-pass stencil
+SHIFT_STENCIL_REACH = 34    # ... of radius ceil|d| + 34
+
+
+def gaussian_walk_taps(ns):
+    """SciPy's gaussian_filter1d weights for sigma = ns cells -> (r, w (2 r + 1), bound).  Float64 count per weight: the argument
+    0.5 / (ns ns) k^2 = a: the square, the quotient, the product (3 u a); exp (2 u): phi_k (1 + (3 a_k + 2) u); the sum of 2 r + 1 positive terms
+    ((2 r + 1) u, and the terms' own errors as their weighted mean); the quotient (1 u)."""
+    ns = float(ns)
+    r = int(4.0 * ns + 0.5)
+    x = _ld(np.arange(-r, r + 1))
+    with np.errstate(under='ignore'):
+        a = LD(0.5) / (LD(ns) * LD(ns)) * x * x
+        phi = np.exp(-a)
+        w = phi / phi.sum()
+        rel = 3 * a + C_EXP
+        e = w * LD(U) * (rel + (w * rel).sum() + (2 * r + 1) + 1)
+    return r, w, e
+
+
+def alphastable_taps(c, alpha, n):
+    """createKernel (transitionModels.py:196-240) for an axis of n points, c in cells -> (k[0 .. n-1], bound): the inverse real DFT as the
+    exact cosine sum  k[j] = (X_0 + (-1)^j X_(m-1) + 2 sum_(q = 1)^(m-2) X_q cos(2 pi j q / K)) / K,  X_q = exp(-|c pi q / (m - 1)|^alpha),
+    m = int(3 n / 2 + 1), K = 2 (m - 1) (numpy.fft.irfft's definition; j q is reduced modulo K in integers).  Float64 count: the argument
+    c pi q / (m - 1) (pi, two products, a quotient: 4 u), pow (alpha times that and its own 4 u), exp (the argument's absolute error and 2 u):
+    X_q (1 + ((4 alpha + 4) p_q + 2) u); a term 2 X_q cos: the cosine (2 u), the product (1 u); the m - 1 additions against
+    sum |X| / K = (X_0 + X_(m-1) + 2 sum X_q) / K; the last quotient (1 u)."""
+    c, alpha, n = float(c), float(alpha), int(n)
+    m = int(3 * n / 2 + 1)
+    K = 2 * (m - 1)
+    q = np.arange(m)
+    u = LD(U)
+    with np.errstate(under='ignore'):
+        p = np.abs(LD(c) * PI_LD * _ld(q) / LD(m - 1)) ** LD(alpha)
+        X = np.exp(-p)
+        eX = X * ((4 * alpha + C_POW) * p + C_EXP) * u
+        jq = (np.arange(n, dtype=np.int64)[:, None] * q[None, 1:m - 1].astype(np.int64)) % K
+        cosm = np.cos(LD(2) * PI_LD * _ld(jq) / LD(K))
+        sign = np.where(np.arange(n) % 2 == 1, LD(-1), LD(1))
+        k = (X[0] + sign * X[m - 1] + LD(2) * (cosm * X[None, 1:m - 1]).sum(axis=1)) / LD(K)
+        S = X[0] + X[m - 1] + LD(2) * X[1:m - 1].sum()
+        e = (eX[0] + eX[m - 1] + LD(2) * (np.abs(cosm) * eX[None, 1:m - 1]).sum(axis=1) + (C_COS + 1 + (m - 1)) * u * S) / LD(K) + u * np.abs(k)
+    return k, e
+
+
+def bivariate_taps(ns1, ns2, rho):
+    """createKernel (transitionModels.py:898-911), sigmas in cells -> (kernel (2 r0 + 1, 2 r1 + 1), bound), r = 3 ceil(ns): exp(-q) / sum,
+    q = (x^2 / ns1^2 - 2 rho x y / (ns1 ns2) + y^2 / ns2^2) / (2 (1 - rho^2)).  Float64 count: each of the three terms at most 4 u (a square or the
+    products with rho, x and y; the product of the sigmas; the quotient), their two additions 2 u of the sum of their magnitudes A D; the
+    denominator D = 2 (1 - rho^2): rho^2 (1 u) and the subtraction, relative to 1 - rho^2: (1 + rho^2) / (1 - rho^2) u; the quotient 1 u.
+    So |dq| <= (7 + (1 + rho^2) / (1 - rho^2)) u A with A = (|T1| + |T2| + |T3|) / D >= |q|; exp 2 u; the sum of all taps; the quotient."""
+    ns1, ns2, rho = float(ns1), float(ns2), float(rho)
+    r0, r1 = 3 * int(math.ceil(ns1)), 3 * int(math.ceil(ns2))
+    x = _ld(np.arange(-r0, r0 + 1))[:, None]
+    y = _ld(np.arange(-r1, r1 + 1))[None, :]
+    s1, s2, rh = LD(ns1), LD(ns2), LD(rho)
+    with np.errstate(under='ignore'):
+        T1, T2, T3 = x * x / (s1 * s1), LD(2) * rh * x * y / (s1 * s2), y * y / (s2 * s2)
+        D = LD(2) * (LD(1) - rh * rh)
+        qv = (T1 - T2 + T3) / D
+        A = (np.abs(T1) + np.abs(T2) + np.abs(T3)) / D
+        v = np.exp(-qv)
+        w = v / v.sum()
+        rel = (7 + (1 + rh * rh) / (1 - rh * rh)) * A + C_EXP
+        e = w * LD(U) * (rel + (w * rel).sum() + w.size + 1)
+    return w, e
+
+
+def _beta3(a):
+    a = np.abs(a)
+    return np.where(a < 1, LD(2) / LD(3) - a * a + a * a * a / LD(2), np.where(a < 2, (LD(2) - a) ** 3 / LD(6), LD(0)))
+
+
+def _beta3_slope(a):
+    """|d beta3 / du| at |u| = a"""
+    a = np.abs(a)
+    return np.where(a < 1, np.abs(LD(1.5) * a * a - LD(2) * a), np.where(a < 2, (LD(2) - a) ** 2 / LD(2), LD(0)))
+
+
+def cardinal_spline(uu, with_bound=False):
+    """eta(u) = sum_n g z^|n| beta3(u - n), g = (1 - z) / (1 + z), z = SciPy's pole: the cubic CARDINAL spline -- the response of SciPy's
+    prefilter (ni_splines.c: the gain (1 - z)(1 - 1 / z), then y[i] = x[i] + z y[i-1] and c[i] = z (c[i+1] - y[i]): together the two-sided sequence
+    g z^|n|; g = sqrt(3) = -6 z / (1 - z^2) for the exact pole sqrt(3) - 2, to 1e-17 for SciPy's literal) sampled by the B-spline (:581:
+    scipy.ndimage.shift, order 3).  Four terms are not zero: n = floor(u) - 1 .. + 2.
+    with_bound: also (bound of a float64 evaluation WITHOUT the rounding of u, sum_n g |z|^|n| |beta3'(u - n)|): per term the gain (C_ETA_GAIN),
+    z^|n| from pow() on a pole that is itself off by C_POLE u (C_POLE |n| + 4), two products, and the weight's W_OPS u absolutely; three
+    additions against the sum of the magnitudes."""
+    uu = _ld(uu)
+    z = LD(SPLINE_POLE)
+    g = (LD(1) - z) / (LD(1) + z)         # SciPy's gain (1 - z)(1 - 1 / z) times the response -z / (1 - z^2) of its two recursions
+    n0 = np.floor(uu)
+    val, err, slope = (np.zeros(uu.shape, dtype=LD) for _ in range(3))
+    with np.errstate(under='ignore'):
+        for k in (-1, 0, 1, 2):
+            n = n0 + k
+            zn = g * z ** np.abs(n)
+            b = _beta3(uu - n)
+            val = val + zn * b
+            err = err + np.abs(zn) * ((C_ETA_GAIN + C_POLE * np.abs(n) + C_POW + 2 + 3) * b + W_OPS) * LD(U)
+            slope = slope + np.abs(zn) * _beta3_slope(uu - n)
+    return (val, err, slope) if with_bound else val
+
+
+def shift_stencil_radius(d):
+    return int(math.ceil(abs(float(d)))) + SHIFT_STENCIL_REACH
+
+
+def small_shift_taps(d, r=None):
+    """The shift by d cells as ONE stencil over the extension SciPy works on: out[i] = sum_m K[m] ext[i + m], K[m] = eta(-d - m), for every
+    integer m (untruncated: exact for |d| <= 12, where no sample reads beyond the coefficients SciPy has) -> (K[-r .. r], bound, slope); r: default
+    the radius ceil|d| + 34 the fused step kernels cut it at.  The bound is cardinal_spline's plus the rounding of the float64 argument -d - m
+    through the slope (the exact difference, not an estimate)."""
+    d = float(d)
+    r = shift_stencil_radius(d) if r is None else int(r)
+    m = np.arange(-r, r + 1)
+    u64 = -np.float64(d) - m.astype(np.float64)
+    exact = -LD(d) - _ld(m)
+    K, e, slope = cardinal_spline(exact, with_bound=True)
+    e = e + np.abs(_ld(u64) - exact) * slope
+    return K, e, slope
+
+
+def shift_tail(d, r=None, more=400):
+    """tail(d) = sum over |m| > r of |eta(-d - m)|: what a stencil cut at radius r (default ceil|d| + 34) leaves out, per unit of the line's
+    maximum.  Summed over the next `more` = 400 cells on either side; what lies beyond is below |z|^400 = 1e-229 of it."""
+    d = float(d)
+    r = shift_stencil_radius(d) if r is None else int(r)
+    m = np.concatenate([np.arange(-r - more, -r), np.arange(r + 1, r + more + 1)])
+    with np.errstate(under='ignore'):
+        return np.abs(cardinal_spline(-LD(d) - _ld(m))).sum()
+
+
+def spline_extension_index(n, idx):
+    """the sample behind position idx (any integer) of the line SciPy's shift works on (_interpolation.py: _prepad_for_spline_filter, mode
+    'nearest': 12 edge samples per side; ni_splines.c: the prefilter's half-sample symmetric boundary, period 2 (n + 24))"""
+    N = n + 2 * SPLINE_PAD
+    j = np.mod(np.asarray(idx) + SPLINE_PAD, 2 * N)
+    j = np.where(j >= N, 2 * N - 1 - j, j)
+    return np.clip(j - SPLINE_PAD, 0, n - 1)
+
+
+def small_shift_stage(v, e, d, axis):
+    """The shift alone for |d| <= 12 as the fused step kernels take it (no renormalisation): the VALUE is spline_shift (SciPy's algorithm); the
+    bound is that of the one-pass stencil of radius lw = ceil|d| + 34:
+        incoming bound through |K|;  2 lw + 1 fused multiply-adds over sum_m |K_m| |ext|;  the weights' bound (small_shift_taps) over |ext|;
+        the rounding of the reference's OWN float64 coordinate fl(fl(i - d) + 12) (_sample_points) against i - d + 12, exactly, through the slope;
+        the truncation tail(d) max |line|, absolute in the line's maximum: the stencil is a finite one by design;  one TINY per tap;
+    and per cell at least the recursion's own bound (below)."""
+    d = float(d)
+    assert abs(d) <= SHIFT_STENCIL_MAX
+    v = _ld(v)
+    e = np.zeros(v.shape, dtype=LD) if e is None else _ld(np.broadcast_to(e, v.shape))
+    out = spline_shift(v, d, axis)
+    lw = shift_stencil_radius(d)
+    K, eK, slope = small_shift_taps(d, lw)
+    vm, em = np.abs(np.moveaxis(v, axis, 0)), np.moveaxis(e, axis, 0)
+    n = vm.shape[0]
+    i = np.arange(n)
+    pp = (i.astype(np.float64) - np.float64(d)) + np.float64(SPLINE_PAD)
+    dpp = np.abs(_ld(pp) - (_ld(i) - LD(d) + LD(SPLINE_PAD)))
+    dpp = dpp.reshape((-1,) + (1,) * (vm.ndim - 1))
+    mag, eo, sl = (np.zeros(vm.shape, dtype=LD) for _ in range(3))
+    with np.errstate(under='ignore'):
+        for j, m in enumerate(range(-lw, lw + 1)):
+            idx = spline_extension_index(n, i + m)
+            mag = mag + np.abs(K[j]) * vm[idx]
+            eo = eo + np.abs(K[j]) * em[idx] + eK[j] * vm[idx]
+            sl = sl + slope[j] * vm[idx]
+        eo = eo + (2 * lw + 1) * LD(U) * mag + dpp * sl + shift_tail(d, lw) * vm.max(axis=0, keepdims=True) + (2 * lw + 1) * LD(TINY)
+    # The reference evaluates the same function by the recursion, whose own counted bound (_shift_err) exceeds the stencil's where an integer
+    # shift leaves nothing but the weights' rounding far from any mass.  A cell is held to the larger of the two counts, so that the float64
+    # reference itself stays inside (tests/test_highprec.py runs it on every problem).  Where the second count wins: at d = +-12 (the only
+    # integer shifts of the tables) on the single-cell and edge inputs, in cells k >= 20 cells from the nearest mass, where the reference's
+    # value is about |z|^k of that mass (1e-12 .. 1e-38 of the line's maximum) and the recursion's count about 20 u |z|^k of it against the
+    # stencil's 40 u |z|^(k + 34); at a fractional shift the truncation term, 1e-21 of the line's maximum, is the larger one in every such
+    # cell, and within reach of any mass the stencil's 2 lw + 1 operations are.  It never widens the bound of a cell that holds mass.
+    return out, np.maximum(np.moveaxis(eo, 0, axis), _shift_err(v, d, axis, e))
+
+
+def zero_boundary_stage(v, e, weights, axis, ew=None):
+    """AlphaStableRandomWalk's convolution (transitionModels.py:242-260) without its renormalisation: out[i] = sum_j v[j] k[|i - j|] inside the
+    grid, nothing outside; weights: k[0 .. n-1] (float64 or longdouble), ew: their bound.  Bound as walk_stage's: n taps."""
+    v = _ld(v)
+    e = np.zeros(v.shape, dtype=LD) if e is None else _ld(np.broadcast_to(e, v.shape))
+    k = _ld(weights).reshape(-1)
+    ek = np.zeros(k.shape, dtype=LD) if ew is None else _ld(ew).reshape(-1)
+    vm, em = np.moveaxis(v, axis, 0), np.moveaxis(e, axis, 0)
+    n = vm.shape[0]
+    assert len(k) >= n
+    out, mag, eo = (np.zeros(vm.shape, dtype=LD) for _ in range(3))
+    i = np.arange(n)
+    with np.errstate(under='ignore'):
+        for j in range(n):
+            kj, ekj = _expand(k[np.abs(i - j)], vm.ndim), _expand(ek[np.abs(i - j)], vm.ndim)
+            out = out + kj * vm[j]
+            mag = mag + np.abs(kj) * np.abs(vm[j])
+            eo = eo + np.abs(kj) * em[j] + ekj * np.abs(vm[j])
+        eo = eo + (n + 2) * LD(U) * mag + n * LD(TINY)
+    return np.moveaxis(out, 0, axis), np.moveaxis(eo, 0, axis)
+
+
+def dense_stage(v, e, kernel, ew=None):
+    """scipy.signal.convolve2d(v, kernel, mode = 'same') with zero fill (transitionModels.py:892) without the renormalisation:
+    out[i, j] = sum_(a, b) kernel[a, b] v[i - (a - r0), j - (b - r1)].  (The reference's kernels are point symmetric: the correlation is the same.)"""
+    v = _ld(v)
+    e = np.zeros(v.shape, dtype=LD) if e is None else _ld(np.broadcast_to(e, v.shape))
+    k = _ld(kernel)
+    ek = np.zeros(k.shape, dtype=LD) if ew is None else _ld(ew)
+    r0, r1 = k.shape[0] // 2, k.shape[1] // 2
+    assert k.shape == (2 * r0 + 1, 2 * r1 + 1)
+    n0, n1 = v.shape
+    pv, pe = (np.zeros((n0 + 2 * r0, n1 + 2 * r1), dtype=LD) for _ in range(2))
+    pv[r0:r0 + n0, r1:r1 + n1], pe[r0:r0 + n0, r1:r1 + n1] = v, e
+    out, mag, eo = (np.zeros(v.shape, dtype=LD) for _ in range(3))
+    with np.errstate(under='ignore'):
+        for a in range(k.shape[0]):
+            for b in range(k.shape[1]):
+                sv = pv[2 * r0 - a:2 * r0 - a + n0, 2 * r1 - b:2 * r1 - b + n1]
+                out = out + k[a, b] * sv
+                mag = mag + np.abs(k[a, b]) * np.abs(sv)
+                eo = eo + np.abs(k[a, b]) * pe[2 * r0 - a:2 * r0 - a + n0, 2 * r1 - b:2 * r1 - b + n1] + ek[a, b] * np.abs(sv)
+        eo = eo + (k.size + 2) * LD(U) * mag + k.size * LD(TINY)
+    return out, eo
+
+
+def apply_stage(st, v, e, nblk=1, sums=None):
+    """one stage of a transition -> (v, e).  ('walk', axis, w, ew) reflecting correlation (:107-115); ('zero', axis, k, ek) and
+    ('dense', K, eK) with the division by the sum (:183-185, :892-893); ('shift', axis, d) Deterministic with the division by the sum
+    (:600-603): |d| <= 12 the one-pass stencil, beyond it SciPy's recursion over the whole line (shift_stage: the 1-D kernels), 0 the identity; ('rs', limit); ('ne', limit).
+    sums: a list that receives (D, bound of D) of every renormalising sum of a shift, a zero-boundary or a dense stage."""
+    kind = st[0]
+    if kind == 'walk':
+        o, eo = walk_stage(v, e, np.asarray(st[2], dtype=np.float64), st[1])
+        if len(st) > 3 and st[3] is not None:       # the weights' own bound, through the same reflecting sum of |v| (rounded UP to float64)
+            ew = np.nextafter(np.asarray(st[3], dtype=np.float64), np.inf)
+            eo = eo + walk_stage(np.abs(_ld(v)), None, ew, st[1])[0]
+        return o, eo
+    if kind == 'rs':
+        return regime_switch_stage(v, e, st[1], nblk)
+    if kind == 'ne':
+        return not_equal_stage(v, e, st[1], nblk)
+    if kind == 'zero':
+        o, eo = zero_boundary_stage(v, e, st[2], st[1], st[3] if len(st) > 3 else None)
+    elif kind == 'dense':
+        o, eo = dense_stage(v, e, st[1], st[2] if len(st) > 2 else None)
+    elif kind == 'shift':
+        if float(st[2]) == 0.0:
+            return _ld(v), (np.zeros(np.shape(v), dtype=LD) if e is None else e)
+        o, eo = (small_shift_stage if abs(float(st[2])) <= SHIFT_STENCIL_MAX else shift_stage)(v, e, st[2], st[1])
+    else:
+        raise ValueError(kind)
+    r, er, D, eD = normalise_stage(o, eo, nblk)
+    if sums is not None:
+        sums.append((D, eD))
+    return r, er
+
+
+def transition_fit(prior, liks, steps, grids, lattice, nblk=1, full=True, shared=None):
+    """core.py:372-470 in longdouble with a running bound, over a per-step stage program (gaussian_fit with one walk list for every step is the
+    special case).  prior float64 on the grid (one or two parameters); liks: per step (L, bound of L); steps: per step t a dict
+        fwd: (source, stages) of the transition INTO step t from t - 1 (unused for t = 0), bwd: the same INTO step t from t + 1 (unused for T - 1)
+    source: 'prev' (the neighbour's state), 'reset' / 'indep' (shared[source], float64, as given: transitionModels.py:300-312, :351-360);
+    stages: apply_stage's, in list order (:645-649).  -> the dict of gaussian_fit: (value, bound) pairs, bounds WITHOUT SLACK; and 'sums': (D, bound of D) of every renormalising
+    sum of a shift, zero-boundary or dense stage, in the order of the pass."""
+    _need_extended()
+    T = len(liks)
+    dV = LD(float(np.prod(np.asarray(lattice, dtype=np.float64))))
+    u = LD(U)
+    nd = len(grids)
+    g = [_ld(_grid_values(grids, k, np.shape(prior))) for k in range(nd)]
+    G = int(np.size(prior))
+    shared = shared or {}
+    liks = [(L, np.zeros(np.shape(L), dtype=LD) if eL is None else eL) for L, eL in liks]
+    out = dict(alpha=[], norm=[], local_fwd=[], post=[], local=[], means=[], sums=[])
+
+    def transition(prog, v, e):
+        source, stages = prog
+        if source != 'prev':
+            v, e = _ld(shared[source]), None
+        for st in stages:
+            v, e = apply_stage(st, v, e, nblk, out['sums'])
+        return v, e
+
+    def means_of(p, ep):
+        m, em = [], []
+        with np.errstate(under='ignore'):
+            for k in range(nd):
+                m.append((p * g[k]).sum())
+                em.append((ep * np.abs(g[k])).sum() + (G + 3) * u * (np.abs(p) * np.abs(g[k])).sum())
+        return np.array(m, dtype=LD), np.array(em, dtype=LD)
+
+    def lazy(norms):
+        worst_p, prod = LD(1), LD(1)
+        for N in norms[:LAZY_LAG]:
+            prod = prod * N
+            worst_p = min(worst_p, prod)
+        return LD(1) / worst_p
+
+    v, e = _ld(prior), None
+    logE, elogE = LD(0), LD(0)
+    Ns = []
+    with np.errstate(under='ignore', over='ignore', invalid='ignore', divide='ignore'):
+        for t in range(T):
+            if t > 0:
+                v, e = transition(steps[t]['fwd'], v, e)
+            a, ea = product_stage(v, e, liks[t][0], liks[t][1])
+            ea = ea + LD(TINY) * lazy(Ns[::-1][:LAZY_LAG - 1])
+            r, er, N, eN = normalise_stage(a, ea, nblk)
+            Ns.append(N)
+            out['alpha'].append((r, er))
+            out['norm'].append((N, eN))
+            out['local_fwd'].append((N * dV, eN * dV + 2 * u * N * dV))
+            logE = logE + np.log(N)
+            elogE = elogE + eN / N + 2 * u * (abs(np.log(N)) + abs(logE))
+            v, e = r, er
+        logE = logE + np.log(dV)
+        out['log_evidence'] = (logE, elogE + 2 * u * abs(logE))
+        if not full:
+            out['means'] = [means_of(r, er) for r, er in out['alpha']]
+            return out
+        beta, eb = np.full(np.shape(prior), LD(1) / LD(G), dtype=LD), np.full(np.shape(prior), u / LD(G), dtype=LD)
+        post, local, means = [None] * T, [None] * T, [None] * T
+        Bs = []
+        for t in range(T - 1, -1, -1):
+            L, eL = _ld(liks[t][0]), _ld(liks[t][1])
+            p, ep = product_stage(out['alpha'][t][0], out['alpha'][t][1], beta, eb)
+            ep = ep + LD(TINY) * lazy(Ns[:t + 1][::-1]) * lazy(Bs[::-1])
+            p, ep = normalise_stage(p, ep, nblk)[:2]
+            post[t] = (p, ep)
+            means[t] = means_of(p, ep)
+            if np.any(L.astype(np.float64) == 0.0):
+                local[t] = (LD(np.nan), LD(0))
+            else:
+                q = p / L
+                relL = np.where(L > eL, eL / (L - eL), LD(np.inf))
+                eq = ep / L + q * relL + 2 * u * q + LD(TINY)
+                S = q.sum()
+                eS = eq.sum() + (G + nblk) * u * S
+                val = LD(1) / (S * dV)
+                local[t] = (val, val * (eS / (S - eS) + 3 * u) + LD(TINY) if S > eS else LD(np.inf))
+            if t > 0:
+                b, ebl = product_stage(beta, eb, L, eL)
+                ebl = ebl + LD(TINY) * lazy(Bs[::-1][:LAZY_LAG - 1])
+                b, ebl = transition(steps[t - 1]['bwd'], b, ebl)
+                beta, eb, Bt = normalise_stage(b, ebl, nblk)[:3]
+                Bs.append(Bt)
         out['post'], out['local'], out['means'] = post, local, means
     return out

@@ -569,3 +569,236 @@ def test_float64_oracle_is_inside_the_bounds_of_the_gaussian_mean_problems():
                     bad.append('%s %s %s[%d]: error / bound %.3g' % (case, steps, what, t, q))
     print('float64 oracle, GaussianMean: worst error / bound %.3f over %d problems' % (top, len(problems)))
     assert not bad, '\n'.join(bad)
+
+
+# ---- the host's tap tables and the transition stages of the fused step kernels (tests/test_step_transitions.py) --------------------------------
+
+def _D(x):
+    return decimal.Decimal(x.numerator) / decimal.Decimal(x.denominator)
+
+
+def _dctx():
+    ctx = decimal.getcontext().copy()
+    ctx.prec = 80
+    ctx.Emin, ctx.Emax = -999999, 999999
+    return decimal.localcontext(ctx)
+
+
+def _exp80(x):
+    with _dctx():
+        return F(_D(x).exp())
+
+
+def _pi80():
+    with _dctx():                                          # Machin: pi = 16 atan(1 / 5) - 4 atan(1 / 239)
+        def atan_inv(q):
+            t = s = decimal.Decimal(1) / q
+            k = 1
+            while abs(t) > decimal.Decimal(10) ** -85:
+                t = -t / (q * q)
+                k += 2
+                s += t / k
+            return s
+        return 16 * atan_inv(decimal.Decimal(5)) - 4 * atan_inv(decimal.Decimal(239))
+
+
+def _cos80(x):
+    with _dctx():
+        t = s = decimal.Decimal(1)
+        k = 0
+        while abs(t) > decimal.Decimal(10) ** -85:
+            k += 2
+            t = -t * x * x / ((k - 1) * k)
+            s += t
+        return s
+
+
+def test_walk_and_bivariate_taps_against_exact_arithmetic():
+    ns = 0.75
+    r, w, e = hp.gaussian_walk_taps(ns)
+    assert r == 3 and len(w) == 7
+    phi = [_exp80(-F(1, 2) / (F(ns) * F(ns)) * k * k) for k in range(-r, r + 1)]
+    _assert_within(w, [p / sum(phi) for p in phi], hp.SLACK * e, 'walk taps')
+    assert hp.gaussian_walk_taps(0.1)[0] == 0 and hp.gaussian_walk_taps((40 - 0.25) / 4.0)[0] == 40
+    s1, s2, rho = 0.8, 0.6, 0.5
+    k, ek = hp.bivariate_taps(s1, s2, rho)
+    assert k.shape == (7, 7)
+    q = [(F(x * x) / (F(s1) * F(s1)) - 2 * F(rho) * x * y / (F(s1) * F(s2)) + F(y * y) / (F(s2) * F(s2))) / (2 * (1 - F(rho) * F(rho)))
+         for x in range(-3, 4) for y in range(-3, 4)]
+    v = [_exp80(-a) for a in q]
+    _assert_within(k, [a / sum(v) for a in v], hp.SLACK * ek, 'bivariate taps')
+    assert hp.bivariate_taps(1.3, 0.7, 0.0)[0].shape == (13, 7)
+
+
+def test_alphastable_taps_against_the_exact_cosine_sum():
+    c, alpha, n = 1.3, 1.5, 4
+    k, e = hp.alphastable_taps(c, alpha, n)
+    m, K = 7, 12
+    with _dctx():
+        pi = _pi80()
+        X = [(-((_D(F(c)) * pi * q / (m - 1)) ** _D(F(alpha)))).exp() if q else decimal.Decimal(1) for q in range(m)]
+        want = []
+        for j in range(n):
+            acc = X[0] + (-1) ** j * X[m - 1]
+            for q in range(1, m - 1):
+                acc += 2 * X[q] * _cos80(2 * pi * ((j * q) % K) / K)
+            want.append(F(acc / K))
+    _assert_within(k, want, hp.SLACK * e, 'alpha-stable taps')
+
+
+def _exact_eta(u):
+    z = F(hp.SPLINE_POLE)
+    g = (1 - z) * (1 - 1 / z) * (-z) / (1 - z * z)          # SciPy's gain, and the response of its causal and anti-causal recursion
+    n0 = math.floor(u)
+    out = F(0)
+    for n in range(n0 - 1, n0 + 3):
+        a = abs(u - n)
+        b = F(2, 3) - a * a + a * a * a / 2 if a < 1 else ((2 - a) ** 3 / 6 if a < 2 else F(0))
+        out += g * z ** abs(n) * b
+    return out
+
+
+@needs_extended
+@pytest.mark.parametrize('d', [0.5, -3.25, 11.999, 12.0])
+def test_small_shift_taps_and_the_truncation_term_against_exact_arithmetic(d):
+    """the cardinal-spline weights in rational arithmetic; the untruncated stencil over SciPy's extension IS SciPy's recursion (to |z|^(2 N - 2)); the
+    stencil cut at ceil|d| + 34 differs from it by no more than tail(d) max |line|, and not by much less on a single-cell line"""
+    K, e, _ = hp.small_shift_taps(d)
+    r = hp.shift_stencil_radius(d)
+    assert len(K) == 2 * r + 1 and r == math.ceil(abs(d)) + 34
+    exact_K = [_exact_eta(-F(d) - m) for m in range(-r, r + 1)]
+    _assert_within(K, exact_K, hp.SLACK * np.maximum(np.asarray(e, dtype=np.float64), 1e-300), 'shift taps')
+    n = 9
+    line = np.zeros(n)
+    line[2] = 1.0
+    want = _exact_shift(line, d)                                                  # (the float64 coordinate fl(fl(i - d) + 12), as SciPy forms it)
+    ext = lambda i: F(float(line[int(hp.spline_extension_index(n, i))]))          # noqa: E731
+    R = 150
+    full = [sum(_exact_eta(-F(d) - m) * ext(i + m) for m in range(-R, R + 1)) for i in range(n)]
+    cut = [sum(exact_K[m + r] * ext(i + m) for m in range(-r, r + 1)) for i in range(n)]
+    pp_err = max(abs(F((float(i) - d) + 12.0) - (i - F(d) + 12)) for i in range(n))
+    for i in range(n):
+        # (SciPy's causal initialisation reads the running sum as c[0] in its last term: |z|^(2 N - 1) of the line away from the exact reflection)
+        assert abs(full[i] - want[i]) <= abs(F(hp.SPLINE_POLE)) ** (2 * (n + 24) - 2) + 2 * pp_err, (i, float(full[i] - want[i]))
+    tail = F(float(hp.shift_tail(d)))
+    worst = max(abs(cut[i] - full[i]) for i in range(n))
+    assert worst <= tail * F(1.0000001), (float(worst), float(tail))
+    if abs(d) < 4:
+        assert worst >= tail / 64, (float(worst), float(tail))                   # (the term is not a loose one: a single cell shows most of it)
+    if not float(d).is_integer():
+        assert 1e-23 < float(tail) < 1e-20                                        # |z|^35 = 9.7e-21: a quarter to all of it, by the fraction
+    out, eo = hp.small_shift_stage(line, None, d, 0)
+    _assert_within(out, want, hp.SLACK * eo, 'small shift stage')
+    assert all(abs(F(float(c)) - w) <= F(float(hp.SLACK * b)) for c, w, b in zip([float(x) for x in cut], want, eo))
+
+
+@needs_extended
+def test_zero_boundary_and_dense_stages_against_exact_arithmetic():
+    rng = np.random.default_rng(78)
+    v = rng.random((4, 5)) ** 3
+    vf = np.array(_frac(v), dtype=object).reshape(v.shape)
+    for axis in (0, 1):
+        n = v.shape[axis]
+        k = rng.random(n)
+        want = np.zeros(v.shape, dtype=object)
+        for i in range(n):
+            for j in range(n):
+                idx_o, idx_i = [slice(None)] * 2, [slice(None)] * 2
+                idx_o[axis], idx_i[axis] = i, j
+                want[tuple(idx_o)] = want[tuple(idx_o)] + F(float(k[abs(i - j)])) * vf[tuple(idx_i)]
+        got, eg = hp.zero_boundary_stage(v, None, k, axis)
+        _assert_within(got, list(want.reshape(-1)), hp.SLACK * eg, 'zero boundary')
+        _, eg2 = hp.zero_boundary_stage(v, None, k, axis, ew=np.full(n, 1e-18))
+        assert np.all(eg2 >= eg) and np.any(eg2 > eg)
+    kern = rng.random((3, 5))                                   # NOT point symmetric: a true convolution (scipy.signal.convolve2d)
+    want = np.zeros(v.shape, dtype=object)
+    for i in range(4):
+        for j in range(5):
+            for a in range(3):
+                for b in range(5):
+                    ii, jj = i - (a - 1), j - (b - 2)
+                    if 0 <= ii < 4 and 0 <= jj < 5:
+                        want[i, j] = want[i, j] + F(float(kern[a, b])) * vf[ii, jj]
+    got, eg = hp.dense_stage(v, None, kern)
+    _assert_within(got, list(want.reshape(-1)), hp.SLACK * eg, 'dense')
+    from scipy.signal import convolve2d
+    assert hp.worst(convolve2d(v, kern, mode='same'), got, hp.SLACK * eg) <= 1.0
+
+
+@needs_extended
+def test_transition_fit_is_gaussian_fit_for_one_walk_list():
+    """the generalised pass restates the same lines of core.py: with one walk list for every step it returns gaussian_fit's values and bounds"""
+    rng = np.random.default_rng(79)
+    shape = (6, 5)
+    prior = rng.random(shape)
+    prior /= prior.sum()
+    liks = [(rng.random(shape) + 0.1, np.full(shape, 1e-18)) for _ in range(3)]
+    w = np.array([0.25, 0.5, 0.25])
+    grids = [np.arange(6.0), np.arange(5.0)]
+    a = hp.gaussian_fit(prior, liks, [(0, w), (1, w)], grids, [1.0, 1.0], nblk=2, clamp=-3.0)
+    prog = ('prev', [('walk', 0, w), ('walk', 1, w), ('rs', float(10.0 ** -3.0))])
+    b = hp.transition_fit(prior, liks, [dict(fwd=prog, bwd=prog)] * 3, grids, [1.0, 1.0], nblk=2)
+    for key in ('alpha', 'post', 'norm', 'local', 'local_fwd', 'means'):
+        for (va, ea), (vb, eb) in zip(a[key], b[key]):
+            assert np.array_equal(np.asarray(va), np.asarray(vb)) and np.array_equal(np.asarray(ea), np.asarray(eb)), key
+    assert a['log_evidence'] == b['log_evidence']
+
+
+STEP_ORACLE_WORST = {}
+
+
+def _step_names():
+    import step_transition_cases as sc
+    return sorted(sc.CASES)
+
+
+@needs_extended
+@pytest.mark.parametrize('name', _step_names())
+def test_float64_oracle_is_inside_the_bounds_of_the_step_transition_problems(name):
+    """oracle/bl_oracle.py (NumPy float64 with its own float64 tap tables, SciPy's recursion for the shifts) on EVERY problem of
+    tests/test_step_transitions.py -- through the same driver, comparison and bounds, with the oracle test double in the engine's place.
+    Inputs the reference itself cannot meet fail here, not on the card.  Prints the worst error / bound."""
+    import step_transition_cases as sc
+    from oracle_engine import OracleEngine
+    eng = OracleEngine()
+    case = sc.CASES[name]
+    chk = sc.Check(name)
+    for kind in case['inputs']:
+        for driver in case['drivers']:
+            refs, ok = sc.reference(name, kind, driver)
+            keep = [b for b, o in enumerate(ok) if o]
+            with np.errstate(all='ignore'):
+                got = sc.run_problem(eng, name, kind, driver, keep, one_at_a_time=True)
+            sc.compare(chk, name, kind, driver, keep, got, refs)
+    fam = case['family']
+    STEP_ORACLE_WORST[fam] = max(STEP_ORACLE_WORST.get(fam, 0.0), chk.top)
+    print('float64 oracle, %s (%s): worst error / bound %.4f' % (name, fam, chk.top))
+    assert not chk.bad, '\n'.join(chk.bad[:20])
+
+
+@needs_extended
+def test_what_the_step_transition_table_leaves_out():
+    """the exact list of what transition_cases.well_conditioned (from the restatement alone) leaves out -- its class is an integer shift that moves
+    the one occupied cell of a single-cell input off the grid -- and, named, not computed, NotEqual of the uniform alpha_0 of the backward driver, 0 / 0 in the reference"""
+    import step_transition_cases as sc
+    left = []
+    for name, kind, driver in sc.combinations():
+        if not any(m[0] in ('shift', 'as', 'biv') for m in sc.CASES[name]['models']):
+            continue                                        # (no renormalising sum in the pass)
+        _, ok = sc.reference(name, kind, driver)
+        left += [(name, kind, driver, sc.CASES[name]['chains'][b]) for b, o in enumerate(ok) if not o]
+    # nothing else is left out silently: every case runs all four inputs, and a case that does not run all three drivers is one of these
+    assert all(c['inputs'] == sc.INPUTS for c in sc.CASES.values())
+    three_only = sorted(n for n, c in sc.CASES.items() if c['drivers'] == ('three',))
+    assert three_only == ['chain1d_mixed_clamps_300', 'chain1d_mixed_shifts_300', 'chain1d_sources_300', 'chain_sources_128x16',
+                          'chainax_sources_32x32', 'fast_band8_sources_140x90', 'fused1d_sources_300', 'generic_change_point_24x20',
+                          'generic_composed_row_300', 'generic_independent_24x20', 'hwide_sources_40x300', 'mfma_band8_sources_140x90',
+                          'persist1d_sources_300', 'persist1d_walks_300', 'vwide_sources_140x64'], three_only     # per-step programs; T > 2 for bl1p::
+    assert all(c['drivers'] in (sc.DRIVERS, ('three',), ('forward', 'three')) for c in sc.CASES.values())
+    assert left == [], left                                 # (today: nothing; the single cells of the table's rows lie beyond 12 cells from the ends)
+    assert sc.NOT_EQUAL_OF_UNIFORM == ['chain1d_not_equal_300', 'chain1d_not_equal_600', 'generic_not_equal_20x140', 'generic_not_equal_24x20']
+    for name in sc.NOT_EQUAL_OF_UNIFORM:
+        assert 'backward' not in sc.CASES[name]['drivers'] and set(sc.CASES[name]['drivers']) == {'forward', 'three'}
+    x = np.full((4, 5), 1.0 / 20)
+    with np.errstate(all='ignore'):
+        assert np.isnan(np.asarray(hp.not_equal_stage(x, None, 1e-4)[0], dtype=np.float64)).all()

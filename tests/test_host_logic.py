@@ -618,3 +618,80 @@ def test_host_transition_hyper_study_closes_the_accumulator_when_a_fit_raises():
         S.fit(silent=True)
     assert ended == [1]
     assert getattr(eng, '_accum_owner', None) is None
+
+
+# ---- the host's tap builders (include/blhip.h: blhip_host_taps) against the longdouble restatements of tests/highprec.py, over the parameters
+#      tests/test_step_transitions.py uses: the GPU file takes the RESTATED weights, so the library's own are pinned here -------------------------------
+
+def _host_taps(kind, params, n=0):
+    import ctypes
+    from bayesloop_amd import _abi
+    lib = _abi.load()
+    p = np.ascontiguousarray(params, dtype=np.float64)
+    rad = (ctypes.c_int * 2)()
+    count = lib.blhip_host_taps(kind, n, _abi.dptr(p), len(p), None, 0, rad)
+    if count < 0:
+        return None, None
+    out = np.full(count + 1, -7.0)
+    assert lib.blhip_host_taps(kind, n, _abi.dptr(p), len(p), _abi.dptr(out), count, rad) == count
+    assert out[count] == -7.0                                          # nothing written beyond `cap`
+    return out[:count], (rad[0], rad[1])
+
+
+def _step_parameters():
+    """(walk sigmas, shifts, (c, alpha, n), (sigma1, sigma2, rho)) of every chain of tests/step_transition_cases.py"""
+    import step_transition_cases as sc
+    walks, shifts, stable, dense = set(), set(), set(), set()
+    for c in sc.CASES.values():
+        for params in c['chains']:
+            for m, p in zip(c['models'], params):
+                if m[0] == 'walk' and p:
+                    walks.add(sc.sigma_of(p))
+                elif m[0] == 'shift':
+                    shifts.update(abs(d) * s for d in (p if isinstance(p, tuple) else (p,)) for s in (1, -1) if 0 < abs(d) <= 12)
+                elif m[0] == 'as':
+                    stable.add((p[0], p[1], c['shape'][m[1]]))
+                elif m[0] == 'biv':
+                    dense.add(p)
+    return sorted(walks), sorted(shifts), sorted(stable), sorted(dense)
+
+
+def test_host_tap_builders_against_the_restatements():
+    import highprec as hp
+    walks, shifts, stable, dense = _step_parameters()
+    assert len(walks) >= 20 and len(shifts) >= 8 and len(stable) == 9 and len(dense) == 3
+    worst = {}
+
+    def hold(what, got, want, bound):
+        q = hp.worst(got, want, hp.SLACK * bound)
+        worst[what] = max(worst.get(what, 0.0), q)
+        assert q <= 1.0, (what, q, hp.worst_at(got, want, hp.SLACK * bound))
+
+    for s in walks:
+        r, w, e = hp.gaussian_walk_taps(s)
+        got, rad = _host_taps(0, [s])
+        assert rad == (r, 0) and len(got) == 2 * r + 1, (s, rad)
+        hold('walk', got, w, e)
+    for d in shifts:
+        K, e, _ = hp.small_shift_taps(d)
+        got, rad = _host_taps(1, [d])
+        assert rad == (hp.shift_stencil_radius(d), 0) and len(got) == len(K), (d, rad)
+        hold('shift', got, K, e)
+    for c, alpha, n in stable:
+        k, e = hp.alphastable_taps(c, alpha, n)
+        got, rad = _host_taps(2, [c, alpha], n)
+        assert rad == (n - 1, 0) and len(got) == n
+        hold('alphastable', got, k, e)
+    for s1, s2, rho in dense:
+        k, e = hp.bivariate_taps(s1, s2, rho)
+        got, rad = _host_taps(3, [s1, s2, rho])
+        assert rad == (k.shape[0] // 2, k.shape[1] // 2) and len(got) == k.size
+        hold('bivariate', got.reshape(k.shape), k, e)
+    print('host tap builders, worst error / bound: ' + ', '.join('%s %.3f' % kv for kv in sorted(worst.items())))
+
+
+def test_host_taps_rejects_what_no_builder_takes():
+    assert _host_taps(0, [0.05])[0].tolist() == [1.0]                  # radius 0: the identity
+    for kind, params, n in ((4, [1.0], 0), (-1, [1.0], 0), (0, [1.0, 2.0], 0), (0, [float('nan')], 0), (0, [-1.0], 0), (1, [12.5], 0),
+                            (2, [1.0, 1.5], 1), (2, [1.0, 1.5], 16385), (2, [1.0, 0.0], 24), (2, [1.0, 2.5], 24), (2, [-1.0, 1.5], 24), (3, [1.0, 1.0, 1.0], 0), (3, [0.0, 1.0, 0.5], 0)):
+        assert _host_taps(kind, params, n)[0] is None, (kind, params, n)
