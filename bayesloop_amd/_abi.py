@@ -118,6 +118,7 @@ PROTOTYPES = {
     'blhip_host_unlag': (C.c_int, [C.c_int, c_double_p, C.c_int64, C.c_int, C.POINTER(C.c_ubyte), c_double_p]),
     'blhip_carry_release': (C.c_int, [C.c_void_p, C.c_int]),
     'blhip_host_rec_envelope': (C.c_int, [C.POINTER(Problem), c_double_p]),
+    'blhip_host_poisson_direct': (C.c_int, [C.POINTER(Problem), C.POINTER(C.c_int)]),
     'blhip_host_taps': (C.c_int64, [C.c_int, C.c_int64, c_double_p, C.c_int, c_double_p, C.c_int64, C.POINTER(C.c_int)]),
 }
 

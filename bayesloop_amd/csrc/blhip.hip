@@ -1047,6 +1047,20 @@ int blhip_host_rec_envelope(const blhip_problem *p, double *bound_out) {
     return b <= REC_ENVELOPE ? 1 : 0;
 }
 
+int blhip_host_poisson_direct(const blhip_problem *p, int *direct_out) {
+    if (!p || p->ndim != 1 || p->obs_model != BLHIP_OM_POISSON || !p->marginal[0] || !p->data || p->n[0] < 1 || p->T < 1 || p->seg_len != 1 ||
+        p->data_dim < 1)
+        return -1;
+    const double max_rate = max_of(p->marginal[0], p->n[0]);
+    int n_direct = 0;
+    for (int64_t t = 0; t < p->T; ++t) {
+        const bool direct = poisson_direct_domain(p->data + t * p->data_dim, p->data_dim, max_rate);
+        if (direct_out) direct_out[t] = direct ? 1 : 0;
+        n_direct += direct ? 1 : 0;
+    }
+    return n_direct;
+}
+
 int64_t blhip_host_taps(int kind, int64_t n, const double *params, int n_params, double *out, int64_t cap, int *radius_out) {
     static const int need[4] = {1, 1, 2, 3};
     if (kind < 0 || kind > 3 || !params || n_params != need[kind]) return -1;

@@ -298,11 +298,19 @@ __device__ __forceinline__ double likelihood(const StepParams &P, int i, int j, 
         const double q = x - g1;
         return exp(-(q * q) * P.rec[1] - P.rec[2]);
     } else if constexpr (OM == OM_POISSON) {
-        // lambda^k exp(-lambda) / k!   observationModels.py:502; cA = exp(-lambda); rec = [k, k!] per dimension
+        // lambda^k exp(-lambda) / k!   observationModels.py:502; cA = exp(-lambda); rec = [k, k!] per dimension.  A record outside the
+        // direct domain (poisson_direct_domain, blhip_program.hpp: k! or lambda^k beyond the float64 range, exp(-lambda) below the normal
+        // one) carries rec = [k, -ln k!] instead -- the sign bit set, -0.0 for k <= 1 -- and is evaluated in log space.  The choice is
+        // the record's, so the branch is uniform across a launch.
         double L = 1.0;
         for (int k = 0; k < P.d; ++k) {
             const double cnt = P.rec[2 * k];
-            if (cnt == cnt) L *= pow(g1, cnt) * cA / P.rec[2 * k + 1];
+            if (cnt == cnt) {
+                const double f = P.rec[2 * k + 1];
+                if (!signbit(f)) L *= pow(g1, cnt) * cA / f;
+                else if (g1 == 0.0) L *= cnt == 0.0 ? 1.0 : 0.0;         // (0 log 0 is NaN; the limit is 0^0 = 1)
+                else L *= exp(cnt * log(g1) - g1 + f);
+            }
         }
         return L;
     } else {

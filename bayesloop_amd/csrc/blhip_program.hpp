@@ -243,6 +243,29 @@ void validate(const blhip_problem *p, int64_t n_chains, const double *op_values)
     if (p->data_dim < 1) fail("data_dim must be >= 1");
 }
 
+// ---- the direct domain of the Poisson likelihood ------------------------------------------------------------------------------------------
+// blk::likelihood<OM_POISSON> forms lambda^k exp(-lambda) / k! factor by factor (observationModels.py:502).  That is sound only while each
+// factor is an ordinary float64: k! is inf from k = 171 on, lambda^k overflows beyond ln(DBL_MAX) = 709.78, exp(-lambda) leaves the normal
+// range beyond lambda = 708.39.  A record is in the direct domain when every count is at most POISSON_MAX_COUNT, max count * ln(max rate)
+// stays below POISSON_MAX_LOG_POW (9 below the overflow threshold: pow()'s and log()'s own rounding are many orders smaller) and the
+// largest rate is at most POISSON_MAX_RATE (exp(-708) = 3.3e-308, normal).  Every other record is evaluated in log space:
+// exp(k ln(lambda) - lambda - ln k!), with ln k! from lgammal_r in long double, rounded to float64 once.  counts: the dd values of one record, NaN values count for nothing.
+constexpr double POISSON_MAX_COUNT = 170.0, POISSON_MAX_LOG_POW = 700.0, POISSON_MAX_RATE = 708.0;
+
+inline bool poisson_direct_domain(const double *counts, int dd, double max_rate) {
+    double kmax = 0.0;
+    for (int k = 0; k < dd; ++k)
+        if (!std::isnan(counts[k])) kmax = std::max(kmax, counts[k]);
+    if (kmax > POISSON_MAX_COUNT || !(max_rate <= POISSON_MAX_RATE)) return false;
+    return kmax == 0.0 || max_rate <= 1.0 || kmax * std::log(max_rate) <= POISSON_MAX_LOG_POW;
+}
+
+inline double max_of(const double *v, int64_t n) {
+    double m = -std::numeric_limits<double>::infinity();
+    for (int64_t j = 0; j < n; ++j) m = std::max(m, v[j]);
+    return m;
+}
+
 // per-step records consumed by blk::likelihood<>
 void build_records(const blhip_problem *p, std::vector<double> &rec, int &rec_len, int &d) {
     const int64_t T = p->T;
@@ -263,17 +286,24 @@ void build_records(const blhip_problem *p, std::vector<double> &rec, int &rec_le
     } else if (p->obs_model == BLHIP_OM_POISSON) {
         d = dd; rec_len = 2 * dd;
         rec.resize(T * 2 * dd);
-        for (int64_t t = 0; t < T; ++t)
+        const double max_rate = max_of(p->marginal[0], p->n[0]);
+        for (int64_t t = 0; t < T; ++t) {
             for (int k = 0; k < dd; ++k) {
                 const double c = p->data[t * dd + k];
-                double f = 1.0;
+                if (!std::isnan(c) && (c < 0 || c != std::floor(c))) fail("Poisson data must be non-negative integers (step %lld)", (long long)t);
+            }
+            const bool direct = poisson_direct_domain(p->data + t * dd, dd, max_rate);
+            for (int k = 0; k < dd; ++k) {
+                const double c = p->data[t * dd + k];
+                double f = direct ? 1.0 : 0.0;
                 if (!std::isnan(c)) {
-                    if (c < 0 || c != std::floor(c)) fail("Poisson data must be non-negative integers (step %lld)", (long long)t);
-                    for (double q = 2.0; q <= c; q += 1.0) f *= q;
+                    if (direct) for (double q = 2.0; q <= c; q += 1.0) f *= q;
+                    else { int sign; f = (double)lgammal_r((long double)c + 1.0L, &sign); }      // (long double, rounded once; no global signgam)
                 }
                 rec[(t * dd + k) * 2] = c;
-                rec[(t * dd + k) * 2 + 1] = f;
+                rec[(t * dd + k) * 2 + 1] = direct ? f : -f;      // (the sign bit selects the log-space route: -0.0 for k <= 1 and for NaN)
             }
+        }
     } else {
         d = 1; rec_len = 1;
         rec.assign(T, 0.0);

@@ -310,6 +310,15 @@ int blhip_host_unlag(int scheme, double *sums, int64_t T, int lag, const unsigne
  * marginal[0..1], n, data, T, seg_len, data_dim of the problem. */
 int blhip_host_rec_envelope(const blhip_problem *problem, double *bound_out);
 
+/* Which records of a Poisson problem the step kernels evaluate DIRECTLY, lambda^k exp(-lambda) / k! factor by factor
+ * (observationModels.py:502), and which in log space, exp(k ln(lambda) - lambda - ln k!) with ln k! from lgammal_r (long double, rounded once).  A record is in the direct
+ * domain when every count is at most 170 (171! is inf), max count * ln(max rate) <= 700 (lambda^k overflows at 709.78) and the largest
+ * rate of the grid is at most 708 (exp(-lambda) is a normal number); NaN counts are ignored.  Inside it the arithmetic is the one the
+ * library has always used; outside it the factors would be inf, 0 or subnormal where the likelihood is an ordinary number.  direct_out
+ * (may be NULL): (T) 1 / 0 per record.  Returns the number of direct records, or -1: not such a problem.  Reads marginal[0], n, data, T,
+ * seg_len, data_dim of the problem. */
+int blhip_host_poisson_direct(const blhip_problem *problem, int *direct_out);
+
 /* The weights the host builds for a transition model's kernel, as the step kernels read them (unit tests hold them to the reference's
  * formulas without a GPU).  kind: 0 GaussianRandomWalk, params = {sigma in cells}: the 2 r + 1 weights of SciPy's gaussian_filter1d,
  * r = int(4 sigma + 0.5) (transitionModels.py:107-115); 1 Deterministic shift of |d| <= 12 cells, params = {d}: the 2 r + 1 stencil

@@ -1121,3 +1121,231 @@ def transition_fit(prior, liks, steps, grids, lattice, nblk=1, full=True, shared
                 Bs.append(Bt)
         out['post'], out['local'], out['means'] = post, local, means
     return out
+
+
+# ---- the Poisson likelihood and the table models (tests/test_observation_kernels.py) ------------------------------------------------------------
+#
+# Written from the reference: observationModels.py:502 (Poisson), :419-439 (Bernoulli), :635 (Laplace), :767 (WhiteNoise), :830-831 (AR1),
+# :893-896 (ScaledAR1), :49-54 (the product over the data dimensions; a dimension whose segment holds a NaN contributes 1).  The bounds are counted
+# along blk::likelihood<OM_POISSON> and blk::lik_table_kernel (blhip_kernels.hpp), build_records (blhip_program.hpp) and the host column
+# cA = exp(-lambda) (blhip_batch.hpp).  Every likelihood function returns L; every bound function returns (e, z): the relative part
+# L (exp(rel) - 1) and the absolute part from results below the normal range, as likelihood_bound_exp(split = True) does -- WITHOUT SLACK.
+#
+# Poisson, per non-NaN count k of a record, DIRECT route  pow(lambda, k) * cA / k!  (times the running product):
+#     pow                      within 2 ulp = C_POW = 4 u
+#     cA = exp(-lambda)        the argument is exact; within 1 ulp = C_EXP = 2 u
+#     k!                       k - 1 rounded products on the host, exact while k! < 2^53 (k <= 18): (k - 1) u beyond
+#     pow * cA, / k!, L *=     3 u                                                          -> (C_POW + C_EXP + 3 + [k - 1]) u
+#   every one of the four results (pow, pow * cA, / k!: sub = 3 in poisson_bound; L *= f: the one _combine adds) may lie below the normal
+#   range; all factors are <= 1 there (k! >= 1, cA <= 1, a probability <= 1): 4 TINY.
+# LOG-SPACE route  exp(k * log(lambda) - lambda + f),  f = -ln k! from the host:
+#     log                      within 1 ulp = C_LOG = 2 u of |ln lambda|; the product with k: 1 u     -> (C_LOG + 1) u k |ln lambda|
+#     - lambda                 1 u |k ln lambda - lambda|
+#     + f                      1 u |argument|
+#     f                        build_records calls lgammal_r on (long double)k + 1 and rounds the result to float64 once: C_LNFACT = 2 u ln k!
+#                              (glibc's table of known errors states 4 ulp OF THE LONG DOUBLE for lgammal on x86-64, 2^-8 u; the rounding
+#                              to float64 is 1 u).  The count is for the x86-64 host, the only one a gfx950 build has; it does not depend on
+#                              the width of NumPy's longdouble in the test process.
+#     exp, L *=                C_EXP + 1
+#   so the argument is off by u ((C_LOG + 1) k |ln lambda| + |k ln lambda - lambda| + |arg| + C_LNFACT ln k!): it grows like
+#   u (k |ln lambda| + lambda + ln k!), which is what limits the route (the largest count inside the 1e-9 bar).
+#
+# blk::lik_table_kernel, per data dimension (x0[, x1]) and cell (g0[, g1]); every factor is followed by L *= f (1 u, one TINY):
+#   Bernoulli   p = g0 or 0, f = p or 1 - p:                                      1 u
+#   Laplace     exp(-|x0 - g0| / g1) / (2 g1): the difference and the quotient 2 u a, a = |x0 - g0| / g1; exp C_EXP; 2 g1 exact; the quotient 1 u.
+#               A subnormal exp() is off by TINY absolutely, and the division by 2 g1 carries that along: TINY / (2 g1), plus the quotient's own.
+#   WhiteNoise  exp(-(x0 x0) / (2 g0 g0) - 0.5 log(2 pi g0 g0)): A = x0^2 / (2 g0^2): the square, the product 2 g0 * g0, the quotient: 3 u A;
+#               B = 0.5 log(2 pi g0 g0): M_PI (1 u), two products: 3 u in the argument = 3 u absolutely in the log, halved; log C_LOG u |2 B|, halved:
+#               1.5 u + C_LOG u |B|; the subtraction u (A + |B|)                        -> (4 A + (C_LOG + 1) |B| + 1.5) u, then exp C_EXP
+#   AR1         r = x1 - g0 x0: the product u |g0 x0|, the difference u |r|: |dr| <= u (|g0 x0| + |r|), carried through the square EXACTLY
+#               ((|r| + dr)^2 - r^2: where r cancels to 0 the first order vanishes and the second does not); r r, 2 g1 g1, the quotient: 3 u A; B as above with g1
+#   ScaledAR1   sc = g1 sqrt(1 - g0 g0): g0 g0 1 u of rho^2, the difference 1 u of 1 - rho^2: relative to 1 - rho^2 that is
+#               (1 + K) u, K = rho^2 / (1 - rho^2) -- the cancellation as |rho| -> 1; sqrt halves it and adds u; the product with g1 1 u:
+#               rel(sc) = (0.5 (1 + K) + 2) u.  A = r^2 / (2 sc sc): r as AR1's, then (2 rel(sc) + 3 u) A; B: (3 u + 2 rel(sc)) / 2 + C_LOG u |B|.
+
+C_LOG = 2
+C_LNFACT = 2
+LN2_LD = np.log(LD(2))
+_LNFACT = {}
+
+
+def ln_factorial_exact(k):
+    """ln k! in longdouble, exactly from math.factorial: the top 64 bits of the integer (truncated: 2^-63 relative) and its binary exponent"""
+    f = math.factorial(int(k))
+    sh = max(f.bit_length() - 64, 0)
+    return np.log(LD(f >> sh)) + LD(sh) * LN2_LD
+
+
+STIRLING_FROM = 2000
+
+
+def ln_factorial(k):
+    """ln k! in longdouble: ln_factorial_exact up to k = 2000; beyond, Stirling's series k ln k - k + ln(2 pi k) / 2 + 1 / (12 k) - 1 / (360 k^3)
+    + 1 / (1260 k^5), whose next term is below 1 / (1680 k^7) = 5e-27 there (tests/test_highprec.py pins it against the exact one at larger k)"""
+    k = int(k)
+    if k not in _LNFACT:
+        if k <= STIRLING_FROM:
+            _LNFACT[k] = ln_factorial_exact(k)
+        else:
+            n = LD(k)
+            _LNFACT[k] = n * np.log(n) - n + LD(0.5) * np.log(LD(2) * PI_LD * n) + LD(1) / (12 * n) - LD(1) / (360 * n ** 3) + LD(1) / (1260 * n ** 5)
+    return _LNFACT[k]
+
+
+def _counts_of(record):
+    return [int(x) for x in np.asarray(record, dtype=np.float64).reshape(-1) if x == x]
+
+
+def _poisson_args(rate, k):
+    """(k ln lambda, argument k ln lambda - lambda - ln k!) in longdouble, for rates > 0"""
+    lam = _ld(rate)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        kl = LD(k) * np.log(np.where(lam > 0, lam, LD(1)))
+    return kl, kl - lam - ln_factorial(k)
+
+
+def poisson_likelihood(rate, record):
+    """prod over the non-NaN counts k of exp(k ln(lambda) - lambda - ln k!) on the rate grid; lambda = 0: 1 at k = 0, 0 at k > 0; all NaN: 1."""
+    lam = _ld(rate).reshape(-1)
+    L = np.ones(lam.shape, dtype=LD)
+    with np.errstate(under='ignore'):
+        for k in _counts_of(record):
+            f = np.exp(_poisson_args(lam, k)[1])
+            L = L * np.where(lam > 0, f, LD(1) if k == 0 else LD(0))
+    return L
+
+
+def _combine(factors):
+    """[(f, rel, sub)] -> (L = prod f, e, z): rel the factor's relative error in units of 1 (u's already in), sub its absolute error in TINYs
+    for results below the normal range; every product L *= f adds one u and one TINY"""
+    shape = np.shape(factors[0][0]) if factors else ()
+    L, rel = np.ones(shape, dtype=LD), np.zeros(shape, dtype=LD)
+    z = np.zeros(shape, dtype=LD)
+    with np.errstate(under='ignore', over='ignore', invalid='ignore'):
+        for f, r, _ in factors:
+            L = L * f
+            rel = rel + r + LD(U)
+        for k, (_, _, sub) in enumerate(factors):
+            others = np.ones(shape, dtype=LD)
+            for j, (f, _, _) in enumerate(factors):
+                if j != k:
+                    others = others * f
+            z = z + LD(TINY) * (sub * others + 1)
+        e = np.where(L == 0, LD(0), L * np.expm1(np.minimum(rel, LD(11000))))
+    return L, e, z
+
+
+def poisson_bound(rate, record, direct):
+    """(e, z) of blk::likelihood<OM_POISSON> for the record on the rate grid; direct: the route the host chose (observation_cases.direct_domain)"""
+    lam = _ld(rate).reshape(-1)
+    u = LD(U)
+    factors = []
+    with np.errstate(under='ignore', over='ignore', invalid='ignore'):
+        for k in _counts_of(record):
+            kl, arg = _poisson_args(lam, k)
+            f = np.where(lam > 0, np.exp(arg), LD(1) if k == 0 else LD(0))
+            if direct:
+                fact_ops = (k - 1) if k > 18 else 0                  # (18! < 2^53 < 19!)
+                factors.append((f, (C_POW + C_EXP + 2 + fact_ops) * u * np.ones(lam.shape, dtype=LD), LD(3)))
+            else:
+                lnf = ln_factorial(k)
+                earg = u * ((C_LOG + 1) * np.abs(kl) + np.abs(kl - lam) + np.abs(arg) + C_LNFACT * lnf)
+                factors.append((f, np.where(lam > 0, earg + C_EXP * u, LD(0)), LD(1)))
+    if not factors:
+        return np.zeros(lam.shape, dtype=LD), np.zeros(lam.shape, dtype=LD)
+    return _combine(factors)[1:]
+
+
+def _segments(seg):
+    """the data dimensions of a segment (seg_len, d) that hold no NaN: [(x0, x1 or None)]"""
+    seg = np.asarray(seg, dtype=np.float64)
+    seg = seg.reshape(seg.shape[0], -1)
+    return [(float(seg[0, k]), float(seg[1, k]) if seg.shape[0] > 1 else None) for k in range(seg.shape[1]) if not np.isnan(seg[:, k]).any()]
+
+
+def _log_term(s2_rel, s):
+    """B = 0.5 ln(2 pi s^2) and its bound for a scale s whose square enters with the relative error s2_rel (beyond M_PI and the two products)"""
+    B = LD(0.5) * np.log(LD(2) * PI_LD * s * s)
+    return B, LD(0.5) * (3 * LD(U) + s2_rel) + C_LOG * LD(U) * np.abs(B)
+
+
+def _gauss_factor(r, dr, s, s_rel):
+    """exp(-r^2 / (2 s^2) - 0.5 ln(2 pi s^2)) for a residual r known to dr absolutely and a scale s known to s_rel relatively: (f, rel, 1)"""
+    u = LD(U)
+    with np.errstate(under='ignore', over='ignore'):
+        den = LD(2) * s * s
+        A = r * r / den
+        eA = ((np.abs(r) + dr) ** 2 - r * r) / den + (3 * u + 2 * s_rel) * A
+        B, eB = _log_term(2 * s_rel, s)
+        f = np.exp(-A - B)
+    return f, eA + eB + u * (A + np.abs(B)) + C_EXP * u, LD(1)
+
+
+def _table_factors(model, g0, g1, seg):
+    u = LD(U)
+    out = []
+    for x0, x1 in _segments(seg):
+        if model == 'bernoulli':            # :430-439: values outside [0, 1] count as 0; any datum other than 0 is a success
+            p = np.where((g0 > 1) | (g0 < 0), LD(0), g0)
+            out.append((p if x0 != 0.0 else LD(1) - p, u * np.ones(np.shape(g0), dtype=LD), LD(1)))
+        elif model == 'laplace':            # :635
+            with np.errstate(under='ignore', over='ignore'):
+                a = np.abs(LD(x0) - g0) / g1
+                out.append((np.exp(-a) / (LD(2) * g1), (2 * a + C_EXP + 1) * u, LD(1) / (LD(2) * g1) + 1))
+        elif model == 'white_noise':        # :767
+            out.append(_gauss_factor(LD(x0) * np.ones(np.shape(g0), dtype=LD), LD(0), g0, LD(0)))
+        elif model in ('ar1', 'scaled_ar1'):
+            r = LD(x1) - g0 * LD(x0)
+            dr = u * (np.abs(g0 * LD(x0)) + np.abs(r))
+            if model == 'ar1':              # :830-831
+                out.append(_gauss_factor(r, dr, g1, LD(0)))
+            else:                           # :893-896
+                one = LD(1) - g0 * g0
+                out.append(_gauss_factor(r, dr, g1 * np.sqrt(one), (LD(0.5) * (1 + g0 * g0 / one) + 2) * u))
+        else:
+            raise ValueError(model)
+    return out
+
+
+def _table(model, grids, seg):
+    g0 = _ld(grids[0]).reshape(-1, 1) if len(grids) == 2 else _ld(grids[0]).reshape(-1)
+    g1 = _ld(grids[1]).reshape(1, -1) if len(grids) == 2 else None
+    shape = (np.size(grids[0]), np.size(grids[1])) if len(grids) == 2 else (np.size(grids[0]),)
+    factors = [(np.broadcast_to(f, shape), np.broadcast_to(r, shape), np.broadcast_to(s, shape)) for f, r, s in _table_factors(model, g0, g1, seg)]
+    if not factors:
+        return np.ones(shape, dtype=LD), np.zeros(shape, dtype=LD), np.zeros(shape, dtype=LD)
+    return _combine(factors)
+
+
+def bernoulli_likelihood(p, seg, bound=False):
+    """observationModels.py:419-439 on the grid p; seg (1, d).  bound: -> (L, e, z) instead of L"""
+    r = _table('bernoulli', [p], seg)
+    return r if bound else r[0]
+
+
+def white_noise_likelihood(sigma, seg, bound=False):
+    """:767 on the grid sigma; seg (1, d)"""
+    r = _table('white_noise', [sigma], seg)
+    return r if bound else r[0]
+
+
+def laplace_likelihood(mu, scale, seg, bound=False):
+    """:635 on the grid mu x scale; seg (1, d)"""
+    r = _table('laplace', [mu, scale], seg)
+    return r if bound else r[0]
+
+
+def ar1_likelihood(rho, sigma, seg, bound=False):
+    """:830-831 on the grid rho x sigma; seg (2, d): rows x_(t-1), x_t"""
+    r = _table('ar1', [rho, sigma], seg)
+    return r if bound else r[0]
+
+
+def scaled_ar1_likelihood(rho, sigma, seg, bound=False):
+    """:893-896 on the grid rho x sigma; seg (2, d)"""
+    r = _table('scaled_ar1', [rho, sigma], seg)
+    return r if bound else r[0]
+
+
+TABLE_LIKELIHOODS = dict(bernoulli=bernoulli_likelihood, white_noise=white_noise_likelihood, laplace=laplace_likelihood, ar1=ar1_likelihood,
+                         scaled_ar1=scaled_ar1_likelihood)

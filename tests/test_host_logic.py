@@ -695,3 +695,56 @@ def test_host_taps_rejects_what_no_builder_takes():
     for kind, params, n in ((4, [1.0], 0), (-1, [1.0], 0), (0, [1.0, 2.0], 0), (0, [float('nan')], 0), (0, [-1.0], 0), (1, [12.5], 0),
                             (2, [1.0, 1.5], 1), (2, [1.0, 1.5], 16385), (2, [1.0, 0.0], 24), (2, [1.0, 2.5], 24), (2, [-1.0, 1.5], 24), (3, [1.0, 1.0, 1.0], 0), (3, [0.0, 1.0, 0.5], 0)):
         assert _host_taps(kind, params, n)[0] is None, (kind, params, n)
+
+
+# ---- which Poisson records take the direct route (include/blhip.h: blhip_host_poisson_direct) -- pure host code of libblhip.so -------------
+
+def _poisson_direct(rates, recs):
+    """(return code, per-record verdicts) as the library decides them for a Poisson problem with this rate grid and these records (T, d)"""
+    import ctypes
+    from bayesloop_amd import _abi
+    rates = np.ascontiguousarray(rates, dtype=np.float64)
+    recs = np.ascontiguousarray(recs, dtype=np.float64)
+    cp = _abi.Problem()
+    cp.ndim, cp.obs_model, cp.T, cp.seg_len, cp.data_dim = 1, _abi.OM_POISSON, len(recs), 1, recs.shape[1]
+    cp.n[0] = len(rates)
+    cp.marginal[0] = _abi.dptr(rates)
+    cp.data = _abi.dptr(recs)
+    out = (ctypes.c_int * len(recs))()
+    rc = _abi.load().blhip_host_poisson_direct(ctypes.byref(cp), out)
+    return rc, list(out)
+
+
+def test_poisson_direct_domain_of_the_issue_cases():
+    """the coal-mining counts stay on the direct route (bit-identical results); counts of 171 and more, k = 150 on rates up to 300 and any count on
+    rates beyond 708 leave it; NaN counts are ignored; each threshold from both sides"""
+    nan = float('nan')
+    tut = np.linspace(0, 6, 1002)[1:-1]
+    assert _poisson_direct(tut, [[0], [6], [nan]]) == (3, [1, 1, 1])
+    assert _poisson_direct(tut, [[170], [171], [nan]]) == (2, [1, 0, 1])
+    r300 = np.linspace(0, 300, 301)[1:]
+    assert _poisson_direct(r300, [[122], [123], [150], [200]]) == (1, [1, 0, 0, 0])        # 122 ln 300 = 695.9, 123 ln 300 = 701.6
+    assert _poisson_direct(r300, [[6, 171], [6, nan], [nan, 171]]) == (1, [0, 1, 0])      # the record's largest count decides for all of its values
+    assert _poisson_direct([0.5, 708.0], [[0], [1], [107]]) == (2, [1, 1, 0])               # 107 ln 708 = 702.1
+    assert _poisson_direct([0.5, 708.5], [[0], [1]]) == (0, [0, 0])                          # exp(-708.5) is subnormal
+    assert _poisson_direct([0.0, 1.0], [[170]]) == (1, [1])                                  # rates up to 1: lambda^k cannot overflow
+    import ctypes
+    from bayesloop_amd import _abi
+    assert _abi.load().blhip_host_poisson_direct(None, None) == -1
+
+
+def test_poisson_direct_domain_matches_its_restatement():
+    """tests/observation_cases.py restates the decision for the bounds of tests/test_observation_kernels.py: the same verdict on every grid and
+    record of that file, alone and in sequences"""
+    import observation_cases as oc
+    n_direct = n_log = 0
+    for case in oc.POISSON_CASES:
+        for n in (300, 600):
+            rates, recs = oc.poisson_rates(case, n), oc.poisson_records(case)
+            for rows in ([0], [1], [2], [0, 1], [0, 1, 2]):
+                rc, verdicts = _poisson_direct(rates, recs[rows])
+                want = [1 if oc.direct_domain(rates, recs[k]) else 0 for k in rows]
+                assert verdicts == want and rc == sum(want), (case, n, rows, verdicts, want)
+                n_direct += sum(want)
+                n_log += len(want) - sum(want)
+    assert n_direct > 50 and n_log > 50                                             # (both verdicts occur)
