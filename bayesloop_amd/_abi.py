@@ -12,10 +12,15 @@ import os
 from .exceptions import BackendError
 
 LIB_NAME = 'libblhip.so'
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 OM_POISSON, OM_GAUSSIAN, OM_GAUSSIAN_MEAN, OM_TABLE = 1, 2, 3, 100
 OM_BERNOULLI, OM_LAPLACE, OM_WHITE_NOISE, OM_AR1, OM_SCALED_AR1 = 4, 5, 6, 7, 8
+OM_PROGRAM = 9      # the density as a postfix program (likprogram.py), evaluated by bllp::lik_program_kernel
+# op codes of a likelihood program (BLHIP_LP_*)
+(LP_CONST, LP_PARAM, LP_DATA, LP_STEP, LP_AXIS, LP_ADD, LP_MUL, LP_DIV, LP_NEG, LP_ABS, LP_SQRT, LP_EXP, LP_LOG, LP_POW, LP_COS, LP_SIN,
+ LP_POWI, LP_LT, LP_LE, LP_EQ, LP_AND, LP_SELECT) = range(22)
+LP_MAX_OPS, LP_MAX_STACK, LP_MAX_POWI = 256, 16, 64
 OP_STATIC, OP_GRW, OP_CHANGEPOINT, OP_REGIMESWITCH, OP_INDEPENDENT, OP_BREAKPOINT, OP_NOTEQUAL = 0, 1, 2, 3, 4, 5, 6
 OP_BIVARIATE, OP_BIVARIATE_ARG, OP_ALPHASTABLE, OP_ALPHASTABLE_ARG = 7, 8, 9, 10
 OP_DETERMINISTIC, OP_DETERMINISTIC_ARG = 11, 12
@@ -119,6 +124,10 @@ PROTOTYPES = {
     'blhip_carry_release': (C.c_int, [C.c_void_p, C.c_int]),
     'blhip_host_rec_envelope': (C.c_int, [C.POINTER(Problem), c_double_p]),
     'blhip_host_poisson_direct': (C.c_int, [C.POINTER(Problem), C.POINTER(C.c_int)]),
+    'blhip_set_lik_program': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int64, c_double_p, C.c_int64, c_double_p, C.c_int64, C.c_int64]),
+    'blhip_host_lik_program_check': (C.c_int, [C.POINTER(C.c_int32), C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_char_p, C.c_int]),
+    'blhip_lik_program_eval': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(c_double_p), C.c_int64, C.c_int, c_double_p,
+                                         c_double_p]),
     'blhip_host_taps': (C.c_int64, [C.c_int, C.c_int64, c_double_p, C.c_int, c_double_p, C.c_int64, C.POINTER(C.c_int)]),
 }
 

@@ -434,9 +434,16 @@ class Study(object):
         if any(op[0] == _abi.OP_INDEPENDENT for op in program):
             indep = self._changepointPrior() / np.prod(self.latticeConstant)      # sum 1 (reference transitionModels.py:351-360)
         data = np.asarray(self.formattedData, dtype=float)
-        lik = None
+        lik = lik_program = None
         code = device_code(om)
-        if code == _abi.OM_TABLE:
+        prog = self._likelihoodProgram(om) if code == _abi.OM_TABLE else None
+        if prog is not None:
+            # the density as a program: the (T, G) table is built on the device (bllp::lik_program_kernel), nothing is evaluated here
+            # but the data-only subtrees (per step and data dimension) and the tables of one-parameter functions (per axis)
+            code = _abi.OM_PROGRAM
+            lp_ops, lp_consts = prog.bind(self.marginalGrid)
+            lik_program = (lp_ops, lp_consts, prog.step_values(data.reshape(len(data), -1)))
+        elif code == _abi.OM_TABLE:
             # the model's own pdf, evaluated once per time step on the host (plug-in interface of the reference)
             lik = np.array([np.asarray(om.processedPdf(self.grid, seg), dtype=float) * np.ones(self.gridSize)
                             for seg in self.formattedData])
@@ -444,9 +451,21 @@ class Study(object):
         problem = FitProblem(obs_model=code, marginal=self.marginalGrid, lattice=self.latticeConstant, data=data,
                              timestamps=np.asarray(self.formattedTimestamps, dtype=float), prior=prior,
                              ops=[(op[0], op[1], op[4], op[5]) for op in program], reset_prior=reset, indep_prior=indep,
-                             lik=lik,
+                             lik=lik, lik_program=lik_program,
                              seg_len=om.segmentLength)
         return problem, program
+
+    @staticmethod
+    def _likelihoodProgram(om):
+        """The observation model's density as a program for the device, or None: the model has none (bl.om.NumPy, user subclasses, a
+        density outside the instruction set), the engine takes none (an engine without ``lik_programs``), or option lik_program is 0."""
+        eng = _engine_mod.get_engine()
+        if not getattr(eng, 'lik_programs', False) or getattr(eng, 'options', {}).get('lik_program', 1.0) == 0:
+            return None
+        if om.segmentLength != 1 or not om.multiplyLikelihoods:
+            return None
+        make = getattr(om, 'likelihoodProgram', None)
+        return make() if make is not None else None
 
     @staticmethod
     def _expandProgram(program, T):

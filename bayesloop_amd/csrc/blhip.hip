@@ -41,6 +41,7 @@
 #include "blhip_chainres.hpp"
 #include "blhip_chain_launch.hpp"
 #include "blhip_nd.hpp"
+#include "blhip_likprog.hpp"
 
 using namespace blk;
 
@@ -64,7 +65,8 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
     // closed-form models without an in-kernel likelihood: their (T, G) table is built on the device, the step kernels
     // then see a tabulated likelihood
     blhip_problem p_local = *p_in;
-    const int table_model = (p_in->obs_model >= BLHIP_OM_BERNOULLI && p_in->obs_model <= BLHIP_OM_SCALED_AR1) ? p_in->obs_model : 0;
+    // (... and models whose density is a program: bllp::lik_program_kernel)
+    const int table_model = (p_in->obs_model >= BLHIP_OM_BERNOULLI && p_in->obs_model <= BLHIP_OM_PROGRAM) ? p_in->obs_model : 0;
     if (table_model) p_local.obs_model = BLHIP_OM_TABLE;
     const blhip_problem *p = &p_local;
     HIPCHECK(hipSetDevice(ctx->device));
@@ -992,7 +994,7 @@ void blhip_destroy(blhip_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     (void)blhip_comm_destroy(ctx);
-    ctx->commbuf.release(); ctx->pinC.release(); ctx->resx.release(); ctx->post2.release(); ctx->postpad.release(); ctx->accw.release(); ctx->accpart.release(); ctx->xch.release(); ctx->axlik.release(); ctx->anchbuf.release(); ctx->probebuf.release(); ctx->p1d.release(); ctx->p1w.release(); ctx->lik1d.release();
+    ctx->commbuf.release(); ctx->pinC.release(); ctx->resx.release(); ctx->post2.release(); ctx->postpad.release(); ctx->accw.release(); ctx->accpart.release(); ctx->xch.release(); ctx->axlik.release(); ctx->anchbuf.release(); ctx->probebuf.release(); ctx->p1d.release(); ctx->p1w.release(); ctx->lik1d.release(); ctx->likprog_dev.release();
     if (ctx->astream) { (void)hipStreamSynchronize(ctx->astream); (void)hipStreamDestroy(ctx->astream); }
     for (auto &e : ctx->aev_done) if (e) (void)hipEventDestroy(e);
     for (DevBuf *b : {&ctx->state, &ctx->post, &ctx->psumF, &ctx->psumB, &ctx->redF, &ctx->redB, &ctx->meta,
@@ -1107,6 +1109,57 @@ int64_t blhip_host_taps(int kind, int64_t n, const double *params, int n_params,
     }
 }
 
+int blhip_host_lik_program_check(const int32_t *ops, int64_t n_ops, int64_t n_consts, int64_t n_step, int ndim, char *err, int errlen) {
+    return bllp::check_program(ops, n_ops, n_consts, n_step, ndim, err, errlen);
+}
+
+int blhip_set_lik_program(blhip_ctx *ctx, const int32_t *ops, int64_t n_ops, const double *consts, int64_t n_consts,
+                          const double *step_values, int64_t n_step, int64_t n_step_values) {
+    return guarded(ctx, [&] {
+        ctx->likprog.armed = false;
+        char msg[256] = "";
+        if (bllp::check_program(ops, n_ops, n_consts, n_step, BLHIP_MAX_DIM, msg, (int)sizeof msg) != 0) fail("blhip_set_lik_program: %s", msg);
+        if ((n_consts > 0 && !consts) || n_step_values < 0 || (n_step_values > 0 && !step_values)) fail("blhip_set_lik_program: consts / step_values is NULL");
+        if (n_step == 0 ? n_step_values != 0 : n_step_values % n_step != 0)
+            fail("blhip_set_lik_program: %lld step values are no (T, data_dim, n_step = %lld) array", (long long)n_step_values, (long long)n_step);
+        blhip_ctx::LikProgram &LP = ctx->likprog;
+        LP.ops.assign(ops, ops + 2 * n_ops);
+        LP.consts.assign(consts, consts + n_consts);
+        LP.step.assign(step_values, step_values + n_step_values);
+        LP.n_step = n_step;
+        LP.armed = true;
+    });
+}
+
+int blhip_lik_program_eval(blhip_ctx *ctx, int ndim, const int64_t *n, const double *const *marginal, int64_t T, int data_dim,
+                           const double *data, double *out) {
+    return guarded(ctx, [&] {
+        if (ndim < 1 || ndim > BLHIP_MAX_DIM || !n || !marginal || T < 1 || data_dim < 1 || !data || !out) fail("blhip_lik_program_eval: bad arguments");
+        HIPCHECK(hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        long long G = 1;
+        size_t mb = 0;
+        for (int k = 0; k < ndim; ++k) {
+            if (n[k] < 1 || n[k] > (1ll << 30) || !marginal[k]) fail("blhip_lik_program_eval: bad grid axis %d", k);
+            G *= n[k];
+            mb += carve_size(8 * (size_t)n[k]);
+        }
+        ScopedDevBuf grid, table;
+        grid.ensure(mb);
+        table.ensure(8 * (size_t)T * G);
+        char *cur = grid.as<char>();
+        const double *dm[BLHIP_MAX_DIM] = {nullptr, nullptr, nullptr, nullptr};
+        for (int k = 0; k < ndim; ++k) {
+            double *d = carve<double>(cur, (size_t)n[k]);
+            HIPCHECK(hipMemcpyAsync(d, marginal[k], 8 * (size_t)n[k], hipMemcpyHostToDevice, st));
+            dm[k] = d;
+        }
+        build_program_table(ctx, ndim, n, dm, T, data_dim, data, table.as<double>());
+        HIPCHECK(hipMemcpyAsync(out, table.p, 8 * (size_t)T * G, hipMemcpyDeviceToHost, st));
+        sync_stream(ctx, st);
+    });
+}
+
 int blhip_set_option(blhip_ctx *ctx, const char *key, double value) {
     if (!ctx || !key) return -1;
     // "resident_ok": the context's memory of a resident launch that gave up (its blocks were not all co-resident) -- settable so that
@@ -1116,7 +1169,7 @@ int blhip_set_option(blhip_ctx *ctx, const char *key, double value) {
     // (a key the library never reads is an error, not a silent no-op: an A/B run over a removed option measured nothing -- ADVICE r05)
     static const char *const known[] = {
         "accum_overlap", "carry_partials", "chain1d", "chain1d_clamp", "chain1d_shift", "chain_ax1", "chain_depad", "chain_prof", "chain_resident", "chain_resident_lag",
-        "chain_force_fail_batch", "chain_force_fail_stage", "chain_table", "chain_wide", "comm_reduce_mode", "fast", "fast_S", "fold2", "fold2_cp", "fold_force_fail_batch", "fuse1d", "fuse_accumulate", "late_sums", "max_batch",
+        "chain_force_fail_batch", "chain_force_fail_stage", "chain_table", "chain_wide", "comm_reduce_mode", "fast", "fast_S", "fold2", "fold2_cp", "fold_force_fail_batch", "fuse1d", "fuse_accumulate", "late_sums", "lik_program", "max_batch",
         "mem_budget_bytes", "mfma", "mfma_S", "mfma_h", "mfma_h_max_cells", "peer_copy_mode", "persist1d", "quiet", "recurrence", "resident",
         "resident_force_abort", "resident_lag", "resident_probe", "resident_probe_force_busy", "resident_probe_interval_s", "resident_probe_timeout_s",
         "resident_table", "resident_timeout_s", "share_prefix", "short_first_batch", "skip_prefix", "trace", "wide_h",

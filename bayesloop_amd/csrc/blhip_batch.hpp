@@ -158,6 +158,54 @@ inline double rec_envelope_bound(const double *m0, int n0, const double *s, int 
     return b == b ? b : INFINITY;          // (a NaN bound -- a zero or NaN std -- is no envelope)
 }
 
+// ---- BLHIP_OM_PROGRAM: the (T, G) likelihood table from the program the context is armed with (bllp::lik_program_kernel) ---------------------
+// d_marginal: the marginal grids on the device, n[k] values each; data: (T, data_dim) on the host; d_lik: (T, G) on the device.  The
+// program's arrays, the step values and the data go into one buffer of the context; queued on the context's stream, not waited for.
+void build_program_table(blhip_ctx *ctx, int ndim, const int64_t *n, const double *const *d_marginal, int64_t T, int data_dim,
+                         const double *data, double *d_lik) {
+    const blhip_ctx::LikProgram &LP = ctx->likprog;
+    if (ctx->option("lik_program", 1.0) == 0.0) fail("BLHIP_OM_PROGRAM: option lik_program = 0 keeps the caller-evaluated table (BLHIP_OM_TABLE)");
+    if (!LP.armed) fail("BLHIP_OM_PROGRAM: no likelihood program is armed (blhip_set_lik_program)");
+    if (ndim < 1 || ndim > bllp::MAX_DIM || T < 1 || data_dim < 1 || !data || !d_lik) fail("BLHIP_OM_PROGRAM: bad grid / data");
+    const int64_t n_ops = (int64_t)LP.ops.size() / 2, n_consts = (int64_t)LP.consts.size();
+    char msg[256] = "";
+    if (bllp::check_program(LP.ops.data(), n_ops, n_consts, LP.n_step, ndim, msg, (int)sizeof msg) != 0) fail("%s", msg);
+    if ((int64_t)LP.step.size() != T * data_dim * LP.n_step)
+        fail("BLHIP_OM_PROGRAM: the armed program carries %lld step values, the problem needs (T, data_dim, n_step) = (%lld, %d, %lld)",
+             (long long)LP.step.size(), (long long)T, data_dim, (long long)LP.n_step);
+    long long G = 1;
+    for (int k = 0; k < ndim; ++k) {
+        if (n[k] < 1 || n[k] > (1ll << 30) || !d_marginal[k]) fail("BLHIP_OM_PROGRAM: bad grid axis %d", k);
+        G *= n[k];
+    }
+    for (int64_t pc = 0; pc < n_ops; ++pc)           // a tabulated function of one parameter spans that parameter's axis
+        if (LP.ops[2 * pc] == bllp::OP_AXIS && (int64_t)(LP.ops[2 * pc + 1] >> 2) + n[LP.ops[2 * pc + 1] & 3] > n_consts)
+            fail("BLHIP_OM_PROGRAM: op %lld: AXIS table of parameter %d (%lld values from constant %d) runs past the %lld constants",
+                 (long long)pc, LP.ops[2 * pc + 1] & 3, (long long)n[LP.ops[2 * pc + 1] & 3], LP.ops[2 * pc + 1] >> 2, (long long)n_consts);
+    hipStream_t st = ctx->stream;
+    const size_t nd = (size_t)T * data_dim;
+    ctx->likprog_dev.ensure(carve_size(LP.ops.size() * 4) + carve_size(std::max<size_t>(1, LP.consts.size()) * 8) +
+                            carve_size(std::max<size_t>(1, LP.step.size()) * 8) + carve_size(nd * 8));
+    char *cur = ctx->likprog_dev.as<char>();
+    bllp::Instr *d_ops = carve<bllp::Instr>(cur, (size_t)n_ops);
+    double *d_consts = carve<double>(cur, std::max<size_t>(1, LP.consts.size())), *d_step = carve<double>(cur, std::max<size_t>(1, LP.step.size())),
+           *d_data = carve<double>(cur, nd);
+    HIPCHECK(hipMemcpyAsync(d_ops, LP.ops.data(), LP.ops.size() * 4, hipMemcpyHostToDevice, st));
+    if (!LP.consts.empty()) HIPCHECK(hipMemcpyAsync(d_consts, LP.consts.data(), LP.consts.size() * 8, hipMemcpyHostToDevice, st));
+    if (!LP.step.empty()) HIPCHECK(hipMemcpyAsync(d_step, LP.step.data(), LP.step.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_data, data, nd * 8, hipMemcpyHostToDevice, st));
+    bllp::LikProgParams P{};
+    P.ops = d_ops; P.consts = d_consts; P.G = G; P.n_ops = (int)n_ops; P.n_step = (int)LP.n_step; P.dd = data_dim; P.ndim = ndim;
+    for (int k = 0; k < ndim; ++k) { P.m[k] = d_marginal[k]; P.n[k] = (int)n[k]; }
+    const unsigned gx = (unsigned)std::min<long long>((G + bllp::NT - 1) / bllp::NT, 2048);
+    for_grid_y(ctx, T, [&](long long t0, unsigned nt) {
+        bllp::LikProgParams Q = P;
+        Q.step = d_step + (size_t)t0 * data_dim * LP.n_step; Q.data = d_data + (size_t)t0 * data_dim; Q.lik = d_lik + (size_t)t0 * G;
+        BL_LAUNCH(bllp::lik_program_kernel, dim3(gx, nt), dim3(bllp::NT), 0, st, Q);
+    });
+    HIPCHECK(hipGetLastError());
+}
+
 // what every chain of the call shares, resident in HBM for the duration of the call
 struct DeviceTables {
     double *m0, *m1, *colA, *colB, *rec, *prior, *reset, *uniform, *indep, *lik;
@@ -218,7 +266,10 @@ DeviceTables upload_tables(blhip_ctx *ctx, const blhip_problem *p, const Geometr
     if (p->obs_model == BLHIP_OM_TABLE) {
         ctx->likbuf.ensure(sizeof(double) * T * G);
         D.lik = ctx->likbuf.as<double>();
-        if (table_model) {
+        if (table_model == BLHIP_OM_PROGRAM) {
+            const double *dm[BLHIP_MAX_DIM] = {p->ndim == 2 ? D.m0 : D.m1, D.m1, nullptr, nullptr};
+            build_program_table(ctx, p->ndim, p->n, dm, T, p->data_dim, p->data, D.lik);
+        } else if (table_model) {
             const size_t nd = (size_t)T * p->seg_len * p->data_dim;
             ctx->databuf.ensure(nd * 8);
             HIPCHECK(hipMemcpyAsync(ctx->databuf.p, p->data, nd * 8, hipMemcpyHostToDevice, st));

@@ -41,7 +41,8 @@ void do_fit_nd(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, const d
     else BL_LAUNCH(fill_kernel, dim3(256), dim3(256), 0, st, d_uniform, G, 1.0 / (double)G);           // beta_T = 1/G, core.py:424-425
     ctx->likbuf.ensure(8 * (size_t)T * G);
     double *d_lik = ctx->likbuf.as<double>();
-    HIPCHECK(hipMemcpyAsync(d_lik, p->lik, 8 * (size_t)T * G, hipMemcpyHostToDevice, st));
+    if (p->obs_model == BLHIP_OM_PROGRAM) build_program_table(ctx, p->ndim, p->n, ng.m, T, p->data_dim, p->data, d_lik);
+    else HIPCHECK(hipMemcpyAsync(d_lik, p->lik, 8 * (size_t)T * G, hipMemcpyHostToDevice, st));
     sync_stream(ctx, st);
 
     // ---- batches ---------------------------------------------------------------------------------------------------------------------

@@ -129,6 +129,10 @@ struct blhip_ctx {
     DevBuf stagebuf, stagemeta;  // composed transitions: two stage outputs (+ their partials) of a step, the stages' per-chain programs (blhip_batch.hpp)
     DevBuf p1d, p1w;             // hand-off buffers / weight table of the persistent 1-D kernel (blhip_persist1d.hpp)
     DevBuf lik1d;                // (T, n) likelihood table the chains of a 1-D batch share (blhip_chain1d.hpp)
+    // the likelihood program blhip_set_lik_program armed for the problems whose obs_model is BLHIP_OM_PROGRAM (blhip_likprog.hpp): host
+    // copies of its arrays, and the device buffer a table build uploads them to
+    struct LikProgram { std::vector<int32_t> ops; std::vector<double> consts, step; int64_t n_step = 0; bool armed = false; } likprog;
+    DevBuf likprog_dev;
     DevBuf accpart;              // partial accumulators of the fused fold (one per launch slot of the chain-resident kernel)
     // The partial accumulators are CARRIED from batch to batch of one blhip_fit call (round 6): the batches' weights share the reference of
     // the first one, the slots go into the average posterior once, after the call's last batch (fold_parts_kernel read 8 + 2 sequences of

@@ -166,7 +166,8 @@ void validate(const blhip_problem *p, int64_t n_chains, const double *op_values)
     if (!p) fail("problem is NULL");
     if (p->ndim < 1 || p->ndim > BLHIP_MAX_DIM) fail("ndim must be 1 .. %d (got %d)", BLHIP_MAX_DIM, p->ndim);
     if (p->ndim > 2) {            // the plain N-D path (blhip_nd.hpp)
-        if (p->obs_model != BLHIP_OM_TABLE) fail("grids with %d parameters need a caller-evaluated likelihood table (BLHIP_OM_TABLE)", p->ndim);
+        if (p->obs_model != BLHIP_OM_TABLE && p->obs_model != BLHIP_OM_PROGRAM)
+            fail("grids with %d parameters need a caller-evaluated likelihood table (BLHIP_OM_TABLE) or a likelihood program (BLHIP_OM_PROGRAM)", p->ndim);
         for (int k = 0; k < p->n_ops; ++k) {
             const blhip_op &op = p->ops[k];
             const bool ok = op.kind == BLHIP_OP_GRW || op.kind == BLHIP_OP_STATIC || (op.kind == BLHIP_OP_CHANGEPOINT && !(op.flags & 1));
@@ -228,6 +229,9 @@ void validate(const blhip_problem *p, int64_t n_chains, const double *op_values)
             break;
         case BLHIP_OM_TABLE:
             if (!p->lik) fail("BLHIP_OM_TABLE needs lik");
+            break;
+        case BLHIP_OM_PROGRAM:
+            if (p->seg_len != 1) fail("BLHIP_OM_PROGRAM: likelihood programs have segment length 1");
             break;
         case BLHIP_OM_BERNOULLI: case BLHIP_OM_WHITE_NOISE:
             if (p->ndim != 1 || p->seg_len != 1) fail("Bernoulli / white-noise models have 1 parameter and segment length 1");

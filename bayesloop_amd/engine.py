@@ -37,6 +37,8 @@ class FitProblem:
     resume_time: float = -1.0           # BLHIP_RESUME: time stamp the transition into step 0 is evaluated at
     carry_slot: int = 0                 # which carried state of the context (OnlineStudy: one per transition model)
     backward_init: Optional[np.ndarray] = None  # the backward message entering the last step (None: uniform, core.py:424-425)
+    # OM_PROGRAM: (ops (n_ops, 2) int32, consts float64, step values (T, data_dim, n_step)) of the density (likprogram.Program)
+    lik_program: Optional[Tuple] = None
 
     @property
     def grid_size(self):
@@ -204,6 +206,7 @@ class HipEngine:
     """One libblhip context on one GPU."""
 
     name = 'hip'
+    lik_programs = True      # takes FitProblem.lik_program (OM_PROGRAM): Study._compile then leaves the likelihood to the device
 
     def __init__(self, device: int = 0):
         self.lib = _abi.load()
@@ -215,6 +218,8 @@ class HipEngine:
             raise BackendError('blhip_create(%d) failed: %s' % (device, self.lib.blhip_last_error(None).decode()))
         self._posterior_owner = None
         self._keep = []
+        self.options = {}            # what set_option was called with
+        self.last_lik_upload_bytes = 0
         self._pinned = _PinnedPool(self.lib)
         # engine options from the environment, e.g. BLHIP_ENGINE_OPTS=resident_timeout_s=2 for processes that SHARE a GPU (the
         # resident kernels wait for peer blocks that another process's kernels may keep off the chip for a while)
@@ -244,6 +249,28 @@ class HipEngine:
 
     def set_option(self, key, value):
         self._check(self.lib.blhip_set_option(self.ctx, key.encode(), float(value)))
+        self.options[key] = float(value)
+
+    def set_lik_program(self, ops, consts, step_values):
+        """Arms this engine's context with a likelihood program (blhip_set_lik_program): ops (n_ops, 2) int32 [code, arg], consts
+        float64, step_values (T, data_dim, n_step) float64."""
+        ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 2)
+        consts, step = _f64(consts).ravel(), _f64(step_values)
+        n_step = step.shape[-1] if step.ndim == 3 else 0
+        self._check(self.lib.blhip_set_lik_program(self.ctx, ops.ctypes.data_as(C.POINTER(C.c_int32)), len(ops), _abi.dptr(consts), consts.size,
+                                                   _abi.dptr(step) if step.size else None, n_step, step.size))
+
+    def lik_program_eval(self, marginal, data):
+        """The (T, G) table bllp::lik_program_kernel builds for the armed program on the grid `marginal` and the data (T, data_dim)."""
+        ms = [_f64(m) for m in marginal]
+        data = _f64(data)
+        T = data.shape[0]
+        data = data.reshape(T, -1)
+        n = (C.c_int64 * len(ms))(*[len(m) for m in ms])
+        mp = (_abi.c_double_p * len(ms))(*[_abi.dptr(m) for m in ms])
+        out = np.empty((T, int(np.prod([len(m) for m in ms]))))
+        self._check(self.lib.blhip_lik_program_eval(self.ctx, len(ms), n, mp, T, data.shape[1], _abi.dptr(data), _abi.dptr(out)))
+        return out
 
     _token_counter = [0]
 
@@ -339,6 +366,9 @@ class HipEngine:
             self._posterior_owner = None
             prev._materialize_posterior()      # the previous study's posterior still lives in this context
         cp, keep = self._problem(problem)
+        if problem.lik_program is not None:           # (every context arms itself: fit(nJobs=N) has one per GPU)
+            self.set_lik_program(*problem.lik_program)
+        self.last_lik_upload_bytes = 0 if problem.lik is None else 8 * problem.T * problem.G      # the host-evaluated table of this fit
         ov = _f64(op_values).reshape(-1, max(1, len(problem.ops))) if len(problem.ops) else np.zeros((len(op_values), 1))
         n = ov.shape[0] if len(problem.ops) else len(op_values)
         T, ndim = problem.T, len(problem.marginal)

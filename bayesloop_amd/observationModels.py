@@ -9,6 +9,11 @@ same.  What differs is who evaluates the likelihood on the grid during ``fit()``
 * ``Bernoulli``, ``Laplace``, ``WhiteNoise``, ``AR1``, ``ScaledAR1``: their (T, G) likelihood table is built ON THE DEVICE
   from the data (``blk::lik_table_kernel``; reference pdfs at observationModels.py:428-430, 635, 767, 830-831, 893-896):
   no host evaluation, no upload.
+* ``SymPy`` and ``SciPy``: where the density is an expression the package can see (``SymPy``: always; ``SciPy``: a fixed list of
+  distributions written out in bayesloop_amd/likprogram.py) it is compiled into a small postfix program and the (T, G) table is built
+  ON THE DEVICE by ``bllp::lik_program_kernel`` -- no host evaluation, no upload.  Densities with a function outside the program's
+  instruction set (``besseli`` of a parameter in VonMises), SciPy distributions off the list and subclasses that override ``pdf``
+  take the next path.
 * any other model -- user subclasses with a ``pdf(grid, dataSegment)`` method (the reference's duck-typed plug-in
   interface, observationModels.py:35-56), including subclasses that override the ``pdf`` of a model above -- is
   evaluated once on the host with the model's own ``pdf`` and uploaded as a (T, G) likelihood table; the recursion
@@ -361,6 +366,32 @@ class SciPy(ObservationModel):
         f = self.rv.pdf if self.isContinuous else self.rv.pmf
         return f(dataSegment[0], **params)
 
+    def likelihoodProgram(self):
+        """The density as a program for the device (bayesloop_amd/likprogram.py), or None: the distribution is not among those written
+        out there, a fixed parameter is no number, or ``pdf`` is overridden.  fixedParameters are folded as constants."""
+        if '_program' not in self.__dict__:
+            self._program = None
+            if type(self).pdf is SciPy.pdf:
+                from . import likprogram
+                import sympy
+                spec = likprogram.scipy_density(getattr(self.rv, 'name', None))
+                try:
+                    if spec is not None:
+                        expr, x, symbols = spec
+                        fixed = {symbols[k]: sympy.Float(float(v)) if float(v) != int(float(v)) else sympy.Integer(int(float(v)))
+                                 for k, v in self.fixedParameterDict.items()}
+                        if set(self.parameterNames) | set(self.fixedParameterDict) == set(symbols):
+                            self._program = likprogram.compile_density(expr.subs(fixed), x, [symbols[n] for n in self.parameterNames],
+                                                                       modules=['scipy', 'numpy'], axis_functions=True)
+                except (KeyError, TypeError, ValueError):
+                    self._program = None
+        return self._program
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop('_program', None)          # (compiled again on first use: it holds host functions that need not pickle)
+        return state
+
 
 class SymPy(ObservationModel):
     """Observation model from a ``sympy.stats`` random variable (reference observationModels.py:272-391):
@@ -414,10 +445,26 @@ class SymPy(ObservationModel):
                 print('    ! WARNING: Failed to determine Jeffreys prior. Will use flat prior instead.')
                 self.prior = None
         x = abc.x
-        self.density = sympy.lambdify([x] + ordered, density(rv)(x), modules=['numpy', {'factorial': factorial, 'besseli': iv}])
+        self.densityExpression, self.densitySymbols = density(rv)(x), [x] + ordered
+        self.density = sympy.lambdify([x] + ordered, self.densityExpression, modules=['numpy', {'factorial': factorial, 'besseli': iv}])
 
     def pdf(self, grid, dataSegment):
         return self.density(dataSegment[0], *grid)
+
+    def likelihoodProgram(self):
+        """The density as a program for the device (bayesloop_amd/likprogram.py), compiled on first use; None when the expression holds
+        anything outside the program's instruction set, or ``pdf`` is overridden."""
+        if '_program' not in self.__dict__:
+            self._program = None
+            if type(self).pdf is SymPy.pdf:
+                from . import likprogram
+                self._program = likprogram.compile_density(self.densityExpression, self.densitySymbols[0], self.densitySymbols[1:])
+        return self._program
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop('_program', None)          # (compiled again on first use: it holds host functions that need not pickle)
+        return state
 
 
 def device_code(om):

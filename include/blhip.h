@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define BLHIP_ABI_VERSION 8
+#define BLHIP_ABI_VERSION 9
 
 typedef struct blhip_ctx blhip_ctx;
 
@@ -57,6 +57,10 @@ enum {
     BLHIP_OM_WHITE_NOISE   = 6,   /* observationModels.py:756-767  1 parameter  (sigma)                           */
     BLHIP_OM_AR1           = 7,   /* observationModels.py:819-831  2 parameters (rho, sigma); seg_len 2           */
     BLHIP_OM_SCALED_AR1    = 8,   /* observationModels.py:881-896  2 parameters (rho, sigma); seg_len 2           */
+    /* (ABI v9) the density as a postfix program the caller compiled from an expression (bl.om.SymPy, bl.om.SciPy): the (T,G) table is
+     * built ON THE DEVICE by one interpreter kernel from the program armed with blhip_set_lik_program; lik stays NULL, seg_len is 1.
+     * Grids of 1 .. BLHIP_MAX_DIM parameters. */
+    BLHIP_OM_PROGRAM       = 9,   /* observationModels.py:35-56 over a density written as a program                */
     BLHIP_OM_TABLE         = 100  /* likelihood evaluated by the caller (any ObservationModel.pdf): lik (T,G) */
 };
 
@@ -106,8 +110,8 @@ typedef struct {
 /* The fit problem: grid, data, prior, transition program (shared by all chains of a call). */
 typedef struct {
     int32_t        ndim;          /* number of observation-model parameters = grid dimensions (core.py:130-176 builds a
-                                     meshgrid over any number): 1 .. BLHIP_MAX_DIM.  3 and more: BLHIP_OM_TABLE models
-                                     (the reference's SciPy / SymPy / NumPy plug-ins) with GRW / STATIC / CHANGEPOINT ops */
+                                     meshgrid over any number): 1 .. BLHIP_MAX_DIM.  3 and more: BLHIP_OM_TABLE / BLHIP_OM_PROGRAM
+                                     models (the reference's SciPy / SymPy / NumPy plug-ins) with GRW / STATIC / CHANGEPOINT ops */
     int32_t        obs_model;     /* BLHIP_OM_*                                                                  */
     int64_t        n[BLHIP_MAX_DIM];          /* grid size per parameter (core.py:157)                           */
     const double  *marginal[BLHIP_MAX_DIM];   /* marginal grid values per parameter, n[k] doubles (core.py:156)  */
@@ -328,6 +332,38 @@ int blhip_host_poisson_direct(const blhip_problem *problem, int *direct_out);
  * Returns the number of weights (nothing is written beyond `cap`: call with out = NULL to size the buffer), or -1 for arguments
  * no builder takes. */
 int64_t blhip_host_taps(int kind, int64_t n, const double *params, int n_params, double *out, int64_t cap, int *radius_out);
+
+/* ---- likelihood programs (ABI v9; bayesloop_amd/likprogram.py compiles them from SymPy expressions) ---------------------------------
+ * The density of an observation model as a postfix program over the data point and the grid's parameters: one {int32 code, int32 arg}
+ * record per op, at most 256 ops, stack depth at most 16, exactly one value left at the end.
+ *   pushes      CONST i: consts[i];  PARAM k: the marginal grid value of parameter k at the cell;  DATA: the datum of the current data
+ *               dimension;  STEP j: step_values[t][dimension][j], a data-only subtree the caller evaluated (factorial(x), binomial(10, x));
+ *               AXIS a: consts[(a >> 2) + index of the cell along parameter (a & 3)], a function of ONE parameter the caller tabulated
+ *               along that parameter's axis inside `consts`
+ *   arithmetic  ADD MUL DIV NEG ABS SQRT EXP LOG POW COS SIN;  POWI n: integer exponent |n| <= 64 by multiplications (x**2 is x * x)
+ *   logic       LT LE EQ (1.0 / 0.0), AND, SELECT (a b c -> c != 0 ? a : b)
+ * The likelihood of a step is the product over the data dimensions of the density; a NaN datum contributes the factor 1
+ * (observationModels.py:35-56). */
+enum {
+    BLHIP_LP_CONST = 0, BLHIP_LP_PARAM = 1, BLHIP_LP_DATA = 2, BLHIP_LP_STEP = 3, BLHIP_LP_AXIS = 4,
+    BLHIP_LP_ADD = 5, BLHIP_LP_MUL = 6, BLHIP_LP_DIV = 7, BLHIP_LP_NEG = 8, BLHIP_LP_ABS = 9, BLHIP_LP_SQRT = 10, BLHIP_LP_EXP = 11,
+    BLHIP_LP_LOG = 12, BLHIP_LP_POW = 13, BLHIP_LP_COS = 14, BLHIP_LP_SIN = 15, BLHIP_LP_POWI = 16,
+    BLHIP_LP_LT = 17, BLHIP_LP_LE = 18, BLHIP_LP_EQ = 19, BLHIP_LP_AND = 20, BLHIP_LP_SELECT = 21
+};
+/* Arms the context: the next blhip_fit / blhip_accum_* problems whose obs_model is BLHIP_OM_PROGRAM evaluate THIS program (the arrays are
+ * copied; it stays armed until the next call).  ops: n_ops records (2 n_ops int32); consts: n_consts doubles; step_values:
+ * (T, data_dim, n_step) doubles (NULL when n_step = 0).  The program is validated here (blhip_host_lik_program_check, with the 4
+ * parameters an ABI grid can have at most) and again against the problem: a fit with BLHIP_OM_PROGRAM and no armed program fails, so does
+ * one whose T * data_dim * n_step differs from n_step_values, the number of doubles passed here. */
+int blhip_set_lik_program(blhip_ctx *ctx, const int32_t *ops, int64_t n_ops, const double *consts, int64_t n_consts,
+                          const double *step_values, int64_t n_step, int64_t n_step_values);
+/* Host-only validation (no GPU, no context): the stack discipline (no underflow, depth <= 16, one value left), n_ops <= 256, every CONST /
+ * STEP / PARAM / AXIS index in range, |n| of POWI <= 64.  Returns 0, or -1 with the reason in err (errlen bytes, may be NULL). */
+int blhip_host_lik_program_check(const int32_t *ops, int64_t n_ops, int64_t n_consts, int64_t n_step, int ndim, char *err, int errlen);
+/* Runs the SAME kernel a fit runs for the armed program on the grid marginal[0 .. ndim-1] (n[k] values each) and the data (T, data_dim),
+ * and copies the (T, G) table to host memory `out`: what the cell-by-cell tests read. */
+int blhip_lik_program_eval(blhip_ctx *ctx, int ndim, const int64_t *n, const double *const *marginal, int64_t T, int data_dim,
+                           const double *data, double *out);
 
 /* ---- multi-GPU exchange of a sharded hyper-study (HyperStudy.fit(nJobs > 1), core.py:1307-1340, 1443-1495) -------------
  * One process per GPU, one context per process; each rank fits its share of the hyper-grid points with blhip_fit and
