@@ -417,6 +417,19 @@ class Study(object):
         self.formattedData = movingWindow(self.rawData, seg)
         self.formattedTimestamps = self.rawTimestamps[seg - 1:]
 
+    def _checkManyParameterProgram(self, program):
+        """Grids with more than two parameters run every built-in transition model but three; raised before any device work."""
+        if len(self.gridSize) <= 2 or program is None:
+            return
+        kinds = set(op[0] for op in program)
+        if _abi.OP_ALPHASTABLE in kinds:                  # (the reference's own refusal, transitionModels.py:213-215)
+            raise ConfigurationError('Parameter grid must either be 1- or 2-dimensional.')
+        if _abi.OP_BIVARIATE in kinds:
+            raise ConfigurationError('BivariateRandomWalk needs an observation model with exactly two parameters.')
+        if _abi.OP_REGIMESWITCH in kinds:
+            raise ConfigurationError('Observation models with more than two parameters cannot be combined with the RegimeSwitch '
+                                     'transition model.')
+
     def _compile(self, silent=True):
         """-> (FitProblem, program) ; program = [(kind, axis, model, hyper index)] in list order."""
         om = self.observationModel
@@ -424,10 +437,7 @@ class Study(object):
         if not 1 <= len(self.gridSize) <= _abi.MAX_DIM:
             raise ConfigurationError('The MI355X engine supports observation models with 1 to {} parameters '
                                      '(got {}).'.format(_abi.MAX_DIM, len(self.gridSize)))
-        if len(self.gridSize) > 2 and not all(op[0] in (_abi.OP_GRW, _abi.OP_STATIC, _abi.OP_CHANGEPOINT) and op[4] < 0
-                                              for op in program):
-            raise ConfigurationError('Observation models with more than two parameters can be combined with GaussianRandomWalk, '
-                                     'Static and ChangePoint transition models.')
+        self._checkManyParameterProgram(program)
         prior = self._computePrior(silent=silent)
         reset = self._changepointPrior() if any(op[0] == _abi.OP_CHANGEPOINT for op in program) else None
         indep = None
@@ -1424,9 +1434,7 @@ class OnlineStudy(HyperStudy):
                                          'contains such a model); user-defined transition models are supported by Study.fit and '
                                          'HyperStudy.fit only.'.format(type(tm).__name__))
             program = self._expandProgram(tm._program(om.parameterNames), 1)
-            if len(self.gridSize) > 2 and not all(op[0] in (_abi.OP_GRW, _abi.OP_STATIC, _abi.OP_CHANGEPOINT) and op[4] < 0 for op in program):
-                raise ConfigurationError('Observation models with more than two parameters can be combined with GaussianRandomWalk, '
-                                         'Static and ChangePoint transition models.')
+            self._checkManyParameterProgram(program)
             # every step is a one-step problem resumed at t = -1 (core.py:2164-2165): the op values never change
             op_values = self._opValueMatrix(program, np.asarray(hpv, dtype=float) if len(hpv) > 0 else np.zeros((1, 0)),
                                             timestamps=[0.0], resume_time=-1.0)

@@ -41,6 +41,7 @@
 #include "blhip_chainres.hpp"
 #include "blhip_chain_launch.hpp"
 #include "blhip_nd.hpp"
+#include "blhip_nd_stages.hpp"
 #include "blhip_likprog.hpp"
 
 using namespace blk;

@@ -27,7 +27,7 @@ void do_fit_nd(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, const d
     // ---- shared tables: marginals, prior(s), uniform, the likelihood table -------------------------------------------------------
     size_t msum = 0;
     for (int k = 0; k < p->ndim; ++k) msum += carve_size(8 * (size_t)p->n[k]);
-    ctx->tables.ensure(msum + 3 * carve_size(8 * (size_t)G));
+    ctx->tables.ensure(msum + (p->indep_prior ? 4 : 3) * carve_size(8 * (size_t)G));
     char *cur = ctx->tables.as<char>();
     for (int k = 0; k < p->ndim; ++k) {
         double *dm = carve<double>(cur, (size_t)p->n[k]);
@@ -39,6 +39,11 @@ void do_fit_nd(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, const d
     if (p->reset_prior) HIPCHECK(hipMemcpyAsync(d_reset, p->reset_prior, 8 * (size_t)G, hipMemcpyHostToDevice, st));
     if (p->backward_init) HIPCHECK(hipMemcpyAsync(d_uniform, p->backward_init, sizeof(double) * G, hipMemcpyHostToDevice, st));
     else BL_LAUNCH(fill_kernel, dim3(256), dim3(256), 0, st, d_uniform, G, 1.0 / (double)G);           // beta_T = 1/G, core.py:424-425
+    double *d_indep = nullptr;                        // Independent restarts from it at every step: sum 1, consumed with scale 1 (transitionModels.py:351-360)
+    if (p->indep_prior) {
+        d_indep = carve<double>(cur, (size_t)G);
+        HIPCHECK(hipMemcpyAsync(d_indep, p->indep_prior, 8 * (size_t)G, hipMemcpyHostToDevice, st));
+    }
     ctx->likbuf.ensure(8 * (size_t)T * G);
     double *d_lik = ctx->likbuf.as<double>();
     if (p->obs_model == BLHIP_OM_PROGRAM) build_program_table(ctx, p->ndim, p->n, ng.m, T, p->data_dim, p->data, d_lik);
@@ -64,13 +69,63 @@ void do_fit_nd(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, const d
         d_carry_src = it->second.buf.as<double>();
     }
     const int nblk = (int)std::min<long long>((G + NTHREADS - 1) / NTHREADS, 256);
-    std::vector<int> grw_ops;                       // the random walks of the program, in list order (transitionModels.py:645-649)
-    bool time_dependent = false;
+    // the ops of the program that launch passes, in list order (transitionModels.py:645-649): the random walks (one filter pass each) and
+    // the renormalising stages of blhip_nd_stages.hpp (NotEqual: three passes, Deterministic: one)
+    std::vector<int> pass_ops;
+    bool time_dependent = false, has_stage = false, has_shift = false;
     for (int k = 0; k < p->n_ops; ++k) {
-        if (p->ops[k].kind == BLHIP_OP_GRW) grw_ops.push_back(k);
-        if (p->ops[k].kind == BLHIP_OP_CHANGEPOINT) time_dependent = true;
+        const int kind = p->ops[k].kind;
+        if (kind == BLHIP_OP_GRW || kind == BLHIP_OP_NOTEQUAL || kind == BLHIP_OP_DETERMINISTIC) pass_ops.push_back(k);
+        if (kind == BLHIP_OP_NOTEQUAL || kind == BLHIP_OP_DETERMINISTIC) has_stage = true;
+        if (kind == BLHIP_OP_DETERMINISTIC) has_shift = true;
+        if (kind == BLHIP_OP_CHANGEPOINT || kind == BLHIP_OP_BREAKPOINT || kind == BLHIP_OP_DETERMINISTIC) time_dependent = true;
     }
-    const int npass = (int)grw_ops.size();
+    const int npass = (int)pass_ops.size();
+    // the time stamp the transition INTO step t is evaluated at; false: the step consumes a shared distribution, no transition
+    //   forward: T_fwd(post_{t-1}, ts[t-1]), core.py:411 (step 0 of a resumed fit: at resume_time, core.py:2164-2165)
+    //   backward: T_bwd(beta_{t+1} L_{t+1}, ts[t+1]) = T_fwd(., ts[t+1] - 1), core.py:467, transitionModels.py:316-317
+    auto stamp = [&](int64_t t, bool fwd, double &tau) {
+        if (fwd) {
+            if (t == 0 && !ff.resume) return false;
+            tau = t == 0 ? p->resume_time : p->timestamps[t - 1];
+        } else {
+            if (t == T - 1) return false;
+            tau = p->timestamps[t + 1] - 1.0;
+        }
+        return true;
+    };
+    // active sub-model of a serial model at tau: the number of boundary values at or before it (transitionModels.py:768)
+    auto segment_at = [&](const double *val, double tau) {
+        int seg = 0;
+        for (int k = 0; k < p->n_ops; ++k) {
+            const blhip_op &op = p->ops[k];
+            if ((op.kind == BLHIP_OP_BREAKPOINT || (op.kind == BLHIP_OP_CHANGEPOINT && (op.flags & 1))) && val[k] <= tau) seg++;
+        }
+        return seg;
+    };
+    // a Deterministic model's shift of a step, in grid cells (its 2 T DETERMINISTIC_ARG ops: forward into step 0 .. T-1, backward into them)
+    auto shift_cells = [&](const double *val, int k, int64_t t, bool fwd) { return val[k + 1 + (fwd ? t : T + t)] / p->lattice[p->ops[k].axis]; };
+    // Shifts beyond 12 cells per step leave what a shift-invariant stencil reproduces (SciPy's pre-padding, TapTable::get_shift); the
+    // two-stage kernel for them (blhip_bigshift.hpp) is 1-D / 2-D only.  Refused for every chain before anything is launched.
+    if (has_shift)
+        for (int64_t c = 0; c < n_chains; ++c) {
+            const double *val = op_values + c * p->n_ops;
+            for (int64_t t = 0; t < T; ++t)
+                for (int dir = 0; dir < 2; ++dir) {
+                    double tau = 0.0;
+                    if (!stamp(t, dir == 0, tau)) continue;
+                    const int seg = segment_at(val, tau);
+                    for (int k : pass_ops) {
+                        const blhip_op &op = p->ops[k];
+                        if (op.kind != BLHIP_OP_DETERMINISTIC || (op.segment >= 0 && op.segment != seg)) continue;
+                        const double dd = shift_cells(val, k, t, dir == 0);
+                        if (std::isnan(dd)) fail("chain %lld: Deterministic shift of step %lld is NaN", (long long)c, (long long)t);
+                        if (std::fabs(dd) > 12.0)
+                            fail("chain %lld, step %lld: Deterministic model shifts by %.3g grid cells in one time step; on grids with %d "
+                                 "parameters up to 12 (SciPy's pre-padding) are supported", (long long)c, (long long)t, dd, p->ndim);
+                    }
+                }
+        }
     ChainProgram no_clamp;                           // (the bookkeeping helpers only ask it for clamp modes)
 
     for (int64_t c0 = 0; c0 < n_chains; c0 += Bmax) {
@@ -83,6 +138,11 @@ void do_fit_nd(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, const d
         const size_t nT = (size_t)T * B;
         std::vector<unsigned char> kindF(nT, SRC_PREV), kindB(nT, SRC_PREV);
         std::vector<int> tapF((size_t)std::max(1, npass) * nT, -1), tapB((size_t)std::max(1, npass) * nT, -1);     // [pass][t][b]
+        // (with stages) kind*: where a step's input comes from; stepK*: what the fused kernel is told -- SRC_PREV too when the chain ran a
+        // renormalising stage at the step, whose sums it then reads its scale from; limit: [pass][b] NotEqual's 10**v dV
+        std::vector<unsigned char> stepKF, stepKB;
+        std::vector<double> limit;
+        if (has_stage) { stepKF.assign(nT, SRC_PREV); stepKB.assign(nT, SRC_PREV); limit.assign((size_t)npass * B, 0.0); }
         for (int64_t b = 0; b < B; ++b) {
             const double *val = op_values ? op_values + (c0 + b) * p->n_ops : nullptr;
             std::vector<int> op_tap(p->n_ops, -1);
@@ -91,29 +151,56 @@ void do_fit_nd(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, const d
                     const double ns = val[k] / p->lattice[p->ops[k].axis];                    // transitionModels.py:108
                     if (std::isnan(ns)) fail("chain %lld: GRW sigma is NaN", (long long)(c0 + b));
                     op_tap[k] = ns > 0.0 ? taps.get(p->ops[k].axis, ns) : -1;                // :110-113
+                } else if (p->ops[k].kind == BLHIP_OP_NOTEQUAL) {
+                    for (int q = 0; q < npass; ++q) if (pass_ops[q] == k) limit[(size_t)q * B + b] = std::pow(10.0, val[k]) * dV;      // :468
                 }
-            // the transition into a step, evaluated at time stamp tau (list order; a change point restarts from the reset
-            // distribution and drops what the models before it did, transitionModels.py:300-312)
-            auto run = [&](bool have_tau, double tau, unsigned char &kind, int *tp, size_t stride) {
+            // the transition into a step, evaluated at time stamp tau (list order; only the ops of the active sub-model of a serial
+            // model act, transitionModels.py:768-776; a change point and an Independent model restart from a shared distribution and
+            // drop what the models before them did, :300-312, :351-360) -> true: the chain ran a renormalising stage
+            auto run = [&](double tau, int64_t t, bool fwd, unsigned char &kind, int *tp, size_t stride) {
                 kind = SRC_PREV;
-                for (int q = 0; q < npass; ++q) tp[q * stride] = -1;
+                bool renorm = false;
+                auto restart = [&](unsigned char from) {
+                    kind = from; renorm = false;
+                    for (int q = 0; q < npass; ++q) tp[q * stride] = -1;
+                };
+                restart(SRC_PREV);
+                const int seg = time_dependent ? segment_at(val, tau) : 0;
                 for (int k = 0; k < p->n_ops; ++k) {
                     const blhip_op &op = p->ops[k];
+                    if (op.segment >= 0 && op.segment != seg) continue;
+                    int q = 0;
+                    while (q < npass && pass_ops[q] != k) ++q;
                     if (op.kind == BLHIP_OP_GRW) {
-                        for (int q = 0; q < npass; ++q) if (grw_ops[q] == k) tp[q * stride] = op_tap[k];
-                    } else if (op.kind == BLHIP_OP_CHANGEPOINT && have_tau && tau == val[k]) {
-                        kind = SRC_RESET;
-                        for (int q = 0; q < npass; ++q) tp[q * stride] = -1;
+                        tp[q * stride] = op_tap[k];
+                    } else if (op.kind == BLHIP_OP_CHANGEPOINT && !(op.flags & 1) && time_dependent && tau == val[k]) {
+                        restart(SRC_RESET);
+                    } else if (op.kind == BLHIP_OP_INDEPENDENT) {
+                        restart(SRC_INDEP);
+                    } else if (op.kind == BLHIP_OP_NOTEQUAL) {                                // transitionModels.py:462-471
+                        tp[q * stride] = 0;
+                        renorm = true;
+                    } else if (op.kind == BLHIP_OP_DETERMINISTIC) {                           // transitionModels.py:571-583, :585-602
+                        const double dd = shift_cells(val, k, t, fwd);
+                        if (dd != 0.0) { tp[q * stride] = taps.get_shift(op.axis, dd); renorm = true; }      // (zero shift: the identity)
                     }
                 }
+                if (time_dependent)
+                    for (int k = 0; k < p->n_ops; ++k) {                                      // serial change-points: after the sub-model acted, :801-813
+                        const blhip_op &op = p->ops[k];
+                        if (op.kind == BLHIP_OP_CHANGEPOINT && (op.flags & 1) && tau == val[k]) restart(SRC_RESET);
+                    }
+                return renorm;
             };
             for (int64_t t = 0; t < T; ++t) {
                 const size_t k = (size_t)t * B + b;
-                if (t == 0 && ff.resume) run(true, p->resume_time, kindF[k], &tapF[k], nT);       // continues a carried state (core.py:2164-2165)
-                else if (t == 0) kindF[k] = SRC_PRIOR;                                  // core.py:363
-                else run(time_dependent, time_dependent ? p->timestamps[t - 1] : 0.0, kindF[k], &tapF[k], nT);          // core.py:411
-                if (t == T - 1) kindB[k] = SRC_UNIFORM;
-                else run(time_dependent, time_dependent ? p->timestamps[t + 1] - 1.0 : 0.0, kindB[k], &tapB[k], nT);    // core.py:467, transitionModels.py:316-317
+                double tau = 0.0;
+                bool rnF = false, rnB = false;
+                if (stamp(t, true, tau)) rnF = run(tau, t, true, kindF[k], &tapF[k], nT);
+                else kindF[k] = SRC_PRIOR;                                              // core.py:363
+                if (stamp(t, false, tau)) rnB = run(tau, t, false, kindB[k], &tapB[k], nT);
+                else kindB[k] = SRC_UNIFORM;
+                if (has_stage) { stepKF[k] = rnF ? (unsigned char)SRC_PREV : kindF[k]; stepKB[k] = rnB ? (unsigned char)SRC_PREV : kindB[k]; }
             }
         }
         taps.w.resize(taps.w.size() + 8, 0.0);
@@ -128,6 +215,7 @@ void do_fit_nd(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, const d
         const size_t ntap = taps.off.size() + 1;
         size_t mb = 2 * carve_size(nT) + 2 * carve_size(tapF.size() * 4) + carve_size(taps.w.size() * 8) + 2 * carve_size(ntap * 4) +
                     2 * carve_size(nT * 8) + 3 * carve_size((size_t)B * 8) + carve_size((size_t)B * 8) + carve_size(nT * 8);
+        if (has_stage) mb += carve_size(limit.size() * 8) + 2 * carve_size((size_t)B * nblk * 8) + carve_size((size_t)B * NRED * nblk * 8);
         ctx->meta.ensure(mb);
         char *mc = ctx->meta.as<char>();
         unsigned char *d_kindF = carve<unsigned char>(mc, nT), *d_kindB = carve<unsigned char>(mc, nT);
@@ -138,18 +226,26 @@ void do_fit_nd(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, const d
         const double **d_ptr_state = carve<const double *>(mc, (size_t)B), **d_ptr_tmp0 = carve<const double *>(mc, (size_t)B),
                      **d_ptr_tmp1 = carve<const double *>(mc, (size_t)B);
         double *d_w = carve<double>(mc, (size_t)B), *d_invN = carve<double>(mc, nT);
+        // the stages' scratch (blhip_nd_stages.hpp): NotEqual's limits, block maxima and block sums, the partial sums of a stage's output
+        double *d_limit = nullptr, *d_bmax = nullptr, *d_bsum = nullptr, *d_stage_sums = nullptr;
+        if (has_stage) {
+            d_limit = carve<double>(mc, limit.size()); d_bmax = carve<double>(mc, (size_t)B * nblk); d_bsum = carve<double>(mc, (size_t)B * nblk);
+            d_stage_sums = carve<double>(mc, (size_t)B * NRED * nblk);
+            HIPCHECK(hipMemcpyAsync(d_limit, limit.data(), limit.size() * 8, hipMemcpyHostToDevice, st));
+        }
         // where a step's input lives: the chain's state, or a shared distribution at a restart
         std::vector<const double *> src0F(nT), src0B(nT), pst(B), pt0(B), pt1(B);
         for (int64_t b = 0; b < B; ++b) {
             pst[b] = d_state + (size_t)b * G; pt0[b] = d_tmp[0] + (size_t)b * G; pt1[b] = d_tmp[1] + (size_t)b * G;
             for (int64_t t = 0; t < T; ++t) {
                 const size_t k = (size_t)t * B + b;
-                src0F[k] = kindF[k] == SRC_PREV ? ((t == 0 && ff.resume) ? d_carry_src + (size_t)b * G : pst[b]) : (kindF[k] == SRC_PRIOR ? d_prior : d_reset);
-                src0B[k] = kindB[k] == SRC_PREV ? pst[b] : (kindB[k] == SRC_UNIFORM ? d_uniform : d_reset);
+                src0F[k] = kindF[k] == SRC_PREV ? ((t == 0 && ff.resume) ? d_carry_src + (size_t)b * G : pst[b])
+                                                : (kindF[k] == SRC_PRIOR ? d_prior : (kindF[k] == SRC_INDEP ? d_indep : d_reset));
+                src0B[k] = kindB[k] == SRC_PREV ? pst[b] : (kindB[k] == SRC_UNIFORM ? d_uniform : (kindB[k] == SRC_INDEP ? d_indep : d_reset));
             }
         }
-        HIPCHECK(hipMemcpyAsync(d_kindF, kindF.data(), nT, hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(d_kindB, kindB.data(), nT, hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(d_kindF, (has_stage ? stepKF : kindF).data(), nT, hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(d_kindB, (has_stage ? stepKB : kindB).data(), nT, hipMemcpyHostToDevice, st));
         HIPCHECK(hipMemcpyAsync(d_tapF, tapF.data(), tapF.size() * 4, hipMemcpyHostToDevice, st));
         HIPCHECK(hipMemcpyAsync(d_tapB, tapB.data(), tapB.size() * 4, hipMemcpyHostToDevice, st));
         HIPCHECK(hipMemcpyAsync(d_taps, taps.w.data(), taps.w.size() * 8, hipMemcpyHostToDevice, st));
@@ -170,19 +266,36 @@ void do_fit_nd(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, const d
             const int *tp = (bwd ? d_tapB : d_tapF) + (size_t)t * B;
             const std::vector<int> &htp = bwd ? tapB : tapF;
             int flip = 0;
+            // whose partial sums the fused kernel reads its scale from: the producing step's, or those of the step's last stage
+            const double *ps_scale = ps_prev;
+            int scale_slot = bwd ? 2 : 0;
             for (int q = 0; q < npass; ++q) {
                 bool any = false;
                 for (int64_t b = 0; b < B && !any; ++b) any = htp[(size_t)q * nT + (size_t)t * B + b] >= 0;
                 if (!any) continue;
-                const int ax = p->ops[grw_ops[q]].axis;
-                BL_LAUNCH(bln::filter_axis_kernel, dim3((unsigned)nblk, (unsigned)B), dim3(NTHREADS), 0, st, d_tmp[flip], in, G, ng.n[ax],
-                                   ng.stride[ax], tp + (size_t)q * nT, d_taps, d_off, d_lw);
+                const blhip_op &op = p->ops[pass_ops[q]];
+                const int ax = op.axis;
+                const dim3 grid((unsigned)nblk, (unsigned)B);
+                const int *id = tp + (size_t)q * nT;
+                if (op.kind == BLHIP_OP_GRW) {
+                    BL_LAUNCH(bln::filter_axis_kernel, grid, dim3(NTHREADS), 0, st, d_tmp[flip], in, G, ng.n[ax], ng.stride[ax], id, d_taps, d_off, d_lw);
+                } else if (op.kind == BLHIP_OP_NOTEQUAL) {
+                    BL_LAUNCH(bln::ne_max_kernel, grid, dim3(NTHREADS), 0, st, in, G, id, d_bmax);
+                    BL_LAUNCH(bln::ne_invert_kernel, grid, dim3(NTHREADS), 0, st, d_tmp[flip], in, G, id, d_bmax, d_bsum);
+                    BL_LAUNCH(bln::ne_clamp_kernel, grid, dim3(NTHREADS), 0, st, d_tmp[flip], G, id, d_limit + (size_t)q * B, d_bsum, ps_scale, scale_slot,
+                              d_stage_sums);
+                    ps_scale = d_stage_sums; scale_slot = 0;
+                } else {
+                    BL_LAUNCH(bln::shift_axis_kernel, grid, dim3(NTHREADS), 0, st, d_tmp[flip], in, G, ng.n[ax], ng.stride[ax], id, d_taps, d_off, d_lw,
+                              ps_scale, scale_slot, d_stage_sums);
+                    ps_scale = d_stage_sums; scale_slot = 0;
+                }
                 in = flip ? d_ptr_tmp1 : d_ptr_tmp0;
                 flip ^= 1;
             }
             bln::NdStep Q{};
             Q.g = ng; Q.B = (int)B; Q.T = (int)T; Q.nblk = nblk; Q.srcs = in; Q.kind = (bwd ? d_kindB : d_kindF) + (size_t)t * B;
-            Q.psum_prev = ps_prev; Q.prev_slot = bwd ? 2 : 0; Q.psum_out = ps_out; Q.lik = d_lik + (size_t)t * G; Q.state = d_state;
+            Q.psum_prev = ps_scale; Q.prev_slot = scale_slot; Q.psum_out = ps_out; Q.lik = d_lik + (size_t)t * G; Q.state = d_state;
             Q.post = d_post ? d_post + (size_t)t * G : nullptr; Q.post_stride = (long long)T * G;
             if (bwd) BL_LAUNCH(bln::step_kernel<true>, dim3((unsigned)nblk, (unsigned)B), dim3(NTHREADS), 0, st, Q);
             else BL_LAUNCH(bln::step_kernel<false>, dim3((unsigned)nblk, (unsigned)B), dim3(NTHREADS), 0, st, Q);

@@ -168,11 +168,13 @@ void validate(const blhip_problem *p, int64_t n_chains, const double *op_values)
     if (p->ndim > 2) {            // the plain N-D path (blhip_nd.hpp)
         if (p->obs_model != BLHIP_OM_TABLE && p->obs_model != BLHIP_OM_PROGRAM)
             fail("grids with %d parameters need a caller-evaluated likelihood table (BLHIP_OM_TABLE) or a likelihood program (BLHIP_OM_PROGRAM)", p->ndim);
+        // (the stages of blhip_nd_stages.hpp carry NotEqual and Deterministic; Independent, break-points and serial models are host-side
+        //  bookkeeping of do_fit_nd.  The reference itself refuses AlphaStableRandomWalk beyond two parameters, transitionModels.py:213-215)
         for (int k = 0; k < p->n_ops; ++k) {
-            const blhip_op &op = p->ops[k];
-            const bool ok = op.kind == BLHIP_OP_GRW || op.kind == BLHIP_OP_STATIC || (op.kind == BLHIP_OP_CHANGEPOINT && !(op.flags & 1));
-            if (!ok || op.segment >= 0)
-                fail("grids with %d parameters support GaussianRandomWalk / Static / ChangePoint transition models (op %d has kind %d)", p->ndim, k, op.kind);
+            const int kind = p->ops[k].kind;
+            if (kind == BLHIP_OP_REGIMESWITCH || kind == BLHIP_OP_ALPHASTABLE || kind == BLHIP_OP_BIVARIATE)
+                fail("grids with %d parameters do not support RegimeSwitch / AlphaStableRandomWalk / BivariateRandomWalk transition models "
+                     "(op %d has kind %d)", p->ndim, k, kind);
         }
     }
     for (int k = 0; k < p->ndim; ++k) {

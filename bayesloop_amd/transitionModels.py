@@ -101,11 +101,12 @@ def _device_transition(model, posterior, t, shift=None):
     grid_size = list(study.gridSize)
     if list(x.shape) != grid_size:
         raise ConfigurationError('computeForwardPrior: distribution of shape {} on a grid of shape {}.'.format(list(x.shape), grid_size))
-    if len(grid_size) > 2:
-        raise NotImplementedError('computeForwardPrior on the device is limited to grids with one or two parameters.')
     program = model._program(study.observationModel.parameterNames)
     if program is None:
         raise NotImplementedError('Transition model "{}" has no device program; define computeForwardPrior.'.format(model))
+    if len(grid_size) > 2 and any(op[0] in (_abi.OP_REGIMESWITCH, _abi.OP_ALPHASTABLE, _abi.OP_BIVARIATE) for op in program):
+        raise NotImplementedError('computeForwardPrior of RegimeSwitch, AlphaStableRandomWalk and BivariateRandomWalk on the device is '
+                                  'limited to grids with one or two parameters.')
     s = float(np.sum(x))
     if not (s > 0.0 and np.isfinite(s)):
         raise ConfigurationError('computeForwardPrior: the distribution has no positive finite mass.')

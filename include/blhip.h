@@ -111,7 +111,8 @@ typedef struct {
 typedef struct {
     int32_t        ndim;          /* number of observation-model parameters = grid dimensions (core.py:130-176 builds a
                                      meshgrid over any number): 1 .. BLHIP_MAX_DIM.  3 and more: BLHIP_OM_TABLE / BLHIP_OM_PROGRAM
-                                     models (the reference's SciPy / SymPy / NumPy plug-ins) with GRW / STATIC / CHANGEPOINT ops */
+                                     models (the reference's SciPy / SymPy / NumPy plug-ins) with every op but REGIMESWITCH /
+                                     ALPHASTABLE / BIVARIATE; DETERMINISTIC shifts of at most 12 grid cells per step */
     int32_t        obs_model;     /* BLHIP_OM_*                                                                  */
     int64_t        n[BLHIP_MAX_DIM];          /* grid size per parameter (core.py:157)                           */
     const double  *marginal[BLHIP_MAX_DIM];   /* marginal grid values per parameter, n[k] doubles (core.py:156)  */
