@@ -515,7 +515,8 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
         const bool p1d_now = fused1d && !c1d_now && !resident_failed && ctx->resident_ok && ctx->option("persist1d", 1.0) != 0.0 && T > K &&
                              (long long)tile.nblk * B <= std::min(ctx->num_cus, 256);
         // (the chains of a batch see the same likelihood: tabulated once per batch by the in-kernel function itself, shared by both passes)
-        const bool c1d_table = c1d_now && B >= 4 && !d_lik && (p->obs_model == BLHIP_OM_POISSON || p->obs_model == BLHIP_OM_GAUSSIAN_MEAN);
+        // (rows beyond bl1c::NMAX: the long-row kernel has no likelihood of its own -- the table for any number of chains)
+        const bool c1d_table = c1d_now && (B >= 4 || g.n1 > bl1c::NMAX) && !d_lik && (p->obs_model == BLHIP_OM_POISSON || p->obs_model == BLHIP_OM_GAUSSIAN_MEAN);
         double *d_lik1 = nullptr;
         if (c1d_table) {
             ctx->lik1d.ensure((size_t)T * G * 8);
@@ -1169,7 +1170,7 @@ int blhip_set_option(blhip_ctx *ctx, const char *key, double value) {
     if (std::strcmp(key, "resident_retry_after") == 0) { ctx->resident_retry_after = std::max(1, (int)value); return 0; }
     // (a key the library never reads is an error, not a silent no-op: an A/B run over a removed option measured nothing -- ADVICE r05)
     static const char *const known[] = {
-        "accum_overlap", "carry_partials", "chain1d", "chain1d_clamp", "chain1d_shift", "chain_ax1", "chain_depad", "chain_prof", "chain_resident", "chain_resident_lag",
+        "accum_overlap", "carry_partials", "chain1d", "chain1d_clamp", "chain1d_long", "chain1d_shift", "chain_ax1", "chain_depad", "chain_prof", "chain_resident", "chain_resident_lag",
         "chain_force_fail_batch", "chain_force_fail_stage", "chain_table", "chain_wide", "comm_reduce_mode", "fast", "fast_S", "fold2", "fold2_cp", "fold_force_fail_batch", "fuse1d", "fuse_accumulate", "late_sums", "lik_program", "max_batch",
         "mem_budget_bytes", "mfma", "mfma_S", "mfma_h", "mfma_h_max_cells", "peer_copy_mode", "persist1d", "quiet", "recurrence", "resident",
         "resident_force_abort", "resident_lag", "resident_probe", "resident_probe_force_busy", "resident_probe_interval_s", "resident_probe_timeout_s",

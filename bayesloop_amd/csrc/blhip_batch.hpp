@@ -409,8 +409,13 @@ GeometryPlan plan_geometry(blhip_ctx *ctx, const blhip_problem *p, const Geometr
         // one (all blocks of all chains on the chip at once) ~4 k (K > 1) / ~7 k (K = 1: a hand-off per step) per step.
         const double c1d_mode = ctx->option("chain1d", 1.0);
         if (shift1d) gp.fused1d = true;              // (decided below: without the chain-resident kernel the batch keeps the generic one)
-        if (gp.fused1d && c1d_mode != 0.0 && !resume && !carry && prog.LW1 < g.n1 && g.n1 <= bl1c::NMAX &&
-            bl1c::lds_doubles(g.n1, prog.LW1, shift1d) * 8 <= 150 * 1024) {
+        // (rows of bl1c::NMAX + 1 .. NMAX_LONG cells: the long-row flavour and its lean LDS layout -- option chain1d_long; shorter rows are
+        //  decided by the layout of their own kernel, also where only the lean one would fit them)
+        const bool long_row = g.n1 > bl1c::NMAX;
+        const bool c1d_fits = long_row ? g.n1 <= bl1c::NMAX_LONG && ctx->option("chain1d_long", 1.0) != 0.0 &&
+                                             bl1c::lds_doubles_long(g.n1, prog.LW1, shift1d) * 8 <= 150 * 1024
+                                       : bl1c::lds_doubles(g.n1, prog.LW1, shift1d) * 8 <= 150 * 1024;
+        if (gp.fused1d && c1d_mode != 0.0 && !resume && !carry && prog.LW1 < g.n1 && c1d_fits) {
             // microseconds per time step of the whole batch, fitted to tools/probe.py chain1d (profiles/r04_notes.md): a block's step =
             // 1.5 us + 1.0 ns per cell (likelihood from the shared table; 2.2 ns with Poisson's pow() in the kernel) + 44 ps per cell and
             // tap (the stencil's operand pairs come out of ONE CU's LDS at ~9 per clock), blocks beyond the chip's capacity queue up;
@@ -420,7 +425,10 @@ GeometryPlan plan_geometry(blhip_ctx *ctx, const blhip_problem *p, const Geometr
             const double n = g.n1, lw = prog.LW1;
             // (rows longer than a block: two cells per thread share their operand pairs, 21 ps per cell and tap -- launch_chain1d)
             const double tap_us = g.n1 > bl1c::NT && true ? 2.1e-5 : 4.4e-5;
-            const double est_c1d = (double)((B + cus - 1) / cus) * (1.5 + n * (B >= 4 ? 0.0010 : 0.0022) + n * (2.0 * lw + 1.0) * tap_us);
+            // (long rows, refitted to 18 shapes of 4608 / 8192 cells -- profiles/chain1d_long_notes.md: 1.4 us + 0.82 ns per cell, always from
+            //  the table, + 19.3 ps per cell and tap; the constants above over-estimated those by up to 54 %)
+            const double est_c1d = long_row ? (double)((B + cus - 1) / cus) * (1.4 + n * 0.00082 + n * (2.0 * lw + 1.0) * 1.93e-5)
+                                            : (double)((B + cus - 1) / cus) * (1.5 + n * (B >= 4 ? 0.0010 : 0.0022) + n * (2.0 * lw + 1.0) * tap_us);
             const int nblk_f = (g.n1 + gp.f1_TJ - 1) / gp.f1_TJ;
             const bool p1d_ok = ctx->option("persist1d", 1.0) != 0.0 && (long long)nblk_f * B <= cus && T > gp.fusedK;
             const double est_other = p1d_ok ? 1.7 + 0.04 * lw : 1.5 + (double)B * n * (29.0 + 0.63 * lw) * 1e-6;

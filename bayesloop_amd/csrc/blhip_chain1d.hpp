@@ -6,8 +6,8 @@
 // :372-411 / :434-470) -- and a 1-D distribution is a few KB.  The K-steps-per-launch kernels (blhip_fused1d.hpp) cut a row into blocks of
 // 128 cells that recompute K lw halo cells per side; with the wide walks such studies use (coal mining: sigma / delta = 6.7 on 200
 // points, 33 on 1000: radius 133) K drops to 1 and a pass is T launches of ~6 us each; the persistent variant (blhip_persist1d.hpp) needs
-// all blocks of all chains on the chip at once (<= 256 blocks).  A chain's whole row (<= 4096 cells here) fits one CU's LDS with any
-// halo, so: block = chain, the time loop runs inside the kernel, ONE barrier per step, no hand-off between blocks at all (the
+// all blocks of all chains on the chip at once (<= 256 blocks).  A chain's whole row (<= 4096 cells; up to 8192 in the long-row flavour at the end of this
+// file) fits one CU's LDS with any halo, so: block = chain, the time loop runs inside the kernel, ONE barrier per step, no hand-off between blocks at all (the
 // normaliser is a block sum), any number of chains (blocks beyond the chip's capacity simply queue), any radius < n.
 //
 // Same arithmetic and the same conventions as the launch-per-step kernels with K = 1 (bl1f::advance_cells: centre first, pairs from
@@ -24,12 +24,21 @@ constexpr int NT = 512;            // 8 waves
 constexpr int NW = NT / 64;
 constexpr int NMAX = 4096;         // cells per row: at most 8 per thread (the stored forward row of the next step waits in registers)
 constexpr int CPT = NMAX / NT;
+constexpr int NMAX_LONG = 8192;    // the long-row flavour (chain1d_long_kernel): 16 cells per thread, the grid values stay in HBM / L2
+constexpr int CPT_LONG = NMAX_LONG / NT;
 
 constexpr int NS = 6;              // sums of a step per wave: N, sum p / L, sum c, mean, mass of the shifted / clamped distribution, maximum of the new state (clamps)
 // doubles of LDS: two state buffers with halo, grid values, exp(-lambda) (Poisson), weights, the waves' partial sums (two parities);
 // shift: + the other half of an asymmetric tap set and the spline coefficients of the 12-padded row (two-stage shifts)
 inline size_t lds_doubles(int n, int LW, bool shift = false) {
     return (size_t)2 * (n + 1 + 2 * (LW + 1)) + 2 * (size_t)n + (LW + 3) + 2 * NW * NS + 8 + (shift ? (size_t)LW + 40 + n + 24 + blk::SPLINE_CONST_DOUBLES : 0);
+}
+
+// ... of the long-row flavour: the same without the grid values and exp(-lambda) -- 2 n + 5 LW + 113 doubles (walks, clamps), 3 n + 6 LW + 433
+// with the shift flavour's coefficient row.  Under the 150 KB the host allows: 8192 cells with a radius up to 540, 6163 cells with two-stage
+// shifts (LW = 46).
+inline size_t lds_doubles_long(int n, int LW, bool shift = false) {
+    return lds_doubles(n, LW, shift) - 2 * (size_t)n;
 }
 
 // The likelihood of a 1-D batch is the same for every chain (same data, same grid: only the transition differs).  Poisson's pow() per
@@ -66,15 +75,21 @@ __global__ __launch_bounds__(256) void lik1d_table_kernel(const bl1f::F1Params P
 // slot 5 (backward), the maximum of the new state (NotEqual inverts around it) as slot 6.  Block = chain: every one of these sums is a
 // block sum of the previous step -- no hand-off, which is what the 2-D resident kernels would need for it.  (CL = 1 keeps the arithmetic
 // of the shift-only flavour bit for bit: the published break-point study's borderline chains, DESIGN 6 COAL_NOISE_CHAINS.)
-template <int OM, bool BWD, int M = 1, int CL = 0>
-__global__ __launch_bounds__(NT) void chain1d_kernel(const bl1f::F1Params P) {
+//
+// The body of both kernels below.  NCPT: cells per thread the row may need (the backward pass's prefetch registers).  LEAN: the long-row
+// layout (lds_doubles_long) -- the grid values are read from P.m1 where a sum needs them (a few KB that stay in L2; the means of a pass
+// are one fma per cell) and the likelihood comes from the (T, n) table only, so neither they nor Poisson's exp(-lambda) take LDS.
+// Everything else -- arithmetic, operation order, sum slots, barriers -- is shared, so the two flavours cannot drift apart.
+template <int OM, bool BWD, int M, int CL, int NCPT, bool LEAN>
+__device__ __forceinline__ void chain1d_body(const bl1f::F1Params &P) {
+    static_assert(!LEAN || OM == blk::OM_TABLE, "long rows: the likelihood comes from the shared table");
     constexpr bool SHIFT = CL != 0, CLAMP = CL == 2;
     static_assert(!(CL == 1 && M != 1), "spline shifts: one cell per thread");      // (CL = 2 with M = 2: programs with clamps but WITHOUT Deterministic steps -- the host's choice)
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int n = P.n;
     const int LW = M == 2 ? (P.LW + 1) & ~1 : P.LW;                  // (M = 2: an even halo, so that cell 0 sits in plane 0)
     const int W = M == 2 ? ((n + 1) & ~1) + 2 * LW : n + 2 * LW, PS = W / 2;
-    double *cur = lds, *nxt = lds + W, *g1s = lds + 2 * W, *cAs = g1s + n, *wl = cAs + n;
+    double *cur = lds, *nxt = lds + W, *g1s = lds + 2 * W, *cAs = g1s + n, *wl = LEAN ? g1s : cAs + n;
     double *red = wl + (LW + 2) + (SHIFT ? LW + 40 : 0);     // [2 parities][NW][NS] wave sums of a step
     double *vt = red + 2 * NW * NS + 8;                      // (SHIFT) [n + 24] spline coefficients of the padded row
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -82,9 +97,11 @@ __global__ __launch_bounds__(NT) void chain1d_kernel(const bl1f::F1Params P) {
     blk::StepParams Q{};
     Q.d = P.d; Q.n1 = n; Q.m0 = nullptr; Q.m1 = P.m1;
 
-    for (int j = tid; j < n; j += NT) {
-        g1s[j] = P.m1[j];
-        if (OM == blk::OM_POISSON) cAs[j] = P.colA[j];
+    if (!LEAN) {
+        for (int j = tid; j < n; j += NT) {
+            g1s[j] = P.m1[j];
+            if (OM == blk::OM_POISSON) cAs[j] = P.colA[j];
+        }
     }
     // position e of the extended row (e = LW + cell index) -> slot of the state buffer
     auto slot = [&](int e) { return M == 2 ? (e & 1) * PS + (e >> 1) : e; };
@@ -98,11 +115,11 @@ __global__ __launch_bounds__(NT) void chain1d_kernel(const bl1f::F1Params P) {
     if (SHIFT && wv == 0) blk::spline_consts(vt + n + 24, n + 24, lane);      // (read by wave 0 only: no barrier)
     const int t0 = P.t_first;
     // backward: the stored forward row of the step that runs next waits in registers (requested a step ahead)
-    double al[CPT];
+    double al[NCPT];
     auto cell_of = [&](int q) { return M == 2 ? 2 * (tid + (q >> 1) * NT) + (q & 1) : tid + q * NT; };      // the q-th cell of this thread
     if (BWD) {
 #pragma unroll
-        for (int q = 0; q < CPT; ++q) { const int j = cell_of(q); al[q] = j < n ? post[(long long)t0 * n + j] : 0.0; }
+        for (int q = 0; q < NCPT; ++q) { const int j = cell_of(q); al[q] = j < n ? post[(long long)t0 * n + j] : 0.0; }
     }
     __syncthreads();
 
@@ -190,7 +207,7 @@ __global__ __launch_bounds__(NT) void chain1d_kernel(const bl1f::F1Params P) {
         double aN = 0.0, aS = 0.0, aC = 0.0, aM = 0.0, aU = 0.0, aX = 0.0;
         // the epilogue of one cell: o = the transition's output (scaled)
         auto finish = [&](int j, int q, double o) {
-            const double g1 = g1s[j];
+            const double g1 = LEAN ? 0.0 : g1s[j];             // (LEAN: read from P.m1 where a mean is summed)
             const double L = blk::likelihood<OM>(Q, 0, j, OM == blk::OM_POISSON ? cAs[j] : 0.0, 0.0, g1);
             if (CLAMP) {
                 if (cm == 2) o = o < lim ? lim : o;      // RegimeSwitch after the stencil
@@ -204,21 +221,21 @@ __global__ __launch_bounds__(NT) void chain1d_kernel(const bl1f::F1Params P) {
                 if (P.store) row[j] = a;
                 aN += a;
                 if (CLAMP) aX = fmax(aX, a);
-                if (P.means) aM = fma(a, g1, aM);
+                if (P.means) aM = fma(a, LEAN ? P.m1[j] : g1, aM);
             } else {
                 const double cn = o * L, p = al[q] * o;
                 put(nxt, j, cn);
                 row[j] = p;
                 aN += p; aS += p / L; aC += cn;          // 0/0 -> NaN as numpy (core.py:463)
                 if (CLAMP) aX = fmax(aX, cn);
-                aM = fma(p, g1, aM);
+                aM = fma(p, LEAN ? P.m1[j] : g1, aM);
             }
         };
         if (M == 2) {
             const double *X0 = cur, *X1 = cur + PS;
             const int A = (lw + 1) >> 1;                 // pairs of taps (the weight beyond the radius is zero)
 #pragma unroll
-            for (int g = 0; g < CPT / 2; ++g) {
+            for (int g = 0; g < NCPT / 2; ++g) {
                 const int j0 = 2 * (tid + g * NT);
                 if (j0 < n) {
                     const int s0 = (LW + j0) >> 1;
@@ -240,7 +257,7 @@ __global__ __launch_bounds__(NT) void chain1d_kernel(const bl1f::F1Params P) {
             }
         } else {
 #pragma unroll
-            for (int q = 0; q < CPT; ++q) {
+            for (int q = 0; q < NCPT; ++q) {
                 const int j = tid + q * NT;
                 if (j < n) {
                     const int e = LW + j;
@@ -279,7 +296,7 @@ __global__ __launch_bounds__(NT) void chain1d_kernel(const bl1f::F1Params P) {
         }
         if (BWD && s + 1 < P.T) {                     // the stored row of the next step: a whole step to arrive
 #pragma unroll
-            for (int q = 0; q < CPT; ++q) { const int j = cell_of(q); al[q] = j < n ? post[(long long)(t - 1) * n + j] : 0.0; }
+            for (int q = 0; q < NCPT; ++q) { const int j = cell_of(q); al[q] = j < n ? post[(long long)(t - 1) * n + j] : 0.0; }
         }
         // ---- the step's sums: waves -> LDS (this step's parity); the totals go to the host in a fixed order --------------------------
         aN = blk::wave_sum(aN);
@@ -316,6 +333,20 @@ __global__ __launch_bounds__(NT) void chain1d_kernel(const bl1f::F1Params P) {
         double *d = P.dst + (long long)b * P.dst_stride;
         for (int j = tid; j < n; j += NT) d[j] = cur[slot(LW + j)];
     }
+}
+
+template <int OM, bool BWD, int M = 1, int CL = 0>
+__global__ __launch_bounds__(NT) void chain1d_kernel(const bl1f::F1Params P) {
+    chain1d_body<OM, BWD, M, CL, CPT, false>(P);
+}
+
+// LONG ROWS, NMAX < n <= NMAX_LONG (the reference's anomalous-diffusion example has 5000 grid points; a break-point or regime-switch
+// study refined from 4000 to 5000 points lost every fast path): the same pass with 16 cells per thread and the lean LDS layout.  The
+// likelihood is the batch's (T, n) table for every batch size (the host builds it for Poisson / GaussianMean, also for fewer than four
+// chains), so there is ONE observation-model flavour: (M, CL) in {(2, 0), (1, 1), (1, 2), (2, 2)} x direction.
+template <bool BWD, int M = 1, int CL = 0>
+__global__ __launch_bounds__(NT) void chain1d_long_kernel(const bl1f::F1Params P) {
+    chain1d_body<blk::OM_TABLE, BWD, M, CL, CPT_LONG, true>(P);
 }
 
 }  // namespace bl1c

@@ -324,6 +324,29 @@ void launch_chain1d_om(hipStream_t s, const bl1f::F1Params &P, bool bwd, size_t 
     else launch_chain1d_m<OM, 1>(s, P, bwd, lds);
 }
 
+// rows of more than bl1c::NMAX cells: the long-row flavour (likelihood from the table only), (M, CL) = (2, 0) walks / restarts, (1, 1) spline
+// shifts, (1, 2) shifts and clamps, (2, 2) clamps without a Deterministic step -- the choice of launch_chain1d_shift
+template <int M, int CL>
+void launch_chain1d_long_t(hipStream_t s, const bl1f::F1Params &P, bool bwd, size_t lds) {
+    if (bwd) {
+        arm_kernel(reinterpret_cast<const void *>(&bl1c::chain1d_long_kernel<true, M, CL>));
+        BL_LAUNCH((bl1c::chain1d_long_kernel<true, M, CL>), dim3((unsigned)P.B), dim3(bl1c::NT), lds, s, P);
+    } else {
+        arm_kernel(reinterpret_cast<const void *>(&bl1c::chain1d_long_kernel<false, M, CL>));
+        BL_LAUNCH((bl1c::chain1d_long_kernel<false, M, CL>), dim3((unsigned)P.B), dim3(bl1c::NT), lds, s, P);
+    }
+}
+void launch_chain1d_long(hipStream_t s, int om, const bl1f::F1Params &P, bool bwd) {
+    if (om != BLHIP_OM_TABLE || !P.lik) fail("internal: chain-resident 1-D path, %d cells: no likelihood table (observation model %d)", P.n, om);
+    if (P.n > bl1c::NMAX_LONG) fail("internal: chain-resident 1-D path: %d cells", P.n);
+    const size_t lds = bl1c::lds_doubles_long(P.n, P.LW, P.cmode != nullptr) * sizeof(double);
+    if (!P.cmode) launch_chain1d_long_t<2, 0>(s, P, bwd, lds);
+    else if (!P.limit) launch_chain1d_long_t<1, 1>(s, P, bwd, lds);
+    else if (P.no_shift) launch_chain1d_long_t<2, 2>(s, P, bwd, lds);
+    else launch_chain1d_long_t<1, 2>(s, P, bwd, lds);
+    HIPCHECK(hipGetLastError());
+}
+
 // the (T, n) likelihood table every chain of a 1-D batch shares (bl1c::lik1d_table_kernel: the in-kernel function, evaluated once)
 void build_lik1d_table(hipStream_t s, int om, const bl1f::F1Params &P, double *out) {
     const dim3 grid((unsigned)std::min(16, (P.n + 255) / 256), (unsigned)P.T);
@@ -335,6 +358,7 @@ void build_lik1d_table(hipStream_t s, int om, const bl1f::F1Params &P, double *o
 
 // cells per thread: 2 adjacent ones (sharing their stencil operands) for rows longer than a block, else 1 (option chain1d_pair: 0 / 1 force)
 void launch_chain1d(hipStream_t s, int om, const bl1f::F1Params &P, bool bwd, int pair_mode) {
+    if (P.n > bl1c::NMAX) return launch_chain1d_long(s, om, P, bwd);
     const size_t lds = bl1c::lds_doubles(P.n, P.LW, P.cmode != nullptr) * sizeof(double);
     const int m = pair_mode == 0 ? 1 : ((pair_mode == 1 || P.n > bl1c::NT) ? 2 : 1);
     switch (om) {
