@@ -2,7 +2,26 @@
 // it uses (FitFlags, TapTable, BatchOutcome, forward_ / backward_bookkeeping, fold_accumulate, keep_posterior, write_results).
 #pragma once
 
-// ---- grids with 3 and 4 parameters: the plain formulation (blhip_nd.hpp) ---------------------------------------------------------------
+// the chain-resident kernel of a batch (blhip_chain_nd.hpp): one block per chain, the small or the large block by the LDS need
+template <int NT>
+void launch_chain_nd_t(hipStream_t s, const bln::ChainNd &Q, bool bwd, size_t lds) {
+    if (bwd) {
+        arm_kernel(reinterpret_cast<const void *>(&bln::chain_nd_kernel<true, NT>));
+        BL_LAUNCH((bln::chain_nd_kernel<true, NT>), dim3((unsigned)Q.B), dim3(NT), lds, s, Q);
+    } else {
+        arm_kernel(reinterpret_cast<const void *>(&bln::chain_nd_kernel<false, NT>));
+        BL_LAUNCH((bln::chain_nd_kernel<false, NT>), dim3((unsigned)Q.B), dim3(NT), lds, s, Q);
+    }
+}
+void launch_chain_nd(hipStream_t s, const bln::ChainNd &Q, bool bwd, int threads, size_t lds) {
+    if (lds > bln::CHAIN_ND_LDS_LIMIT || Q.g.G > (long long)threads * bln::chain_nd_cpt(threads))
+        fail("internal: chain-resident N-D kernel: %zu bytes of LDS, %lld cells on %d threads", lds, Q.g.G, threads);
+    if (threads == bln::CHAIN_ND_NT_SMALL) launch_chain_nd_t<bln::CHAIN_ND_NT_SMALL>(s, Q, bwd, lds);
+    else launch_chain_nd_t<bln::CHAIN_ND_NT_LARGE>(s, Q, bwd, lds);
+    HIPCHECK(hipGetLastError());
+}
+
+// ---- grids with 3 and 4 parameters: the plain formulation (blhip_nd.hpp), the chain-resident kernel for batches (blhip_chain_nd.hpp) -----
 void do_fit_nd(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, const double *op_values, const double *log_w, uint32_t flags,
                blhip_result *res) {
     HIPCHECK(hipSetDevice(ctx->device));
@@ -127,6 +146,12 @@ void do_fit_nd(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, const d
                 }
         }
     ChainProgram no_clamp;                           // (the bookkeeping helpers only ask it for clamp modes)
+    // the chain-resident kernel (blhip_chain_nd.hpp) takes a batch of walks and restarts that is neither resumed nor carried; option
+    // chain_nd: 0 off, 1 the batches the cost model gives it (at least CHAIN_ND_MIN_CHAINS chains), 2 wherever it fits
+    const int chain_nd_opt = (int)ctx->option("chain_nd", 1.0);
+    const bool chain_nd_program = !has_stage && !ff.resume && !ff.carry && npass <= bln::CHAIN_ND_MAXPASS;
+    long long n_sum = 0;
+    for (int k = 0; k < p->ndim; ++k) n_sum += p->n[k];
 
     for (int64_t c0 = 0; c0 < n_chains; c0 += Bmax) {
         const int64_t B = std::min<int64_t>(Bmax, n_chains - c0);
@@ -204,12 +229,34 @@ void do_fit_nd(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, const d
             }
         }
         taps.w.resize(taps.w.size() + 8, 0.0);
+        int lw_max = 0;
+        for (int v : taps.lw) lw_max = std::max(lw_max, v);
+        // the walks that have a kernel somewhere in the batch, and the taps of its slowest chain (the cost model's W)
+        int walks_on = 0, W_taps = 0;
+        bool beyond_axis = false;                     // a walk wider than its axis: the kernel's multi-period reflection
+        // (only a program without stages is asked: there every pass is a walk and every id >= 0 a tap set of the table -- NotEqual's
+        //  passes carry a flag, not an id, and have no axis)
+        for (int q = 0; chain_nd_program && q < npass; ++q) {
+            int lw_q = 0;
+            for (size_t k = 0; k < nT; ++k) {
+                const int f = tapF[(size_t)q * nT + k], r = tapB[(size_t)q * nT + k];
+                if (f >= 0) lw_q = std::max(lw_q, taps.lw[f]);
+                if (r >= 0) lw_q = std::max(lw_q, taps.lw[r]);
+            }
+            if (lw_q > 0) { walks_on += 1; W_taps += 2 * lw_q + 1; }
+            if (lw_q > ng.n[p->ops[pass_ops[q]].axis]) beyond_axis = true;
+        }
+        const bool chain_nd = bln::chain_nd_route(chain_nd_opt, chain_nd_program && bln::chain_nd_fits(G, lw_max, npass, n_sum), G, B, walks_on, W_taps, beyond_axis,
+                                                  bln::chain_nd_threads(G, lw_max, npass, n_sum), std::min(ctx->num_cus, 256));
+        const int nb = chain_nd ? 1 : nblk;          // partial sums per (step, chain, slot): the resident kernel writes block totals
+        if (chain_nd) ctx->timing.fwd_kernel_variant = ctx->timing.bwd_kernel_variant = 10;
         // ---- device buffers ----------------------------------------------------------------------------------------------------------
-        ctx->state.ensure((size_t)3 * B * G * 8);
+        // (a chain-resident batch keeps its state in LDS: no state / scratch arrays, no tables of where a step's input lives)
+        if (!chain_nd) ctx->state.ensure((size_t)3 * B * G * 8);
         double *d_state = ctx->state.as<double>(), *d_tmp[2] = {d_state + (size_t)B * G, d_state + (size_t)2 * B * G};
         double *d_post = nullptr;
         if (!ff.evidence_only) { ctx->post.ensure((size_t)B * T * G * 8); d_post = ctx->post.as<double>(); }
-        const size_t psz = (size_t)T * B * NRED * nblk;
+        const size_t psz = (size_t)T * B * NRED * nb;
         ctx->psumF.ensure(psz * 8); ctx->redF.ensure(nT * NRED * 8);
         if (ff.full) { ctx->psumB.ensure(psz * 8); ctx->redB.ensure(nT * NRED * 8); }
         const size_t ntap = taps.off.size() + 1;
@@ -234,8 +281,8 @@ void do_fit_nd(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, const d
             HIPCHECK(hipMemcpyAsync(d_limit, limit.data(), limit.size() * 8, hipMemcpyHostToDevice, st));
         }
         // where a step's input lives: the chain's state, or a shared distribution at a restart
-        std::vector<const double *> src0F(nT), src0B(nT), pst(B), pt0(B), pt1(B);
-        for (int64_t b = 0; b < B; ++b) {
+        std::vector<const double *> src0F(chain_nd ? 0 : nT), src0B(chain_nd ? 0 : nT), pst(B), pt0(B), pt1(B);
+        for (int64_t b = 0; !chain_nd && b < B; ++b) {
             pst[b] = d_state + (size_t)b * G; pt0[b] = d_tmp[0] + (size_t)b * G; pt1[b] = d_tmp[1] + (size_t)b * G;
             for (int64_t t = 0; t < T; ++t) {
                 const size_t k = (size_t)t * B + b;
@@ -253,11 +300,13 @@ void do_fit_nd(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, const d
             HIPCHECK(hipMemcpyAsync(d_off, taps.off.data(), taps.off.size() * 4, hipMemcpyHostToDevice, st));
             HIPCHECK(hipMemcpyAsync(d_lw, taps.lw.data(), taps.lw.size() * 4, hipMemcpyHostToDevice, st));
         }
-        HIPCHECK(hipMemcpyAsync(d_src0F, src0F.data(), nT * 8, hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(d_src0B, src0B.data(), nT * 8, hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(d_ptr_state, pst.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(d_ptr_tmp0, pt0.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(d_ptr_tmp1, pt1.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
+        if (!chain_nd) {
+            HIPCHECK(hipMemcpyAsync(d_src0F, src0F.data(), nT * 8, hipMemcpyHostToDevice, st));
+            HIPCHECK(hipMemcpyAsync(d_src0B, src0B.data(), nT * 8, hipMemcpyHostToDevice, st));
+            HIPCHECK(hipMemcpyAsync(d_ptr_state, pst.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
+            HIPCHECK(hipMemcpyAsync(d_ptr_tmp0, pt0.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
+            HIPCHECK(hipMemcpyAsync(d_ptr_tmp1, pt1.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
+        }
         sync_stream(ctx, st);
 
         // one time step: the passes of the transition, then the fused elementwise kernel
@@ -301,7 +350,7 @@ void do_fit_nd(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, const d
             else BL_LAUNCH(bln::step_kernel<false>, dim3((unsigned)nblk, (unsigned)B), dim3(NTHREADS), 0, st, Q);
         };
         double *d_psF = ctx->psumF.as<double>();
-        const size_t per_step = (size_t)B * NRED * nblk;
+        const size_t per_step = (size_t)B * NRED * nb;
         float ms = 0;
         // BLHIP_RESUME: the carried states are normalised -- the "partial sums of the step before" add up to 1
         const double *d_unit = nullptr;
@@ -313,18 +362,31 @@ void do_fit_nd(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, const d
             sync_stream(ctx, st);
             d_unit = ctx->unit.as<double>();
         }
+        // one pass of the chain-resident kernel: every step of every chain of the batch in one launch
+        auto chain_pass = [&](bool bwd, double *ps) {
+            bln::ChainNd Q{};
+            Q.g = ng; Q.B = (int)B; Q.T = (int)T; Q.npass = npass;
+            for (int q = 0; q < npass; ++q) { const int ax = p->ops[pass_ops[q]].axis; Q.pass_n[q] = ng.n[ax]; Q.pass_inner[q] = (int)ng.stride[ax]; }
+            Q.tap_slot = lw_max + 1;
+            Q.kind = bwd ? d_kindB : d_kindF; Q.tap = bwd ? d_tapB : d_tapF; Q.taps = d_taps; Q.tap_off = d_off; Q.tap_lw = d_lw;
+            Q.shared[SRC_PREV] = nullptr; Q.shared[SRC_PRIOR] = d_prior; Q.shared[SRC_RESET] = d_reset; Q.shared[SRC_UNIFORM] = d_uniform;
+            Q.shared[SRC_INDEP] = d_indep;
+            Q.lik = d_lik; Q.post = d_post; Q.post_stride = (long long)T * G; Q.psum = ps;
+            launch_chain_nd(st, Q, bwd, bln::chain_nd_threads(G, lw_max, npass, n_sum), bln::chain_nd_lds_doubles(G, lw_max, npass, n_sum) * sizeof(double));
+        };
         // ---- forward pass (core.py:372-411) ---------------------------------------------------------------------------------------------
         HIPCHECK(hipEventRecord(ev[0], st));
-        for (int64_t t = 0; t < T; ++t) step(false, t, t > 0 ? d_psF + (size_t)(t - 1) * per_step : (d_unit ? d_unit : d_psF), d_psF + (size_t)t * per_step);
+        if (chain_nd) chain_pass(false, d_psF);
+        else for (int64_t t = 0; t < T; ++t) step(false, t, t > 0 ? d_psF + (size_t)(t - 1) * per_step : (d_unit ? d_unit : d_psF), d_psF + (size_t)t * per_step);
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipEventRecord(ev[1], st));
-        BL_LAUNCH(reduce_partials_kernel, dim3((unsigned)(nT * NRED)), dim3(NTHREADS), 0, st, d_psF, ctx->redF.as<double>(), nblk, 0);      // (0: every slot is a sum -- slot 6 is the 4th parameter's mean here)
+        BL_LAUNCH(reduce_partials_kernel, dim3((unsigned)(nT * NRED)), dim3(NTHREADS), 0, st, d_psF, ctx->redF.as<double>(), nb, 0);      // (0: every slot is a sum -- slot 6 is the 4th parameter's mean here)
         ctx->pinF.ensure(nT * NRED * 8);
         double *redF = ctx->pinF.as<double>();
         HIPCHECK(hipMemcpyAsync(redF, ctx->redF.p, nT * NRED * 8, hipMemcpyDeviceToHost, st));
         sync_stream(ctx, st);
         HIPCHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        ctx->timing.forward_ms += ms; ctx->timing.forward_launches += T;
+        ctx->timing.forward_ms += ms; ctx->timing.forward_launches += chain_nd ? 1 : T;
         BatchOutcome O;
         forward_bookkeeping(p, no_clamp, redF, B, dV, false, 1, ff.evidence_only, ff.forward_only, O);
         O.invN.assign(nT, 0.0);
@@ -332,16 +394,17 @@ void do_fit_nd(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, const d
         if (ff.full) {
             double *d_psB = ctx->psumB.as<double>();
             HIPCHECK(hipEventRecord(ev[2], st));
-            for (int64_t t = T - 1; t >= 0; --t) step(true, t, t < T - 1 ? d_psB + (size_t)(t + 1) * per_step : d_psB, d_psB + (size_t)t * per_step);
+            if (chain_nd) chain_pass(true, d_psB);
+            else for (int64_t t = T - 1; t >= 0; --t) step(true, t, t < T - 1 ? d_psB + (size_t)(t + 1) * per_step : d_psB, d_psB + (size_t)t * per_step);
             HIPCHECK(hipGetLastError());
             HIPCHECK(hipEventRecord(ev[3], st));
-            BL_LAUNCH(reduce_partials_kernel, dim3((unsigned)(nT * NRED)), dim3(NTHREADS), 0, st, d_psB, ctx->redB.as<double>(), nblk, 0);
+            BL_LAUNCH(reduce_partials_kernel, dim3((unsigned)(nT * NRED)), dim3(NTHREADS), 0, st, d_psB, ctx->redB.as<double>(), nb, 0);
             ctx->pinB.ensure(nT * NRED * 8);
             double *redB = ctx->pinB.as<double>();
             HIPCHECK(hipMemcpyAsync(redB, ctx->redB.p, nT * NRED * 8, hipMemcpyDeviceToHost, st));
             sync_stream(ctx, st);
             HIPCHECK(hipEventElapsedTime(&ms, ev[2], ev[3]));
-            ctx->timing.backward_ms += ms; ctx->timing.backward_launches += T;
+            ctx->timing.backward_ms += ms; ctx->timing.backward_launches += chain_nd ? 1 : T;
             backward_bookkeeping(p, no_clamp, redF, redB, B, dV, false, -1, O);
         } else if (ff.forward_only) {
             for (int64_t b = 0; b < B; ++b)
