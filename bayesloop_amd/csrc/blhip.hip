@@ -23,6 +23,7 @@
 #include <mutex>
 #include <set>
 #include <string>
+#include <string_view>
 #include <system_error>
 #include <chrono>
 #include <thread>
@@ -40,6 +41,7 @@
 #include "blhip_resident.hpp"
 #include "blhip_chainres.hpp"
 #include "blhip_chain_launch.hpp"
+#include "blhip_chainclamp_plan.hpp"
 #include "blhip_nd.hpp"
 #include "blhip_nd_stages.hpp"
 #include "blhip_chain_nd.hpp"
@@ -292,6 +294,8 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
             FP.shared[SRC_PREV] = nullptr; FP.shared[SRC_PRIOR] = d_prior; FP.shared[SRC_RESET] = d_reset;
             FP.shared[SRC_UNIFORM] = d_uniform; FP.shared[SRC_INDEP] = d_indep; P.shared[SRC_INDEP] = d_indep; FP.taps = d_taps; FP.tap_off = d_off; FP.tap_lw = d_lw;
             FP.m0 = d_m0; FP.m1 = d_m1; FP.colA = d_colA; FP.colB = d_colB; FP.prev_nblk = tile.nblk;
+        }
+        if (fast || gp.fast_but_clamp) {      // (fast_but_clamp: only step0 / use_rec are read, by the chain-resident clamp kernels' setup)
             // likelihood recurrence along rows needs an equally spaced row axis (to rounding)
             const double *m0h = p->marginal[0];
             const double step = (m0h[g.n0 - 1] - m0h[0]) / (double)(g.n0 - 1);
@@ -313,7 +317,7 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
         E.chain_means = res && res->posterior_mean;
         E.overlap_acc = overlap_acc;
         E.tr = &tr;
-        E.fold_ev = &fold_ev; E.bi = bi; E.allow_chainres = bi > fallback_until;
+        E.fold_ev = &fold_ev; E.bi = bi; E.allow_chainres = bi > fallback_until; E.fast_but_clamp = gp.fast_but_clamp;
         ResidentRun RR;
         RR.setup(E, n_chains, fast, FP.use_rec != 0, psz);
         ChainRun CR;
@@ -661,7 +665,7 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
             if (!RR.forward_ok(E, redF)) { resident_failed = true; return false; }
         }
         if (cres_now) {
-            ctx->timing.fwd_kernel_variant = 6;
+            ctx->timing.fwd_kernel_variant = CR.clamp ? blcp::VARIANT : 6;
             if (!CR.forward_ok(E, redF)) { resident_failed = true; return false; }
             tr.mark("  forward_ok");
         }
@@ -745,7 +749,7 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
                 if (resident_gave_up(ctx, st, d_abort1)) { resident_failed = true; return false; }
             }
             if (cres_now) {
-                ctx->timing.bwd_kernel_variant = 6;
+                ctx->timing.bwd_kernel_variant = CR.clamp ? blcp::VARIANT : 6;
                 if (!CR.backward_ok(E, redB)) { resident_failed = true; return false; }
                 tr.mark("  backward_ok");
                 if (CR.fused && !CR.fold(E, redB, fold_ev)) { resident_failed = true; return false; }
@@ -915,17 +919,26 @@ int blhip_abi_version(void) { return BLHIP_ABI_VERSION; }
 
 int64_t blhip_kernel_census(char *buf, int64_t cap) {
     try {
-        std::vector<std::pair<std::string, unsigned long long>> rows;
+        // (the names live in ONE arena and the temporaries are reused: a string of its own per kernel was ~1500 small heap blocks allocated
+        //  and freed per call -- the tests take a census around every fit)
+        struct Row { size_t off, len; unsigned long long launches; };
+        std::vector<Row> rows;
+        std::string arena, name;
+        arena.reserve((size_t)1 << 17);
+        char *dm = nullptr;
+        size_t dmlen = 0;
+        struct FreeDm { char *&p; ~FreeDm() { std::free(p); } } free_dm{dm};
+        const std::string pre = "blreg::Site<&(", post = ")>";
         for (blreg::Entry *e = blreg::head().load(std::memory_order_acquire); e; e = e->next) {
             // typeid name of blreg::Site<&kernel>: demangled "blreg::Site<&blc::chain_kernel<4, 1, false, false, false, false>(blc::ChainParams)>"
             int status = 0;
-            char *dm = abi::__cxa_demangle(e->mangled, nullptr, nullptr, &status);
-            std::string name = (status == 0 && dm) ? dm : (e->mangled ? e->mangled : "?");
-            std::free(dm);
+            char *r = abi::__cxa_demangle(e->mangled, dm, &dmlen, &status);      // (dm: malloc'ed, grown by the demangler as needed)
+            if (r) dm = r;
+            name.assign((status == 0 && r) ? r : (e->mangled ? e->mangled : "?"));
             // -> "blreg::Site<&(void blc::chain_kernel<10, 1, false, false, false, false>(blc::ChainParams))>": keep the kernel with its template arguments
-            const std::string pre = "blreg::Site<&(", post = ")>";
             if (name.size() > pre.size() + post.size() && name.compare(0, pre.size(), pre) == 0 && name.compare(name.size() - post.size(), post.size(), post) == 0) {
-                name = name.substr(pre.size(), name.size() - pre.size() - post.size());
+                name.erase(name.size() - post.size());
+                name.erase(0, pre.size());
                 if (name.compare(0, 5, "void ") == 0) name.erase(0, 5);
                 if (!name.empty() && name.back() == ')') {            // the parameter list: the last top-level parenthesis group
                     int depth = 0;
@@ -935,12 +948,22 @@ int64_t blhip_kernel_census(char *buf, int64_t cap) {
                     }
                 }
             }
-            else if (name.compare(0, 13, "blreg::Site<&") == 0 && name.back() == '>') name = name.substr(13, name.size() - 14);      // (a kernel that is no template)
-            rows.emplace_back(name, e->launches.load(std::memory_order_relaxed));
+            else if (name.compare(0, 13, "blreg::Site<&") == 0 && name.back() == '>') { name.erase(name.size() - 1); name.erase(0, 13); }      // (a kernel that is no template)
+            rows.push_back(Row{arena.size(), name.size(), e->launches.load(std::memory_order_relaxed)});
+            arena += name;
         }
-        std::sort(rows.begin(), rows.end());
+        auto view = [&](const Row &r) { return std::string_view(arena.data() + r.off, r.len); };
+        std::sort(rows.begin(), rows.end(), [&](const Row &a, const Row &b) { const int c = view(a).compare(view(b)); return c != 0 ? c < 0 : a.launches < b.launches; });
         std::string out;
-        for (const auto &r : rows) out += std::to_string(r.second) + "\t" + r.first + "\n";
+        out.reserve(arena.size() + 24 * rows.size());
+        for (const Row &r : rows) {
+            char num[24];
+            const int nn = std::snprintf(num, sizeof num, "%llu", r.launches);
+            out.append(num, (size_t)nn);
+            out.push_back('\t');
+            out.append(arena, r.off, r.len);
+            out.push_back('\n');
+        }
         if (buf && cap > 0) {
             const size_t n = std::min<size_t>((size_t)cap - 1, out.size());
             std::memcpy(buf, out.data(), n);
@@ -1032,7 +1055,15 @@ int blhip_host_unlag(int scheme, double *sums, int64_t T, int lag, const unsigne
     try {
         std::vector<double> red((size_t)T * NRED, 0.0), rowsum, scales;
         for (int64_t t = 0; t < T; ++t) red[(size_t)t * NRED] = sums[t];
-        const bool ok = scheme == 0 ? resident_unlag(red.data(), T, lag, rowsum) : chain_unlag(red.data(), T, lag, rowsum, 1, 0, &scales, kinds);
+        // (scheme 2: bit 6 of a step's kind marks a clamped step -- exact scale; the other bits are its source kind as in scheme 1)
+        std::vector<unsigned char> src, clamped;
+        if (scheme == 2 && kinds) {
+            src.resize((size_t)T); clamped.resize((size_t)T);
+            for (int64_t t = 0; t < T; ++t) { src[t] = kinds[t] & 0x3f; clamped[t] = (kinds[t] & 0x40) ? 1 : 0; }
+        }
+        const bool ok = scheme == 0 ? resident_unlag(red.data(), T, lag, rowsum)
+                      : (scheme == 2 && kinds ? chain_unlag(red.data(), T, lag, rowsum, 1, 0, &scales, src.data(), 0, clamped.data())
+                                              : chain_unlag(red.data(), T, lag, rowsum, 1, 0, &scales, kinds));
         if (!ok) return 1;
         for (int64_t t = 0; t < T; ++t) sums[t] = red[(size_t)t * NRED];
         if (scales_out)
@@ -1171,7 +1202,7 @@ int blhip_set_option(blhip_ctx *ctx, const char *key, double value) {
     if (std::strcmp(key, "resident_retry_after") == 0) { ctx->resident_retry_after = std::max(1, (int)value); return 0; }
     // (a key the library never reads is an error, not a silent no-op: an A/B run over a removed option measured nothing -- ADVICE r05)
     static const char *const known[] = {
-        "accum_overlap", "carry_partials", "chain1d", "chain1d_clamp", "chain1d_long", "chain1d_shift", "chain_ax1", "chain_depad", "chain_prof", "chain_resident", "chain_resident_lag",
+        "accum_overlap", "carry_partials", "chain1d", "chain1d_clamp", "chain1d_long", "chain1d_shift", "chain_ax1", "chain_clamp", "chain_depad", "chain_prof", "chain_resident", "chain_resident_lag",
         "chain_force_fail_batch", "chain_force_fail_stage", "chain_nd", "chain_table", "chain_wide", "comm_reduce_mode", "fast", "fast_S", "fold2", "fold2_cp", "fold_force_fail_batch", "fuse1d", "fuse_accumulate", "late_sums", "lik_program", "max_batch",
         "mem_budget_bytes", "mfma", "mfma_S", "mfma_h", "mfma_h_max_cells", "peer_copy_mode", "persist1d", "quiet", "recurrence", "resident",
         "resident_force_abort", "resident_lag", "resident_probe", "resident_probe_force_busy", "resident_probe_interval_s", "resident_probe_timeout_s",

@@ -349,6 +349,7 @@ struct GeometryPlan {
     bool shift1d = false;        // the chain-resident 1-D kernel's flavours with spline shifts (Deterministic steps) / clamps (RegimeSwitch, NotEqual)
     bool clamp1d = false;        // ... the one with clamps (CL = 2)
     bool fast = false, fused1d = false, use_mfma = false;
+    bool fast_but_clamp = false;  // fast in everything but ChainProgram::has_clamp, with a walk on the first parameter only (blc::chain_clamp_kernel's candidates)
     bool chain1d = false;         // 1-D batches: one block per chain runs the whole pass (blhip_chain1d.hpp); bookkeeping of a K = 1 fused pass
     bool wideH = false;           // axis-1 walks wider than the fused kernels' halo: row filter as a pre-pass per step (blhip_hwide.hpp)
     bool wideV = false;           // axis-0 walks wider than the matrix-pipe kernels' largest band: column filter as a pre-pass, no stencil left
@@ -371,6 +372,8 @@ GeometryPlan plan_geometry(blhip_ctx *ctx, const blhip_problem *p, const Geometr
                       ctx->option("fast", 1.0) != 0.0 && !prog.has_clamp && (prog.LW0 <= FAST_R0_MAX || wide_v) &&
                       (prog.LW1 <= blf::R1MAX || wide_h_ok) &&
                       g.n0 >= (wide_v ? 0 : ((prog.LW0 + 7) / 8) * 8) + 2 * blf::CH && g.n1 >= 2 * blf::R1MAX && d <= blf::DMAX;
+    gp.fast_but_clamp = p->ndim == 2 && p->obs_model == BLHIP_OM_GAUSSIAN && ctx->option("fast", 1.0) != 0.0 && prog.has_clamp &&
+                        prog.LW0 <= FAST_R0_MAX && prog.LW1 == 0 && g.n0 >= ((prog.LW0 + 7) / 8) * 8 + 2 * blf::CH && g.n1 >= 2 * blf::R1MAX && d <= blf::DMAX;
     gp.wideV = gp.fast && wide_v;
     gp.wideH = gp.fast && (prog.LW1 > blf::R1MAX || (gp.wideV && prog.LW1 > 0));       // (with a column pre-pass every filter runs as a pre-pass)
     // Chains of such a batch WITHOUT an axis-1 filter (a hyper-grid that includes the width 0) skip the pre-pass: it would be a copy.

@@ -26,8 +26,10 @@ bool resident_unlag(double *redF, int64_t T, int lag, std::vector<double> &rowsu
 // s_k = S_(k-lag-1) s_(k-lag) / S_(k-lag)  (1 while k < lag; S_(-1) = 1).
 // kinds (may be null): a step whose source kind is not SRC_PREV consumed a distribution of known mass instead of the previous
 // state: its normaliser is S_k / s_k.
+// clamped (may be null; blhip_chainclamp.hpp): a step whose entry is not 0 ran at the EXACT scale s_k = 1 / S_(k-1) -- it waited for that
+// sum -- and the lagged rule of the steps behind it reads that scale like any other.
 bool chain_unlag(double *redF, int64_t T, int lag, std::vector<double> &rowsum, int64_t B, int64_t b, std::vector<double> *scales = nullptr,
-                 const unsigned char *kinds = nullptr, int64_t t0 = 0) {
+                 const unsigned char *kinds = nullptr, int64_t t0 = 0, const unsigned char *clamped = nullptr) {
     // t0 > 0 (blc::ChainParams::skip_prefix): the chain's own pass began at step t0 -- the rows before it are another chain's (same
     // values, that chain's scale history), the scale history of the rows from t0 on starts there (s = 1 for lag steps, S_(t0 - 1) := 1)
     rowsum.assign(T, 0.0);
@@ -40,6 +42,7 @@ bool chain_unlag(double *redF, int64_t T, int lag, std::vector<double> &rowsum, 
         if (!(St > 1e-150 && St < 1e150)) return false;
         const int64_t base = t >= t0 ? t0 : 0;                                 // first step of the scale history this step belongs to
         if (t - base >= lag) s[t] = (t - lag - 1 >= base ? rowsum[t - lag - 1] : 1.0) * s[t - lag] / rowsum[t - lag];
+        if (clamped && t > 0 && clamped[(size_t)t * B + b]) s[t] = 1.0 / rowsum[t - 1];
         const bool fresh = t == 0 || (kinds && kinds[(size_t)t * B + b] != SRC_PREV);
         const double norm = fresh ? St / s[t] : St / (rowsum[t - 1] * s[t]);
         double *r = &redF[((size_t)t * B + b) * NRED];
@@ -53,7 +56,7 @@ bool chain_unlag(double *redF, int64_t T, int lag, std::vector<double> &rowsum, 
 // read and rewritten step by step over all chains, the recurrence in between runs on the gathered rows.  Same operations per chain, same
 // order: bit-identical to chain_unlag.  -> index of the first chain that failed, or -1.
 int64_t chain_unlag_batch(double *redF, int64_t T, int lag, int64_t B, std::vector<std::vector<double>> &rowsum, std::vector<std::vector<double>> &scales,
-                          const unsigned char *kinds, const int *t0s) {
+                          const unsigned char *kinds, const int *t0s, const unsigned char *clamped = nullptr) {
     rowsum.assign(B, std::vector<double>());
     scales.assign(B, std::vector<double>());
     for (int64_t b = 0; b < B; ++b) { rowsum[b].resize(T); scales[b].assign(T, 1.0); }
@@ -71,6 +74,7 @@ int64_t chain_unlag_batch(double *redF, int64_t T, int lag, int64_t B, std::vect
             if (!(St > 1e-150 && St < 1e150)) return b;
             const int64_t base = t >= t0 ? t0 : 0;
             if (t - base >= lag) s[t] = (t - lag - 1 >= base ? rs[t - lag - 1] : 1.0) * s[t - lag] / rs[t - lag];
+            if (clamped && t > 0 && clamped[(size_t)t * B + b]) s[t] = 1.0 / rs[t - 1];
             const bool fresh = t == 0 || (kinds && kinds[(size_t)t * B + b] != SRC_PREV);
             norms[(size_t)b * T + t] = fresh ? St / s[t] : St / (rs[t - 1] * s[t]);
         }

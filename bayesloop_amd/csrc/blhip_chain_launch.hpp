@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "blhip_chainres.hpp"
+#include "blhip_chainclamp.hpp"
 
 namespace blcl {
 
@@ -43,6 +44,11 @@ void chainax_ntw4(hipStream_t s, const blc::ChainParams &Q, int nk, bool bwd, bo
 void chainax_ntw12_pad(hipStream_t s, const blc::ChainParams &Q, int nk, int ntw, bool bwd, bool store);      // grids smaller than the square geometry
 void chainax_ntw4_pad(hipStream_t s, const blc::ChainParams &Q, int nk, bool bwd, bool store);
 
-constexpr int N_SLICES = 22;      // BLC_TU = 1 .. N_SLICES (blhip_chain_tu.hip)
+// ... RegimeSwitch inside the one-axis kernels (blc::chain_clamp_kernel: 128 / 256 / 512 rows, ring lengths 4, 8, 12 .. 24; 18 kernels per slice)
+void chain_clamp_ntw1(hipStream_t s, const blc::ClampParams &Q, int nk, bool bwd, bool store);
+void chain_clamp_ntw2(hipStream_t s, const blc::ClampParams &Q, int nk, bool bwd, bool store);
+void chain_clamp_ntw4(hipStream_t s, const blc::ClampParams &Q, int nk, bool bwd, bool store);
+
+constexpr int N_SLICES = 25;      // BLC_TU = 1 .. N_SLICES (blhip_chain_tu.hip)
 
 }   // namespace blcl

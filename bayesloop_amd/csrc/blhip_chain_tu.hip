@@ -7,8 +7,11 @@
 #ifndef BLC_TU
 #define BLC_TU 0        // (no slice selected -- a bare `hipcc -c` of this file: an empty object; build.py passes -DBLC_TU=1 .. N_SLICES)
 #endif
-#if BLC_TU >= 19
+#if BLC_TU >= 19 && BLC_TU <= 22
 #include "blhip_chainax.hpp"      // (only the slices that hold its kernels: an edit of that header recompiles three units)
+#endif
+#if BLC_TU >= 23
+#include "blhip_chainclamp.hpp"   // (the clamp flavour of the one-axis kernels: three slices, one per geometry)
 #endif
 
 namespace {
@@ -130,7 +133,7 @@ void launch_fold2_w(hipStream_t s, const blc::ChainParams &Q, int nk, bool pad) 
 }
 #undef BLC_CASE
 
-#if BLC_TU >= 19
+#if BLC_TU >= 19 && BLC_TU <= 22
 // walks on both parameters: forward (stored / evidence-only), backward (stored / folded); ring lengths 8 .. 24 in steps of 4
 template <int NK, int NTW, bool PAD>
 void launch_k_ax(hipStream_t s, const blc::ChainParams &Q, bool bwd, bool store) {
@@ -149,6 +152,37 @@ void launch_w_ax(hipStream_t s, const blc::ChainParams &Q, int nk, bool bwd, boo
         case 20: launch_k_ax<20, NTW, PAD>(s, Q, bwd, store); break;
         case 24: launch_k_ax<24, NTW, PAD>(s, Q, bwd, store); break;
         default: fail("internal: both-axes chain-resident kernel with %d band blocks", nk);
+    }
+}
+#endif
+
+#if BLC_TU >= 23
+// RegimeSwitch inside the one-axis kernels (blc::chain_clamp_kernel): forward (evidence-only / storing), backward (storing); ring lengths 4
+// (no stencil) and 8 .. 24 in steps of 4; 128, 256 and 512 rows (a 384-row grid runs padded inside 512)
+#define launch_clamp_fn(K, s, Q, lds) (blreg::hit<&K>(), launch_clamp_ptr(&K, s, Q, lds))
+template <typename KernT>
+void launch_clamp_ptr(KernT KERN, hipStream_t s, const blc::ClampParams &Q, size_t lds) {
+    arm_kernel(reinterpret_cast<const void *>(KERN));
+    hipLaunchKernelGGL(KERN, dim3((unsigned)(Q.C.nslots * Q.C.strips)), dim3(blc::NT), lds, s, Q);
+}
+template <int NK, int NTW>
+void launch_k_clamp(hipStream_t s, const blc::ClampParams &Q, bool bwd, bool store) {
+    const size_t lds = blc::lds_doubles_clamp<NK, NTW>() * sizeof(double);
+    if (bwd && !store) fail("internal: clamped chain-resident launch of a folding backward pass");
+    if (bwd) launch_clamp_fn((blc::chain_clamp_kernel<NK, NTW, true, true>), s, Q, lds);
+    else if (store) launch_clamp_fn((blc::chain_clamp_kernel<NK, NTW, false, true>), s, Q, lds);
+    else launch_clamp_fn((blc::chain_clamp_kernel<NK, NTW, false, false>), s, Q, lds);
+}
+template <int NTW>
+void launch_w_clamp(hipStream_t s, const blc::ClampParams &Q, int nk, bool bwd, bool store) {
+    switch (nk) {
+        case 4: launch_k_clamp<4, NTW>(s, Q, bwd, store); break;
+        case 8: launch_k_clamp<8, NTW>(s, Q, bwd, store); break;
+        case 12: launch_k_clamp<12, NTW>(s, Q, bwd, store); break;
+        case 16: launch_k_clamp<16, NTW>(s, Q, bwd, store); break;
+        case 20: launch_k_clamp<20, NTW>(s, Q, bwd, store); break;
+        case 24: launch_k_clamp<24, NTW>(s, Q, bwd, store); break;
+        default: fail("internal: clamped chain-resident kernel with %d band blocks", nk);
     }
 }
 #endif
@@ -257,6 +291,12 @@ void chainax_ntw12_pad(hipStream_t s, const blc::ChainParams &Q, int nk, int ntw
 }
 #elif BLC_TU == 22
 void chainax_ntw4_pad(hipStream_t s, const blc::ChainParams &Q, int nk, bool bwd, bool store) { launch_w_ax<4, true>(s, Q, nk, bwd, store); }
+#elif BLC_TU == 23
+void chain_clamp_ntw1(hipStream_t s, const blc::ClampParams &Q, int nk, bool bwd, bool store) { launch_w_clamp<1>(s, Q, nk, bwd, store); }
+#elif BLC_TU == 24
+void chain_clamp_ntw2(hipStream_t s, const blc::ClampParams &Q, int nk, bool bwd, bool store) { launch_w_clamp<2>(s, Q, nk, bwd, store); }
+#elif BLC_TU == 25
+void chain_clamp_ntw4(hipStream_t s, const blc::ClampParams &Q, int nk, bool bwd, bool store) { launch_w_clamp<4>(s, Q, nk, bwd, store); }
 #else
 #error "BLC_TU out of range"
 #endif

@@ -17,6 +17,7 @@ struct BatchEnv {
     std::vector<hipEvent_t> *fold_ev = nullptr;      // start / end events of fold kernels nobody waits for (do_fit reads them after its last batch)
     int64_t bi = 0;               // index of the batch in the call
     bool allow_chainres = true;   // false: a repeated batch (its first attempt poisoned the carried partial accumulators)
+    bool fast_but_clamp = false;  // the batch would take the fast 2-D kernels but for its clamps (plan_geometry's conditions without has_clamp)
     Trace *tr = nullptr;          // option trace: host phases on stderr
     void mark(const char *what) const { if (tr) tr->mark(what); }
 };
@@ -302,6 +303,20 @@ inline bool chain_forced_fail(const BatchEnv &E, int stage) {
     return (int64_t)E.ctx->option("chain_force_fail_batch", -1.0) == E.bi && (int)E.ctx->option("chain_force_fail_stage", 0.0) == stage;
 }
 
+// what blcp::chain_clamp_envelope reads, from the batch (restarts / same_taps: filled in behind plan_chainres); false: a clamp mode the
+// kernels do not carry
+inline bool clamp_facts(const BatchEnv &E, bool gauss, blcp::ClampFacts &f) {
+    const ChainProgram &prog = *E.prog;
+    f.ndim = E.p->ndim; f.gaussian_recurrence = gauss;
+    f.n0 = E.g.n0; f.n1 = E.g.n1; f.radius0 = prog.LW0; f.radius1 = prog.LW1;
+    f.composed = prog.multi;
+    f.resumed = E.ff.resume; f.carried = E.ff.carry; f.backward_init = E.p->backward_init != nullptr;
+    f.cus = std::min(E.ctx->num_cus, 256);
+    f.regime_switch_only = prog.other_clamp && !prog.dense_clamp && !prog.has_shift;
+    for (size_t e = 0; e < prog.cmodeF.size() && f.regime_switch_only; ++e) f.regime_switch_only = prog.cmodeF[e] <= 2 && prog.cmodeB[e] <= 2;
+    return f.regime_switch_only;
+}
+
 struct ChainRun {
     bool on = false;
     ChainResPlan cp;
@@ -316,6 +331,7 @@ struct ChainRun {
     bool post_private = false;
     bool tab = false;                              // the likelihood comes out of a table (blc::chain_kernel TAB)
     bool ax1 = false;                              // walks on both parameters: blc::chainax_kernel (the distribution is transposed between the filters)
+    bool clamp = false;                            // RegimeSwitch steps: blc::chain_clamp_kernel (blhip_chainclamp.hpp; a clamped step waits for the sums of the step before)
     size_t xch_bytes = 0;
     int ax_mode = -1;                              // exchange mode (-1: per launch, see pass())
     // a padded grid whose sequence is NOT private (an ordinary fit that keeps its posteriors): the kernels work on a scratch sequence on
@@ -356,13 +372,28 @@ struct ChainRun {
         tab = E.p->obs_model == BLHIP_OM_TABLE && E.DT->lik != nullptr && ctx->option("chain_table", 1.0) != 0.0;
         // walks on the second parameter too: the transposing kernels (blc::chainax_kernel; Gaussian recurrence, exact square geometries)
         const bool may_ax1 = (gauss || tab) && prog.LW1 > 0 && ctx->option("chain_ax1", 1.0) != 0.0;
-        if (fast && (gauss || tab) && !E.ff.resume && !E.ff.carry && !E.p->backward_init &&
-            !prog.has_clamp && (prog.LW1 == 0 || may_ax1) && (double)G * 8.0 < 4.0e9 && ctx->option("chain_resident", 1.0) != 0.0 && ctx->resident_ok &&
+        // RegimeSwitch batches (blhip_chainclamp.hpp): the envelope and the routing rule are blcp::chain_clamp_envelope / _route
+        const int clamp_opt = (int)ctx->option("chain_clamp", 1.0);
+        blcp::ClampFacts cf;
+        const bool clamp_try = prog.has_clamp && E.fast_but_clamp && clamp_opt != 0 && clamp_facts(E, gauss, cf) && blcp::chain_clamp_envelope(cf);
+        if ((fast || clamp_try) && (gauss || tab) && !E.ff.resume && !E.ff.carry && !E.p->backward_init &&
+            (!prog.has_clamp || clamp_try) && (prog.LW1 == 0 || may_ax1) && (double)G * 8.0 < 4.0e9 && ctx->option("chain_resident", 1.0) != 0.0 && ctx->resident_ok &&
             E.allow_chainres) {
-            cp.r0_max = (!tab && ctx->option("chain_wide", 1.0) != 0.0) ? CHAIN_R0_MAX : FAST_R0_MAX;
+            cp.r0_max = (!tab && !clamp_try && ctx->option("chain_wide", 1.0) != 0.0) ? CHAIN_R0_MAX : FAST_R0_MAX;
             cp.allow_ax1 = may_ax1;
             on = plan_chainres(E.g, prog, *E.taps, B, T, E.ff.full, std::min(ctx->num_cus, 256), cp);
             E.mark("  plan_chainres");
+            if (clamp_try) {
+                // (plan_chainres has checked: the prior first, ONE tap set per chain at every step, restarts noted)
+                cf.same_taps = on; cf.restarts = on && cp.has_reset;
+                on = on && blcp::chain_clamp_envelope(cf) && !cp.ax1 && cp.ntw <= 4 &&
+                     blcp::chain_clamp_route(clamp_opt, true, B, cp.strips, T, E.ff.full ? 2 : 1, std::min(ctx->num_cus, 256));
+                if (on) {
+                    clamp = true;
+                    if (cp.ntw == 3) { cp.ntw = 4; cp.n0p = 512; cp.pad = true; }          // (a 384-row grid runs padded inside 512 rows)
+                    for (int &nk : cp.round_nk) nk = nk <= 4 ? 4 : (nk + 3) / 4 * 4;       // (ring lengths 4, 8, 12 .. 24)
+                }
+            }
             if (on && tab && cp.ntw > 4) on = false;
             if (on && tab && cp.pad && cp.ntw >= 3 && !cp.ax1) on = false;      // (padded 384 / 512-row geometries with a likelihood table: no kernel -- never selected by a test or workload, pruned in round 5)
             if (on && prog.LW1 > 0 && !cp.ax1) on = false;
@@ -452,7 +483,8 @@ struct ChainRun {
         // (not beside overlapped folds: a FoldJob of the previous batch may still read ctx->accw and read-modify-write ctx->acc on the
         //  second stream while this batch re-carves accw and its fused fold writes ctx->acc on the main stream)
         // (a restart inside a FILTERING chain would need sum(alpha T(reset)) for the predicted sums: such batches store and fold separately)
-        fused = post_private && !cp.mixed && !E.overlap_acc && ctx->option("fuse_accumulate", 1.0) != 0.0;
+        // (clamped batches store and fold afterwards: the predicted sums of the fused fold do not survive a clamp)
+        fused = post_private && !cp.mixed && !clamp && !E.overlap_acc && ctx->option("fuse_accumulate", 1.0) != 0.0;
         if (fused && cp.has_reset) {
             // change-point batches: the predicted sums survive a restart only through the two-chain fold kernel's restart rule, and
             // only if the two passes restart at the same places (backward step t restarts <=> forward step t + 1 does: unit-spaced
@@ -612,6 +644,10 @@ struct ChainRun {
                     }
                 }
             }
+            else if (clamp) {
+                blc::ClampParams CP{Q, bwd ? E.M->cmodeB : E.M->cmodeF, bwd ? E.M->limitB : E.M->limitF};
+                launch_chain_clamp(st, CP, rnk[r], cp.ntw, bwd, bwd || !E.ff.evidence_only);
+            }
             else if (two) launch_fold2(st, Q, rnk[r], cp.ntw, cp.pad);
             else launch_chain(st, Q, rnk[r], cp.ntw, bwd, fold_now ? false : (bwd || !E.ff.evidence_only), cp.pad);
             {   // HBM: only what the fit keeps -- forward the stored state (8 B; nothing for evidence-only fits), backward the stored
@@ -664,7 +700,7 @@ struct ChainRun {
                 for (int64_t t = 0; t < h_tshare[b]; ++t)
                     std::memcpy(&redF[((size_t)t * E.B + b) * NRED], &redF[((size_t)t * E.B + prov) * NRED], NRED * sizeof(double));
         if (chain_unlag_batch(redF, E.T, CQ.lag, E.B, rowsumC, sfwdC, cp.has_reset ? E.prog->kindF.data() : nullptr,
-                              skip_prefix ? h_tshare.data() : nullptr) >= 0) { E.ctx->resident_last_reason = BLHIP_FALLBACK_RANGE; return false; }
+                              skip_prefix ? h_tshare.data() : nullptr, clamp ? E.prog->cmodeF.data() : nullptr) >= 0) { E.ctx->resident_last_reason = BLHIP_FALLBACK_RANGE; return false; }
         return true;
     }
 

@@ -496,6 +496,15 @@ void launch_chain(hipStream_t s, const blc::ChainParams &Q, int nk, int ntw, boo
     HIPCHECK(hipGetLastError());
 }
 
+// RegimeSwitch inside the one-axis kernels (blc::chain_clamp_kernel, blhip_chainclamp.hpp): 128 / 256 / 512 rows
+void launch_chain_clamp(hipStream_t s, const blc::ClampParams &Q, int nk, int ntw, bool bwd, bool store) {
+    if (ntw == 4) blcl::chain_clamp_ntw4(s, Q, nk, bwd, store);
+    else if (ntw == 2) blcl::chain_clamp_ntw2(s, Q, nk, bwd, store);
+    else if (ntw == 1) blcl::chain_clamp_ntw1(s, Q, nk, bwd, store);
+    else fail("internal: clamped chain-resident kernel with %d tiles per wave", ntw);
+    HIPCHECK(hipGetLastError());
+}
+
 // walks on both parameters (blc::chainax_kernel, blhip_chainax.hpp)
 void launch_chainax(hipStream_t s, const blc::ChainParams &Q, int nk, int ntw, bool bwd, bool store, bool pad) {
     if (ntw == 4) { if (pad) blcl::chainax_ntw4_pad(s, Q, nk, bwd, store); else blcl::chainax_ntw4(s, Q, nk, bwd, store); }

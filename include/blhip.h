@@ -302,6 +302,9 @@ int blhip_accum_row_stats(blhip_ctx *ctx, const blhip_problem *problem, double *
  * HBM); the host reconstructs the reference's normalisers (core.py:385) from the sums S_k they report:
  *   scheme 0 (blhip_resident.hpp):  s_k = 1 / S_(k-lag)                              norm_k = S_k / (S_(k-1) s_k)
  *   scheme 1 (blhip_chainres.hpp):  s_k = S_(k-lag-1) s_(k-lag) / S_(k-lag)          (s_k = 1 while k < lag, S_(-1) = 1)
+ *   scheme 2 (blhip_chainclamp.hpp): scheme 1, except that a step whose kind has bit 6 (0x40) set -- a clamped step, RegimeSwitch -- ran at
+ *                                    the exact scale s_k = 1 / S_(k-1); the lagged rule of later steps reads that scale like any other.
+ *                                    The low six bits of a kind are the source kind as in scheme 1.
  * sums: (T) in, the normalisers out (in place).  kinds (scheme 1, may be NULL): (T) source kinds, a step whose kind is not 0
  * (blk::SRC_PREV) restarted from a distribution of known mass: norm_k = S_k / s_k.  scales_out (may be NULL): (T) the scales s_k.
  * Returns 0, or 1 if a sum left (1e-150, 1e150) -- the fit then repeats the batch with the launch-per-step kernels. */
