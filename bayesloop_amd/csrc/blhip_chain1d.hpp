@@ -55,6 +55,13 @@ __global__ __launch_bounds__(256) void lik1d_table_kernel(const bl1f::F1Params P
         out[(long long)t * P.n + j] = blk::likelihood<OM>(Q, 0, j, OM == blk::OM_POISSON ? P.colA[j] : 0.0, 0.0, P.m1[j]);
 }
 
+// 2^-k for 2^k <= |v| < 2^(k + 1): the power of two that brings v into [1, 2).  1 for zero, subnormal, infinite, NaN and for the top binade,
+// whose reciprocal power is not a normal number
+__device__ __forceinline__ double pow2_recip(double v) {
+    const long long e = (__double_as_longlong(v) >> 52) & 0x7ff;
+    return (e < 1 || e > 2045) ? 1.0 : __longlong_as_double((2046 - e) << 52);
+}
+
 // M = 2: TWO ADJACENT cells per thread on a plane-interleaved state (even positions in one plane, odd ones in the other: the lanes of a
 // wave still read consecutive 8-byte slots, conflict-free).  At large radii the M = 1 loop is bound by the LDS pipe -- every output reads
 // both operands and the weight of every tap: 3 reads per output and tap.  Two adjacent outputs share their operands (the right operand of
@@ -129,6 +136,13 @@ __device__ __forceinline__ void chain1d_body(const bl1f::F1Params &P) {
         const int kind = P.srckind[tb];
         const int tp = P.tap[tb];
         double *rk = red + (s & 1) * (NW * NS), *rp = red + ((s + 1) & 1) * (NW * NS);
+        // backward: the stored row a_t carries the forward pass's lazily dropped normalisers (its sum N_t is whatever the likelihoods and a
+        // shift's mass left of it) and beta is ~ 1 / n per cell, so a_t beta reaches the subnormals a factor n / N_t above where the reference's
+        // alpha_norm beta does, and the row normaliser 1 / sum(a_t beta) multiplies the lost bits back up (4100 cells, a row shifted by 40
+        // cells and back: N_t = 0.006, 13 % off in the cells the spline's tail leaves at 1e-317).  The product is formed with beta times the
+        // power of two next to 1 / N_t: exact, so every row and every ratio of sums the host forms is bit for bit what it was wherever
+        // nothing was subnormal; slots 0, 1 and 3 of the step's sums carry the factor like the row does
+        const double kf = (BWD && P.fwd_sums) ? pow2_recip(P.fwd_sums[tb * NRED * P.nblk]) : 1.0;
         const int l2 = (SHIFT && M == 1 && tp >= 0 && P.cmode[tb] == 6) ? P.tap_lw2[tp] : 0;
         const bool asym = SHIFT && l2 == -1, big = SHIFT && l2 == -2, shift = asym || big;
         // ---- the step's weights (block-uniform: re-staged only when the chain's tap set changes) ---------------------------------------
@@ -223,7 +237,7 @@ __device__ __forceinline__ void chain1d_body(const bl1f::F1Params &P) {
                 if (CLAMP) aX = fmax(aX, a);
                 if (P.means) aM = fma(a, LEAN ? P.m1[j] : g1, aM);
             } else {
-                const double cn = o * L, p = al[q] * o;
+                const double cn = o * L, p = al[q] * (o * kf);
                 put(nxt, j, cn);
                 row[j] = p;
                 aN += p; aS += p / L; aC += cn;          // 0/0 -> NaN as numpy (core.py:463)

@@ -43,6 +43,8 @@ struct F1Params {
     const unsigned char *cmode; const int *tap_lw2;
     const double *limit;                           // ... CL = 2 (programs with RegimeSwitch / NotEqual clamps): [T][B] the clamp level of every step
     int no_shift;                                  // ... and none of its steps is a Deterministic shift: long rows may take two cells per thread (M = 2)
+    // chain-resident kernel, backward: the forward pass's own sums ([T][B][NRED][nblk], slot 0 = the sum of the stored row a_t), or nullptr
+    const double *fwd_sums;
 };
 
 // One step over the cells of a block's window that are still exact after it (lo .. hi - 1): stencil out of LDS, likelihood, new state

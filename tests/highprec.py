@@ -1032,7 +1032,7 @@ def apply_stage(st, v, e, nblk=1, sums=None):
 
 def transition_fit(prior, liks, steps, grids, lattice, nblk=1, full=True, shared=None):
     """core.py:372-470 in longdouble with a running bound, over a per-step stage program (gaussian_fit with one walk list for every step is the
-    special case).  prior float64 on the grid (one or two parameters); liks: per step (L, bound of L); steps: per step t a dict
+    special case).  prior float64 on the grid (any number of parameters: every stage works along an axis moved to the front); liks: per step (L, bound of L); steps: per step t a dict
         fwd: (source, stages) of the transition INTO step t from t - 1 (unused for t = 0), bwd: the same INTO step t from t + 1 (unused for T - 1)
     source: 'prev' (the neighbour's state), 'reset' / 'indep' (shared[source], float64, as given: transitionModels.py:300-312, :351-360);
     stages: apply_stage's, in list order (:645-649).  -> the dict of gaussian_fit: (value, bound) pairs, bounds WITHOUT SLACK; and 'sums': (D, bound of D) of every renormalising

@@ -12,6 +12,9 @@ order of a CombinedTransitionModel (transitionModels.py:645-649):
     ('shift', axis)     Deterministic; parameter: the shift d (|d| <= 12: the one-pass stencil; 1-D grids: beyond it the two-stage shift), applied
                         in the direction a driver looks at, 0 in the other; a tuple: one shift per transition (a number: d, then -d)
     ('cp',)             ChangePoint; parameter: the step it fires behind       ('indep',)  Independent; no parameter (None)
+    ('bp',)             BreakPoint of a SerialTransitionModel; parameter: the time stamp from which the next sub-model acts.  A case with break
+                        points names the sub-model of every model (`segments`, one entry per model; None: the model acts in every segment)
+Grids with more than two parameters (the families `nd` and `chain_nd`) take walks, NotEqual, shifts of up to 12 cells and the sources.
 DRIVERS (every step has a table likelihood, BLHIP_OM_TABLE):
     forward    T = 2, prior = x, likelihood 1, forward-only, posteriors kept: step 1's posterior is normalise(K x)
     backward   T = 2, uniform prior, likelihoods (1, x), full fit: step 0's posterior is the normalised backward transition of x
@@ -40,10 +43,12 @@ BIG_1D = [12.0000001, 40.5]
 CASES = {}
 
 
-def _case(name, family, shape, opts, models, chains, drivers=DRIVERS, inputs=INPUTS):
+def _case(name, family, shape, opts, models, chains, drivers=DRIVERS, inputs=INPUTS, segments=None):
     assert name not in CASES
+    segments = [None] * len(models) if segments is None else list(segments)
+    assert len(segments) == len(models) and all(len(c) == len(models) for c in chains), name
     CASES[name] = dict(name=name, family=family, shape=tuple(shape), opts=opts, models=models, chains=[tuple(c) for c in chains],
-                       drivers=tuple(drivers), inputs=tuple(inputs))
+                       drivers=tuple(drivers), inputs=tuple(inputs), segments=segments)
 
 
 # ---- blk::step_kernel<100, 0 / 1, *>: 24 x 20 (two tiles of 16 rows) and 20 x 140 (two tiles of 128 columns) --------------------------------
@@ -114,6 +119,92 @@ _case('mfma_band8_sources_140x90', 'mfma', (140, 90), OFF, [('cp',), ('walk', 0)
 _case('hwide_sources_40x300', 'hwide', (40, 300), OFF, [('cp',), ('walk', 1)], [(1, 64), (0, 9)], drivers=('three',))
 _case('vwide_sources_140x64', 'vwide', (140, 64), OFF, [('cp',), ('walk', 0)], [(1, 41), (0, 128)], drivers=('three',))
 
+# ---- grids with three and four parameters: the plain path (bln::filter_axis_kernel, bln::step_kernel<BWD> and the renormalising stages
+#      ne_max / ne_invert / ne_clamp / shift_axis_kernel; chain_nd = 0) and bln::chain_nd_kernel<BWD, 256 | 1024> (chain_nd = 2: walks and
+#      restarts).  5 x 18 x 14: five blocks of 256 cells with a partial last one, inner = 252, 14 and 1; 3 x 7 x 5: less than a block;
+#      3 x 3 x 7 x 6: four parameters.  The first walk is the one on the WIDE axis (18 resp. 7 cells), so that `single` and `edges` speak of its
+#      lines: radii n, n + 1 (the kernels' other reflection branch) and beyond 2 n (several periods); walks on every axis and on all; a chain
+#      without a walk ---------------------------------------------------------------------------------------------------------------------------------
+ND, CHAIN_ND = dict(chain_nd=0), dict(chain_nd=2)
+ND_SHAPES = {'5x18x14': (5, 18, 14), '3x7x5': (3, 7, 5), '3x3x7x6': (3, 3, 7, 6), '4x16x32': (4, 16, 32)}
+ND_WALKS = {
+    '5x18x14': ([('walk', 1), ('walk', 0), ('walk', 2)], [(18, 0, 0), (19, 0, 0), (23, 0, 0), (0, 2, 0), (0, 0, 3), (5, 2, 3), (0, 0, 0)]),
+    '3x7x5': ([('walk', 1), ('walk', 0), ('walk', 2)], [(7, 0, 0), (8, 0, 0), (16, 0, 0), (0, 2, 0), (0, 0, 3), (3, 2, 3), (0, 0, 0)]),
+    '3x3x7x6': ([('walk', 2), ('walk', 0), ('walk', 3), ('walk', 1)],
+                [(7, 0, 0, 0), (8, 0, 0, 0), (16, 0, 0, 0), (0, 2, 0, 0), (0, 0, 3, 0), (0, 0, 0, 1), (3, 2, 3, 1), (0, 0, 0, 0)]),
+    '4x16x32': ([('walk', 1), ('walk', 0), ('walk', 2)], [(16, 0, 0), (17, 0, 0), (35, 0, 0), (0, 3, 0), (0, 0, 5), (4, 3, 5), (0, 0, 0)]),
+}
+
+
+def _nd_walks_and_sources(fam, opts, tag):
+    shape = ND_SHAPES[tag]
+    wide = ND_WALKS[tag][0][0]                       # the walk on the axis of 18 (7, 16) cells
+    n = shape[wide[1]]
+    _case('%s_walks_%s' % (fam, tag), fam, shape, opts, *ND_WALKS[tag])
+    # a change point in FRONT of the walk (the stencil reads the reset prior) and BEHIND it (the walk is dropped); chains that fire behind step 1
+    # and behind step 0; Independent between two walks
+    _case('%s_cp_then_walk_%s' % (fam, tag), fam, shape, opts, [('cp',), wide], [(1, 3), (0, n + 1)], drivers=('three',))
+    _case('%s_walk_then_cp_%s' % (fam, tag), fam, shape, opts, [wide, ('cp',)], [(3, 1), (n + 1, 0)], drivers=('three',))
+    _case('%s_independent_%s' % (fam, tag), fam, shape, opts, [wide, ('indep',), ('walk', len(shape) - 1)], [(3, None, 2)], drivers=('three',))
+
+
+for tag in ('5x18x14', '3x7x5', '3x3x7x6'):
+    _nd_walks_and_sources('nd', ND, tag)
+    _nd_walks_and_sources('chain_nd', CHAIN_ND, tag)
+# ... the 1024-thread block (two cells per thread), and a batch in which every chain has another radius on the same walks (one of them none)
+# and another step at which its change point fires (7: never): the tap slots of a block, the source kind loaded a step ahead
+_case('chain_nd_walks_4x16x32', 'chain_nd', ND_SHAPES['4x16x32'], CHAIN_ND, *ND_WALKS['4x16x32'])
+for tag in ('5x18x14', '4x16x32'):
+    _case('chain_nd_mixed_%s' % tag, 'chain_nd', ND_SHAPES[tag], CHAIN_ND, [('walk', 1), ('cp',), ('walk', 2)],
+          [(3, 1, 2), (19, 0, 0), (0, 7, 5), (7, 0, 1), (0, 1, 0), (1, 7, 3)], drivers=('three',))
+
+# NotEqual (three launches: the maximum, the inversion, the clamp) alone, behind a walk, in front of one, and twice with a walk between
+for nm, models, chains in (('not_equal', [('ne',)], [(-4.0,), (-7.0,)]),
+                           ('walk_then_ne', [('walk', 1), ('ne',)], [(3, -4.0), (19, -7.0)]),
+                           ('ne_then_walk', [('ne',), ('walk', 1)], [(-4.0, 3), (-7.0, 19)]),
+                           ('ne_walk_ne', [('ne',), ('walk', 2), ('ne',)], [(-4.0, 3, -7.0), (-7.0, 0, -4.0)])):
+    _case('nd_%s_5x18x14' % nm, 'nd', (5, 18, 14), ND, models, chains, drivers=('forward', 'three'))
+_case('nd_not_equal_3x3x7x6', 'nd', (3, 3, 7, 6), ND, [('ne',)], [(-4.0,), (-7.0,)], drivers=('forward', 'three'))
+# shifts on the first, the middle and the last axis, and on an axis of the four-parameter grid
+for ax in (0, 1, 2):
+    _case('nd_shift_axis%d_5x18x14' % ax, 'nd', (5, 18, 14), ND, [('shift', ax)], [(d,) for d in SHIFTS_2D])
+_case('nd_shift_axis2_3x3x7x6', 'nd', (3, 3, 7, 6), ND, [('shift', 2)], [(d,) for d in SHIFTS_2D])
+_case('nd_shift_then_walk_5x18x14', 'nd', (5, 18, 14), ND, [('shift', 0), ('walk', 1)], [(0.5, 3), (-3.25, 19), (12.0, 0)])
+# a batch that mixes a shift and none per chain and step: the chain without one passes through shift_axis_kernel BY COPY, values and the
+# partial sums its scale is read from; a NotEqual chain beside chains whose change point restarts at that step (ne_clamp_kernel's copy)
+_case('nd_mixed_shifts_5x18x14', 'nd', (5, 18, 14), ND, [('shift', 1)], [((0.0, 3.25),), ((-12.0, 0.5),), ((0.5, 0.0),)], drivers=('three',))
+_case('nd_mixed_shifts_3x3x7x6', 'nd', (3, 3, 7, 6), ND, [('shift', 3)], [((0.0, 3.25),), ((-12.0, 0.5),), ((0.5, 0.0),)], drivers=('three',))
+_case('nd_ne_beside_restart_5x18x14', 'nd', (5, 18, 14), ND, [('ne',), ('cp',)], [(-4.0, 7), (-4.0, 1), (-7.0, 0)], drivers=('forward', 'three'))
+
+
+def chain_nd_threads(case):
+    """bln::chain_nd_threads restated (blhip_chain_nd.hpp): 256 threads while two state buffers, a tap slot of the batch's widest radius per
+    walk, the grid values and the reduction scratch take at most 32 KB of LDS, 1024 beyond"""
+    shape = case['shape']
+    walks = [k for k, m in enumerate(case['models']) if m[0] == 'walk']
+    lw = max([c[k] for c in case['chains'] for k in walks] + [0])
+    doubles = 2 * int(np.prod(shape)) + len(walks) * (lw + 1) + sum(shape) + 7 * (1024 // 64) + 8
+    return 256 if doubles * 8 <= 32 * 1024 else 1024
+
+
+# the large block runs on 4 x 16 x 32 alone, at two cells per thread; every other grid of the family is below the 32 KB
+for _n, _c in CASES.items():
+    if _c['family'] == 'chain_nd':
+        assert chain_nd_threads(_c) == (1024 if _n.endswith('4x16x32') else 256), _n
+assert 1024 < int(np.prod(ND_SHAPES['4x16x32'])) <= 2 * 1024
+assert chain_nd_threads(dict(CASES['chain_nd_walks_4x16x32'], shape=(4, 16, 31))) == 1024      # (not THE threshold: 1984 cells are beyond it too)
+
+# ---- bl1c::chain1d_long_kernel<BWD, M, CL>: rows of 4097 .. 8192 cells, the cases of bl1c::chain1d_kernel above on n = 4100 (the first partial
+#      round of 512 threads beyond 4096); (M, CL) = (2, 0) walks, (2, 2) clamps, (1, 1) shifts, (1, 2) shifts and clamps in one program ----------
+for nm in ('walks', 'rs_then_walk', 'walk_then_rs', 'not_equal', 'shifts', 'mixed_shifts', 'mixed_clamps', 'sources'):
+    c = CASES['chain1d_%s_300' % nm]
+    _case('chain1d_long_%s_4100' % nm, 'chain1d_long', (4100,), CHAIN1D, c['models'],
+          [tuple(300 if p == 299 else p for p in ch) for ch in c['chains']], drivers=c['drivers'])
+# a serial model: RegimeSwitch up to the break point, the shift from it on (one program cannot hold both at one step: that is the composed row)
+_case('chain1d_long_rs_or_shift_4100', 'chain1d_long', (4100,), CHAIN1D, [('rs',), ('bp',), ('shift', 0)],
+      [(-4.0, 1.0, (0.5, 3.25)), (-300.0, 1.0, (-12.0, 40.5)), (-5.0, 7.0, (3.25, 3.25))], drivers=('three',), segments=[0, None, 1])
+_case('chain1d_long_walks_8192', 'chain1d_long', (8192,), CHAIN1D, [('walk', 0)], [(0,), (540,)], drivers=('three',))    # 2 n + 5 LW + 113 = 19 197 of 19 200 doubles
+
 # NotEqual inverts around the maximum of its input: of the uniform alpha_0 of the backward driver it is 0 / 0 in the reference
 # (transitionModels.py:462-465).  Named here, asserted by tests/test_highprec.py with what well_conditioned leaves out.
 NOT_EQUAL_OF_UNIFORM = sorted(n for n, c in CASES.items() if any(m[0] == 'ne' for m in c['models']))
@@ -123,11 +214,23 @@ def steps_of(driver):
     return 3 if driver == 'three' else 2
 
 
-def state(kind, shape, seed=0):
-    """a normalised float64 distribution (transition_cases.state; 1-D grids: one line)"""
+def line_axis(case, seed):
+    """the axis whose lines `single` and `edges` speak of on a grid with more than two parameters: the one the case's first walk or shift
+    acts on -- the lines its stencil runs along --, seed % ndim for a case without one"""
+    return next((m[1] for m in case['models'] if m[0] in ('walk', 'shift')), seed % len(case['shape']))
+
+
+def state(kind, shape, seed=0, axis=None):
+    """a normalised float64 distribution (transition_cases.state; 1-D grids: one line; more than two parameters: (n, lines) of the lines
+    along `axis`, moved back into place)"""
     if len(shape) == 1:
         return tc.state(kind, (shape[0], 1), 0, seed)[:, 0].copy()
-    return tc.state(kind, shape, seed % 2, seed)
+    if len(shape) == 2:
+        return tc.state(kind, shape, seed % 2, seed)
+    axis = seed % len(shape) if axis is None else axis
+    rest = [n for k, n in enumerate(shape) if k != axis]
+    x = tc.state(kind, (shape[axis], int(np.prod(rest))), 0, seed)
+    return np.ascontiguousarray(np.moveaxis(x.reshape([shape[axis]] + rest), 0, axis))
 
 
 def tables(case, kind, driver):
@@ -135,7 +238,8 @@ def tables(case, kind, driver):
     shape = case['shape']
     G = int(np.prod(shape))
     seed = sum(ord(ch) for ch in case['name']) % 97
-    x = state(kind, shape, seed)
+    axis = line_axis(case, seed)
+    x = state(kind, shape, seed, axis)
     rng = np.random.default_rng(4000 + seed)
     T = steps_of(driver)
     lik = np.ones((T,) + shape)
@@ -146,8 +250,8 @@ def tables(case, kind, driver):
     elif driver == 'three':
         lik[1] = 3.0 * (0.5 + rng.random(shape))
         lik[2] = 0.25 * (0.5 + rng.random(shape)) ** 2
-    reset = state('cube', shape, seed + 1)
-    indep = state('decades', shape, seed + 2)
+    reset = state('cube', shape, seed + 1, axis)
+    indep = state('decades', shape, seed + 2, axis)
     return prior, lik, reset, indep
 
 
@@ -166,9 +270,10 @@ def abi_program(case, driver):
     """-> (ops, values (chains, n_ops)) in the C-ABI's layout (include/blhip.h)"""
     T = steps_of(driver)
     ops, cols = [], []
-    for m in case['models']:
+    for m, seg in zip(case['models'], case['segments']):
         cols.append(len(ops))
         ax = m[1] if len(m) > 1 else 0
+        first = len(ops)
         if m[0] == 'walk':
             ops.append((_abi.OP_GRW, ax, -1, 0))
         elif m[0] == 'rs':
@@ -185,14 +290,18 @@ def abi_program(case, driver):
             ops.append((_abi.OP_CHANGEPOINT, 0, -1, 0))
         elif m[0] == 'indep':
             ops.append((_abi.OP_INDEPENDENT, 0, -1, 0))
+        elif m[0] == 'bp':
+            ops.append((_abi.OP_BREAKPOINT, 0, -1, 0))
         else:
             raise ValueError(m)
+        if seg is not None:
+            ops[first:] = [(o[0], o[1], seg, o[3]) for o in ops[first:]]
     values = np.full((len(case['chains']), len(ops)), np.nan)
     for b, params in enumerate(case['chains']):
         for m, col, p in zip(case['models'], cols, params):
             if m[0] == 'walk':
                 values[b, col] = sigma_of(p)
-            elif m[0] in ('rs', 'ne', 'cp'):
+            elif m[0] in ('rs', 'ne', 'cp', 'bp'):
                 values[b, col] = p
             elif m[0] == 'biv':
                 values[b, col:col + 3] = p
@@ -229,7 +338,10 @@ def stage_program(case, params, driver):
 
     def program(tau, step, fwd):
         source, stages = 'prev', []
-        for m, p in zip(case['models'], params):
+        active = sum(1 for m, p in zip(case['models'], params) if m[0] == 'bp' and p <= tau)      # the sub-model of a serial model (transitionModels.py:768)
+        for m, p, seg in zip(case['models'], params, case['segments']):
+            if seg is not None and seg != active:
+                continue
             if m[0] == 'walk':
                 if p:
                     w, e = _taps('walk', sigma_of(p))
@@ -370,6 +482,17 @@ def _kernels(case):
     if fam == 'generic':
         composed = ['blk::step_kernel<100, 2, false>', 'blk::step_kernel<100, 3, false>'] if 'composed' in name else []
         return dict(forward=['blk::step_kernel<100, 0, true>'], full=['blk::step_kernel<100, 0, false>', 'blk::step_kernel<100, 1, true>'] + composed)
+    if fam == 'nd':             # the fused step kernel behind one launch per pass of the transition: a filter per walk, three per NotEqual, one per shift
+        kinds = {m[0] for m in case['models']}
+        stages = (['bln::filter_axis_kernel'] if 'walk' in kinds else []) + (['bln::shift_axis_kernel'] if 'shift' in kinds else []) + \
+                 (['bln::ne_max_kernel', 'bln::ne_invert_kernel', 'bln::ne_clamp_kernel'] if 'ne' in kinds else [])
+        return ['bln::step_kernel<{b}>'] + stages
+    if fam == 'chain_nd':       # one launch per pass, nothing else
+        return ['bln::chain_nd_kernel<{b}, %d>' % chain_nd_threads(case)]
+    if fam == 'chain1d_long':   # (M, CL) as launch_chain1d_long picks them: a shift keeps one cell per thread; a clamp is CL = 2
+        kinds = {m[0] for m in case['models']}
+        shift, clamp = 'shift' in kinds, bool(kinds & {'rs', 'ne'})
+        return ['bl1c::chain1d_long_kernel<{b}, %d, %d>' % (1 if shift else 2, 2 if clamp else (1 if shift else 0))]
     if fam == 'chain1d':
         cl = 1 if any(m[0] == 'shift' for m in case['models']) else (2 if any(m[0] in ('rs', 'ne') for m in case['models']) else 0)
         return ['bl1c::chain1d_kernel<100, {b}, %d, %d>' % (1 if shape[0] <= 512 else 2, cl)]

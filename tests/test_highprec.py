@@ -790,13 +790,21 @@ def test_what_the_step_transition_table_leaves_out():
     # nothing else is left out silently: every case runs all four inputs, and a case that does not run all three drivers is one of these
     assert all(c['inputs'] == sc.INPUTS for c in sc.CASES.values())
     three_only = sorted(n for n, c in sc.CASES.items() if c['drivers'] == ('three',))
-    assert three_only == ['chain1d_mixed_clamps_300', 'chain1d_mixed_shifts_300', 'chain1d_sources_300', 'chain_sources_128x16',
-                          'chainax_sources_32x32', 'fast_band8_sources_140x90', 'fused1d_sources_300', 'generic_change_point_24x20',
-                          'generic_composed_row_300', 'generic_independent_24x20', 'hwide_sources_40x300', 'mfma_band8_sources_140x90',
-                          'persist1d_sources_300', 'persist1d_walks_300', 'vwide_sources_140x64'], three_only     # per-step programs; T > 2 for bl1p::
+    nd_three = ['%s_%s_%s' % (f, c, s) for f in ('chain_nd', 'nd') for c in ('cp_then_walk', 'independent', 'walk_then_cp')
+                for s in ('3x3x7x6', '3x7x5', '5x18x14')]
+    assert three_only == sorted(['chain1d_mixed_clamps_300', 'chain1d_mixed_shifts_300', 'chain1d_sources_300', 'chain_sources_128x16',
+                                 'chainax_sources_32x32', 'fast_band8_sources_140x90', 'fused1d_sources_300', 'generic_change_point_24x20',
+                                 'generic_composed_row_300', 'generic_independent_24x20', 'hwide_sources_40x300', 'mfma_band8_sources_140x90',
+                                 'persist1d_sources_300', 'persist1d_walks_300', 'vwide_sources_140x64',
+                                 # grids with three and four parameters, long rows: per-step programs; 8192 cells: the cost of the reference
+                                 'chain1d_long_mixed_clamps_4100', 'chain1d_long_mixed_shifts_4100', 'chain1d_long_rs_or_shift_4100',
+                                 'chain1d_long_sources_4100', 'chain1d_long_walks_8192', 'chain_nd_mixed_4x16x32', 'chain_nd_mixed_5x18x14',
+                                 'nd_mixed_shifts_3x3x7x6', 'nd_mixed_shifts_5x18x14'] + nd_three), three_only     # per-step programs; T > 2 for bl1p::
     assert all(c['drivers'] in (sc.DRIVERS, ('three',), ('forward', 'three')) for c in sc.CASES.values())
     assert left == [], left                                 # (today: nothing; the single cells of the table's rows lie beyond 12 cells from the ends)
-    assert sc.NOT_EQUAL_OF_UNIFORM == ['chain1d_not_equal_300', 'chain1d_not_equal_600', 'generic_not_equal_20x140', 'generic_not_equal_24x20']
+    assert sc.NOT_EQUAL_OF_UNIFORM == ['chain1d_long_not_equal_4100', 'chain1d_not_equal_300', 'chain1d_not_equal_600', 'generic_not_equal_20x140',
+                                       'generic_not_equal_24x20', 'nd_ne_beside_restart_5x18x14', 'nd_ne_then_walk_5x18x14', 'nd_ne_walk_ne_5x18x14',
+                                       'nd_not_equal_3x3x7x6', 'nd_not_equal_5x18x14', 'nd_walk_then_ne_5x18x14']
     for name in sc.NOT_EQUAL_OF_UNIFORM:
         assert 'backward' not in sc.CASES[name]['drivers'] and set(sc.CASES[name]['drivers']) == {'forward', 'three'}
     x = np.full((4, 5), 1.0 / 20)

@@ -3,7 +3,9 @@ The TRANSITION half of the fused step kernels on the MI355X -- the stencil, the 
 the prior of a step, and the bookkeeping sums that go with it -- cell by cell against tests/highprec.py: blk::step_kernel<100, 0 / 1, *> (walks,
 clamp modes 1, 2, 3, the dense BivariateRandomWalk kernel, the AlphaStable stencil, the small spline shift, every source kind),
 bl1c::chain1d_kernel (CL = 0, 1, 2; one and two cells per thread), bl1f::fused1d_kernel, bl1p::persist1d_kernel, blf::fast_step_kernel and
-blm::mfma_step_kernel in every radius bucket from both sides, blh::hwide_kernel / vwide_kernel, and the resident families with a table likelihood.
+blm::mfma_step_kernel in every radius bucket from both sides, blh::hwide_kernel / vwide_kernel, the resident families with a table likelihood,
+the plain path on grids with three and four parameters (bln::filter_axis_kernel, bln::step_kernel<BWD>, the stages ne_max / ne_invert / ne_clamp /
+shift_axis_kernel), bln::chain_nd_kernel<BWD, 256 | 1024> and bl1c::chain1d_long_kernel<BWD, M, CL> in its four (M, CL) flavours.
 Every comparison is worst(got, want, SLACK * bound) <= 1 over ALL cells with a bound COUNTED in tests/highprec.py (no literal tolerance); the
 weights are the restated ones rounded to float64 (tests/test_host_logic.py holds the library's to them), never the library's own.  Problems,
 drivers and references: tests/step_transition_cases.py, which tests/test_highprec.py runs through the float64 oracle at the same bounds.  What
@@ -24,11 +26,11 @@ from conftest import kernel_census
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not hp.EXTENDED, reason=hp.REQUIRES_EXTENDED)]
 
 WORST = {}
-DEFAULTS = dict(chain_resident=1, resident=1, mfma=1, fast=1, chain1d=1, persist1d=1, fuse1d=8)
+DEFAULTS = dict(chain_resident=1, resident=1, mfma=1, fast=1, chain1d=1, persist1d=1, fuse1d=8, chain_nd=1, chain1d_long=1)
 # the instantiations that apply a transition to a table-likelihood fit, and the large-shift / stage kernels none of these problems may reach
 WATCH = re.compile(r'^(blk::step_kernel<100,|blk::bigshift_kernel<|bl1c::chain1d_kernel<100,|bl1f::fused1d_kernel<100,|bl1p::persist1d_kernel<100,|'
                    r'blf::fast_step_kernel<100,|blm::mfma_step_kernel<100,|blh::hwide_kernel|blh::vwide_kernel|blr::resident_kernel<.*, true>$|'
-                   r'blc::chain_kernel<.*, true>$|blc::chain_fold2_kernel<|blc::chainax_kernel<)')
+                   r'blc::chain_kernel<.*, true>$|blc::chain_fold2_kernel<|blc::chainax_kernel<|bln::|bl1c::chain1d_long_kernel<)')
 
 
 @pytest.fixture(scope='module')
@@ -72,7 +74,8 @@ COMBOS = [(name, kind) for name, c in sc.CASES.items() for kind in c['inputs']]
 
 def test_every_watched_family_is_in_the_table():
     fams = {c['family'] for c in sc.CASES.values()}
-    assert fams == {'generic', 'chain1d', 'fused1d', 'persist1d', 'fast', 'mfma', 'hwide', 'vwide', 'resident', 'chain', 'chainax'}
+    assert fams == {'generic', 'chain1d', 'fused1d', 'persist1d', 'fast', 'mfma', 'hwide', 'vwide', 'resident', 'chain', 'chainax', 'nd', 'chain_nd',
+                    'chain1d_long'}
     for name, c in sc.CASES.items():
         assert set(sc.EXPECT[name]) == set(c['drivers']), name
 
