@@ -158,6 +158,26 @@ inline double rec_envelope_bound(const double *m0, int n0, const double *s, int 
     return b == b ? b : INFINITY;          // (a NaN bound -- a zero or NaN std -- is no envelope)
 }
 
+// May the fast, resident and chain-resident kernels run the likelihood recurrence along the rows of this grid, and with which row step?
+struct RowRecurrence { double step0 = 0.0; bool use_rec = false; };
+
+RowRecurrence plan_recurrence(blhip_ctx *ctx, const blhip_problem *p, int n0, int n1) {
+    RowRecurrence rr;
+    // likelihood recurrence along rows needs an equally spaced row axis (to rounding)
+    const double *m0h = p->marginal[0];
+    const double step = (m0h[n0 - 1] - m0h[0]) / (double)(n0 - 1);
+    double dev = 0.0, mx = 0.0;
+    for (int i = 0; i < n0; ++i) {
+        dev = std::max(dev, std::fabs(m0h[i] - (m0h[0] + i * step)));
+        mx = std::max(mx, std::fabs(m0h[i]));
+    }
+    rr.step0 = step;
+    rr.use_rec = p->obs_model == BLHIP_OM_GAUSSIAN && dev <= 8.0 * 2.3e-16 * mx && ctx->option("recurrence", 1.0) != 0.0;
+    // ... and arguments inside its envelope (exponents are added in int, exp_mn clamps): beyond it the per-cell exponential
+    if (rr.use_rec && !(rec_envelope_bound(m0h, n0, p->marginal[1], n1, p->data, p->T * p->seg_len, p->data_dim) <= REC_ENVELOPE)) rr.use_rec = false;
+    return rr;
+}
+
 // ---- BLHIP_OM_PROGRAM: the (T, G) likelihood table from the program the context is armed with (bllp::lik_program_kernel) ---------------------
 // d_marginal: the marginal grids on the device, n[k] values each; data: (T, data_dim) on the host; d_lik: (T, G) on the device.  The
 // program's arrays, the step values and the data go into one buffer of the context; queued on the context's stream, not waited for.
@@ -294,14 +314,14 @@ constexpr int CHAIN_TALL_ROWS = 1024;         // ... and the one geometry beyond
 inline bool chain_rows_ok(int n0) { return n0 >= CHAIN_MIN_ROWS && n0 <= CHAIN_TALL_ROWS; }
 inline bool chain_tall(int n0) { return n0 > 512 && n0 <= CHAIN_TALL_ROWS; }
 
-int64_t chains_per_batch(blhip_ctx *ctx, const blhip_problem *p, const Geometry &g, const FitFlags &ff, int64_t n_chains, int post_buffers) {
+int64_t chains_per_batch(blhip_ctx *ctx, const blhip_problem *p, const Geometry &g, const FitFlags &ff, int64_t n_chains) {
     const int64_t T = p->T;
     const long long G = g.G;
     size_t free_b = 0, total_b = 0;
     HIPCHECK(hipMemGetInfo(&free_b, &total_b));
     // (every reusable buffer of the context counts as available, so that the plan -- and with it the buffer sizes -- is the same from
     //  fit to fit: a plan that changed between two fits of one study re-allocated the 100-GB sequence buffer, 5 s)
-    double budget = std::min((double)free_b + (double)ctx->state.cap + (double)ctx->post.cap + (double)ctx->post2.cap + (double)ctx->accpart.cap,
+    double budget = std::min((double)free_b + (double)ctx->state.cap + (double)ctx->post.cap + (double)ctx->accpart.cap,
                              ctx->option("mem_budget_bytes", 0.70 * (double)total_b)) * 0.9;
     // the chain-resident kernels lay their sequences out on a padded geometry (rows 128 / 256 / 512, columns a multiple of 16)
     double Gk = (double)G;
@@ -324,7 +344,7 @@ int64_t chains_per_batch(blhip_ctx *ctx, const blhip_problem *p, const Geometry 
         const double slots = std::max(1, std::min(ctx->num_cus, 256) / ((g.n1 + blc::WCOL - 1) / blc::WCOL));
         budget -= std::min(0.5 * budget, std::min<double>(slots, (double)n_chains) * (double)T * Gk * 8.0);
     }
-    const double per_chain = (ff.evidence_only ? 2.0 : (double)post_buffers * (double)T + 2.0) * Gk * 8.0 +
+    const double per_chain = (ff.evidence_only ? 2.0 : (double)T + 2.0) * Gk * 8.0 +
                              (double)T * NRED * 8.0 * 2 * 64.0 /*partials, rough*/;
     int64_t Bmax = (int64_t)std::max(1.0, std::floor(budget / per_chain));
     // (1-D grids: a chain is a few KB and a batch of the chain-resident 1-D kernel costs a fixed ~1 ms of launches, syncs and read-backs --
@@ -341,6 +361,30 @@ int64_t chains_per_batch(blhip_ctx *ctx, const blhip_problem *p, const Geometry 
                  (long long)it->second.chains, (long long)it->second.G, (long long)n_chains, (long long)G);
     }
     return Bmax;
+}
+
+// ---- batches: at most Bmax chains each, cut where the axis-0 radius bucket changes.  A bucket cut by a batch boundary becomes
+//      two under-filled launches per step (round 1: the 107-chain radius-24 bucket of the C4 study ran as 36 + 71 chains at
+//      4.1 TB/s); hyper-grids are usually monotone in the random-walk width, so contiguous cuts suffice.
+// -> batch_start: batch b holds the chains [batch_start[b], batch_start[b + 1])
+std::vector<int64_t> plan_fit_batches(blhip_ctx *ctx, const blhip_problem *p, const Geometry &g, const FitFlags &ff, int64_t n_chains,
+                                      const double *op_values) {
+    const int64_t Bmax = chains_per_batch(ctx, p, g, ff, n_chains);
+    // (cuts on radius-bucket boundaries serve the launch-per-step kernels; grids the chain-resident kernel takes keep whole launches)
+    const bool chain_shape = p->ndim == 2 && (p->obs_model == BLHIP_OM_GAUSSIAN || (p->obs_model == BLHIP_OM_TABLE && g.n0 <= 512)) && chain_rows_ok(g.n0) && g.n1 <= 16 * blc::MAX_STRIPS &&
+                             ctx->option("chain_resident", 1.0) != 0.0 && ctx->resident_ok;
+    std::vector<int64_t> batch_start = plan_batches(p, n_chains, op_values, Bmax, !chain_shape);
+    // (the cut: 40; grids the chain-resident kernels take: 80)
+    const bool chain_wide = chain_shape && p->obs_model == BLHIP_OM_GAUSSIAN && ctx->option("chain_wide", 1.0) != 0.0;
+    if (!ff.keep && !ff.resume && !ff.carry && ctx->option("wide_v", 1.0) != 0.0)
+        split_wide_axis0(p, n_chains, op_values, batch_start, chain_wide ? CHAIN_R0_MAX : FAST_R0_MAX);
+    // Batches of thousands of chains (1-D studies: the published break-point study runs 6 x 3900): the per-(step, chain) program of batch
+    // bi + 1 is built by a second host thread while batch bi runs -- all but the FIRST one's, 3.9 ms of a 42-ms fit with the GPU idle.  A
+    // short first batch (1024 chains: 0.7 ms of program) starts the pipeline earlier.
+    if (batch_start.size() >= 2 && batch_start[1] - batch_start[0] >= 2048 && !ff.keep && !ff.resume && !ff.carry &&
+        ctx->option("short_first_batch", 1.0) != 0.0)
+        batch_start.insert(batch_start.begin() + 1, batch_start[0] + 1024);
+    return batch_start;
 }
 
 // which kernel family runs a batch and with what block geometry (segment lengths from a small cost model: long segments read every
@@ -667,18 +711,15 @@ void store_carry(blhip_ctx *ctx, const blhip_problem *p, int64_t B, long long G,
 }
 
 // fold the batch into the average posterior (core.py:1358-1366): linear accumulator with a running reference exponent.
-// Two halves, so that the kernel can be launched later than the bookkeeping is done (overlapped folds, see do_fit): prepare_fold
-// turns the batch's evidences into weights (staged in h_w / h_invN, which must stay valid until the launch has consumed them) and
+// Two halves: prepare_fold turns the batch's evidences into weights (staged in h_w / h_invN, which must stay valid until the launch has consumed them) and
 // advances the accumulator's reference; launch_fold copies them to the device and runs the pass on `st`.
 struct FoldJob {
-    bool pending = false;
     const double *d_post = nullptr;
     int64_t B = 0;
     double *h_w = nullptr, *h_invN = nullptr;        // host staging (B), (T * B)
     double *d_w = nullptr, *d_invN = nullptr;        // device copies
     double r = 0.0;                                  // factor of what the accumulator already holds
     int first = 0;
-    int parity = 0;
     int sm_n0 = 0;                                   // > 0: d_post is in the chain-resident kernel's strip-major layout (rows per strip)
     int pad_n0p = 0, pad_n0 = 0, pad_n1 = 0;         // > 0: ... on a padded geometry (rows per strip n0p; the grid's true sizes)
     int pad_ax = 0;                                  //      ... in the alternating layouts of the both-axes kernels (blk::ax_layout_b)

@@ -1,23 +1,28 @@
-// The resident paths of a batch (kernels: blhip_resident.hpp, blhip_chainres.hpp): eligibility, buffers, launches and the host-side
-// checks after each pass, one struct per path.  Included by blhip.hip INSIDE its anonymous namespace, after the helpers it uses
-// (DeviceTables, DeviceMeta, ChainProgram, TapTable, plan_ / launch_ functions, resident_unlag / chain_unlag, BatchOutcome).
+// The paths of a batch, one struct per path; do_fit (blhip.hip) sets the one up that runs a batch, calls its passes and knows nothing of its
+// buffers.  Here: BatchEnv, what every path reads of the batch, and the resident paths (kernels: blhip_resident.hpp, blhip_chainres.hpp)
+// with their eligibility, buffers, launches and the host-side checks after each pass.  The 1-D paths: blhip_fit_row1d.hpp; the
+// launch-per-step path: blhip_fit_step.hpp.  Included by blhip.hip INSIDE its anonymous namespace, after the helpers it uses
+// (DeviceTables, DeviceMeta, GeometryPlan, ChainProgram, TapTable, plan_ / launch_ functions, resident_unlag / chain_unlag, BatchOutcome).
 #pragma once
 
-// ---- what the resident paths of a batch need to know about it -------------------------------------------------------------------------
+// ---- what the paths of a batch need to know about it ----------------------------------------------------------------------------------
 struct BatchEnv {
     blhip_ctx *ctx; const blhip_problem *p; hipStream_t st;
     Geometry g; long long G; int64_t T, B, c0; int d, rec_len;
     FitFlags ff;
     const DeviceTables *DT; const DeviceMeta *M; const ChainProgram *prog; const TapTable *taps;
+    const GeometryPlan *gp;       // which kernel family the batch would take without the resident paths, and its block geometry
+    Tile tile;                    // ... the tile of the launch-per-step and 1-D kernels: tile.nblk partial-sum slots per (step, chain, sum)
     double step0;                 // lattice step of the row axis (likelihood recurrence)
     double *d_post;               // the batch's sequence buffer (null: evidence-only)
+    double *d_pp[2];              // the two state buffers, B x G each (evidence-only forward passes, every backward pass)
+    const double *d_carry_src;    // BLHIP_RESUME: step 0 reads each chain's carried (normalised) state ...
+    const double *d_unit;         // ... and these "previous partial sums", which add up to 1
     const double *log_w;          // log weights of ALL chains of the call (accumulate)
     bool chain_means;             // the caller asked for per-chain posterior means
-    bool overlap_acc;             // folds of earlier batches may still run on the second stream (option accum_overlap)
     std::vector<hipEvent_t> *fold_ev = nullptr;      // start / end events of fold kernels nobody waits for (do_fit reads them after its last batch)
     int64_t bi = 0;               // index of the batch in the call
     bool allow_chainres = true;   // false: a repeated batch (its first attempt poisoned the carried partial accumulators)
-    bool fast_but_clamp = false;  // the batch would take the fast 2-D kernels but for its clamps (plan_geometry's conditions without has_clamp)
     Trace *tr = nullptr;          // option trace: host phases on stderr
     void mark(const char *what) const { if (tr) tr->mark(what); }
 };
@@ -375,7 +380,7 @@ struct ChainRun {
         // RegimeSwitch batches (blhip_chainclamp.hpp): the envelope and the routing rule are blcp::chain_clamp_envelope / _route
         const int clamp_opt = (int)ctx->option("chain_clamp", 1.0);
         blcp::ClampFacts cf;
-        const bool clamp_try = prog.has_clamp && E.fast_but_clamp && clamp_opt != 0 && clamp_facts(E, gauss, cf) && blcp::chain_clamp_envelope(cf);
+        const bool clamp_try = prog.has_clamp && E.gp->fast_but_clamp && clamp_opt != 0 && clamp_facts(E, gauss, cf) && blcp::chain_clamp_envelope(cf);
         if ((fast || clamp_try) && (gauss || tab) && !E.ff.resume && !E.ff.carry && !E.p->backward_init &&
             (!prog.has_clamp || clamp_try) && (prog.LW1 == 0 || may_ax1) && (double)G * 8.0 < 4.0e9 && ctx->option("chain_resident", 1.0) != 0.0 && ctx->resident_ok &&
             E.allow_chainres) {
@@ -480,11 +485,9 @@ struct ChainRun {
         }
         // (the separate fold reads pairs of cells: an even number of columns; the fused fold's partials take any grid -- fold_parts_kernel)
         post_private = E.ff.accumulate && E.ff.full && !E.ff.keep && !E.ff.carry && ((G & 1) == 0 || cp.pad || ax1) && ((uintptr_t)ctx->acc & 15) == 0;
-        // (not beside overlapped folds: a FoldJob of the previous batch may still read ctx->accw and read-modify-write ctx->acc on the
-        //  second stream while this batch re-carves accw and its fused fold writes ctx->acc on the main stream)
         // (a restart inside a FILTERING chain would need sum(alpha T(reset)) for the predicted sums: such batches store and fold separately)
         // (clamped batches store and fold afterwards: the predicted sums of the fused fold do not survive a clamp)
-        fused = post_private && !cp.mixed && !clamp && !E.overlap_acc && ctx->option("fuse_accumulate", 1.0) != 0.0;
+        fused = post_private && !cp.mixed && !clamp && ctx->option("fuse_accumulate", 1.0) != 0.0;
         if (fused && cp.has_reset) {
             // change-point batches: the predicted sums survive a restart only through the two-chain fold kernel's restart rule, and
             // only if the two passes restart at the same places (backward step t restarts <=> forward step t + 1 does: unit-spaced
@@ -520,7 +523,7 @@ struct ChainRun {
             size_t free_b = 0, total_b = 0;
             (void)hipMemGetInfo(&free_b, &total_b);
             const double need = (double)B * (double)T * (double)Gk * 8.0;
-            depad = ctx->option("chain_depad", 1.0) != 0.0 && !E.overlap_acc && (cp.ntw <= 4 || !E.ff.full) &&
+            depad = ctx->option("chain_depad", 1.0) != 0.0 && (cp.ntw <= 4 || !E.ff.full) &&
                     need < 0.8 * ((double)free_b + (double)ctx->postpad.cap);
             if (!depad) { on = false; fused = false; fold2 = false; return; }
             fused = false; fold2 = false;

@@ -121,9 +121,7 @@ struct blhip_ctx {
     long long resident_giveups = 0;
     int resident_last_reason = 0;                  // BLHIP_FALLBACK_* of the last resident batch that fell back
     int num_cus = 0;
-    // average posterior folded on a second stream while the next batch's forward pass runs (do_fit): second sequence buffer,
-    // private copies of the per-batch weights, the stream and its events
-    DevBuf post2, accw;
+    DevBuf accw;                 // device copies of the fused fold's per-chain scales and weights (ChainRun::setup)
     DevBuf postpad;              // padded strip-major sequence of a chain-resident batch whose posteriors are handed out (de-padded into post)
     DevBuf hsrc;                 // the axis-1 pre-pass's output of one step (blhip_hwide.hpp)
     DevBuf stagebuf, stagemeta;  // composed transitions: two stage outputs (+ their partials) of a step, the stages' per-chain programs (blhip_batch.hpp)
@@ -152,8 +150,6 @@ struct blhip_ctx {
     DevBuf xch;                  // exchange buffers of the both-axes chain-resident kernel (blhip_chainax.hpp): [slot][2 step parities][Gk]
     hipStream_t cstream = nullptr;      // copy stream: the forward pass's sums travel to the host beside the backward pass (do_fit: late_copy)
     hipEvent_t cev[2] = {nullptr, nullptr};
-    hipStream_t astream = nullptr;
-    hipEvent_t aev_done[2] = {nullptr, nullptr};
     // the co-residency probe (blr::residency_probe_kernel): when it last ran (steady-clock seconds, < 0: never / run it again), what it saw
     DevBuf probebuf;
     double probe_last = -1.0;

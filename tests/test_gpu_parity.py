@@ -1575,18 +1575,20 @@ def test_chain_resident_kernel_not_taken_outside_its_envelope():
         assert abs(S.logEvidence - want['logEvidence']) <= 1e-9 * abs(want['logEvidence'])
 
 
-def test_average_posterior_folded_on_the_second_stream():
-    """accum_overlap = 1: the study is cut into ~4 batches, the fold of a batch runs on a second stream beside the next batch's
-    forward pass (two sequence buffers).  Same results as the default (folds on the main stream) up to the order of the sums."""
+def test_average_posterior_folded_by_the_separate_pass_over_three_batches():
+    """fuse_accumulate = 0, max_batch = 32: the study is cut into three or more batches, each stored and folded by the separate fold
+    pass.  Same results as the default (one batch, folded inside the backward kernel) up to the order of the sums."""
     eng = bl.get_engine()
     c = _hyper(128, 64, 71, 8, ('cint', 0, 0.9, 80))
     A = cases.build(bl, c); A.fit(silent=True)
-    eng.set_option('accum_overlap', 1)
+    eng.set_option('fuse_accumulate', 0)
+    eng.set_option('max_batch', 32)
     try:
         B = cases.build(bl, c); B.fit(silent=True)
         assert B.lastTiming['batches'] >= 3, B.lastTiming
     finally:
-        eng.set_option('accum_overlap', 0)
+        eng.set_option('fuse_accumulate', 1)
+        eng.set_option('max_batch', 1024)
     assert abs(A.logEvidence - B.logEvidence) <= 1e-12 * abs(A.logEvidence)
     np.testing.assert_allclose(np.array(B.posteriorSequence), np.array(A.posteriorSequence), rtol=1e-11, atol=1e-300)
     np.testing.assert_allclose(B.posteriorMeanValues, A.posteriorMeanValues, rtol=1e-11)
