@@ -12,7 +12,7 @@ import os
 from .exceptions import BackendError
 
 LIB_NAME = 'libblhip.so'
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 OM_POISSON, OM_GAUSSIAN, OM_GAUSSIAN_MEAN, OM_TABLE = 1, 2, 3, 100
 OM_BERNOULLI, OM_LAPLACE, OM_WHITE_NOISE, OM_AR1, OM_SCALED_AR1 = 4, 5, 6, 7, 8
@@ -99,6 +99,9 @@ PROTOTYPES = {
     'blhip_posterior_release': (C.c_int, [C.c_void_p]),
     'blhip_posterior_marginal': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, c_double_p]),
     'blhip_posterior_time_average': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, c_double_p]),
+    'blhip_posterior_predictive': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(Problem), c_double_p,
+                                             C.c_int64, c_double_p, c_double_p, c_double_p]),
+    'blhip_host_predictive_plan': (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_double, C.POINTER(C.c_int64)]),
     'blhip_accum_begin': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     'blhip_accum_state': (C.c_int, [C.c_void_p, c_double_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     'blhip_accum_rescale': (C.c_int, [C.c_void_p, C.c_double]),

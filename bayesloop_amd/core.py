@@ -814,26 +814,70 @@ class Study(object):
     def getPD(self, t, name, plot=False, density=True, **kwargs):
         return self.getParameterDistribution(t, name, plot=plot, density=density, **kwargs)
 
+    # A call for ONE row (a time stamp, the time average) with fewer than PREDICTIVE_MIN_VALUES observation values and fewer than
+    # PREDICTIVE_MIN_WORK grid cells x values stays on the host path: the device path costs 0.065 - 0.085 ms whatever the size (a few
+    # launches, two small copies), the host path 0.045 - 0.07 ms there (measured: profiles/predictive_notes.md).  t='all' never does.
+    PREDICTIVE_MIN_VALUES = 8
+    PREDICTIVE_MIN_WORK = 16384
+
+    def _devicePredictive(self, x, index):
+        """The sums of simulate from the device (DevicePosterior.predictive), or None: the posterior is on the host, its handle or the
+        engine has no such path, option predictive is 0, x is no 1-D array of finite numbers, or the call is too small to gain."""
+        pending = self._posterior_pending
+        if pending is None or not hasattr(pending, 'predictive'):
+            return None
+        if getattr(getattr(pending, 'engine', None), 'options', {}).get('predictive', 1.0) == 0:
+            return None
+        try:
+            xa = np.asarray(x, dtype=float)
+        except (TypeError, ValueError):
+            return None
+        if xa.ndim != 1 or xa.size == 0 or not np.all(np.isfinite(xa)):
+            return None
+        one_row = not (isinstance(index, str) and index == 'all')
+        if one_row and xa.size < self.PREDICTIVE_MIN_VALUES and xa.size * int(np.prod(self.gridSize)) < self.PREDICTIVE_MIN_WORK:
+            return None
+        return pending.predictive(self.observationModel, self.marginalGrid, xa, index=index, grid=self.grid)
+
     def simulate(self, x, t=None, density=False):
         """Probability (density) of the observation values ``x`` under the inferred parameter distribution of time stamp
-        ``t`` (or its time average), reference core.py:566-597.  Only the (time-averaged) distribution of one step leaves
-        the GPU: G doubles, not the (T, G) sequence."""
+        ``t`` (or its time average), reference core.py:566-597.  ``t='all'``: every time stamp at once, a (T, len(x)) array whose row i
+        is ``simulate(x, t=formattedTimestamps[i], density=density)`` -- the predictive band over time.  While the posterior sequence is
+        on the GPU the sums over the grid are formed there (blhip_posterior_predictive): only the result leaves it."""
         om = self.observationModel
         if om.segmentLength > 1:
             raise NotImplementedError('Method "simulate" is only available for observation models with segment length 1.')
         pending = self._posterior_pending
-        if t is None:
-            if pending is not None and hasattr(pending, 'time_average'):
-                post = pending.time_average()
-            else:
+        if isinstance(t, str) and t == 'all':
+            prob = self._devicePredictive(x, 'all')
+            if prob is None:
                 seq = self._requirePosterior()
-                post = np.sum(seq, axis=0) / len(seq)
+                prob = np.empty((len(seq), len(x)))
+                for j, xi in enumerate(x):
+                    lik = om.pdf(self.grid, [xi])
+                    for i in range(len(seq)):
+                        prob[i, j] = np.sum(lik * seq[i])
+            if not density:
+                with np.errstate(invalid='ignore', divide='ignore'):
+                    prob = prob / np.sum(prob, axis=1, keepdims=True)
+            return prob
+        if t is None:
+            prob = self._devicePredictive(x, 'avg')
+            if prob is None:
+                if pending is not None and hasattr(pending, 'time_average'):
+                    post = pending.time_average()
+                else:
+                    seq = self._requirePosterior()
+                    post = np.sum(seq, axis=0) / len(seq)
         else:
             if t not in self.formattedTimestamps:
                 raise PostProcessingError('Supplied time ({}) does not exist in data or is out of range.'.format(t))
             index = list(self.formattedTimestamps).index(t)
-            post = pending.row(index) if pending is not None and hasattr(pending, 'row') else self._requirePosterior()[index]
-        prob = np.array([np.sum(om.pdf(self.grid, [xi]) * post) for xi in x])
+            prob = self._devicePredictive(x, index)
+            if prob is None:
+                post = pending.row(index) if pending is not None and hasattr(pending, 'row') else self._requirePosterior()[index]
+        if prob is None:
+            prob = np.array([np.sum(om.pdf(self.grid, [xi]) * post) for xi in x])
         if not density:
             prob /= np.sum(prob)
         return prob

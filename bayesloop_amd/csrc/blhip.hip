@@ -46,6 +46,7 @@
 #include "blhip_nd_stages.hpp"
 #include "blhip_chain_nd.hpp"
 #include "blhip_likprog.hpp"
+#include "blhip_predictive.hpp"
 
 using namespace blk;
 
@@ -626,7 +627,7 @@ void blhip_destroy(blhip_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     (void)blhip_comm_destroy(ctx);
-    ctx->commbuf.release(); ctx->pinC.release(); ctx->resx.release(); ctx->postpad.release(); ctx->accw.release(); ctx->accpart.release(); ctx->xch.release(); ctx->axlik.release(); ctx->anchbuf.release(); ctx->probebuf.release(); ctx->p1d.release(); ctx->p1w.release(); ctx->lik1d.release(); ctx->likprog_dev.release();
+    ctx->commbuf.release(); ctx->pinC.release(); ctx->resx.release(); ctx->postpad.release(); ctx->accw.release(); ctx->accpart.release(); ctx->xch.release(); ctx->axlik.release(); ctx->anchbuf.release(); ctx->probebuf.release(); ctx->p1d.release(); ctx->p1w.release(); ctx->lik1d.release(); ctx->likprog_dev.release(); ctx->predws.release(); ctx->predx.release();
     for (DevBuf *b : {&ctx->state, &ctx->post, &ctx->psumF, &ctx->psumB, &ctx->redF, &ctx->redB, &ctx->meta,
                       &ctx->tables, &ctx->likbuf, &ctx->small, &ctx->accum_own, &ctx->stats, &ctx->mix, &ctx->unit, &ctx->databuf, &ctx->postinv})
         b->release();
@@ -808,7 +809,7 @@ int blhip_set_option(blhip_ctx *ctx, const char *key, double value) {
     static const char *const known[] = {
         "carry_partials", "chain1d", "chain1d_clamp", "chain1d_long", "chain1d_shift", "chain_ax1", "chain_clamp", "chain_depad", "chain_prof", "chain_resident", "chain_resident_lag",
         "chain_force_fail_batch", "chain_force_fail_stage", "chain_nd", "chain_table", "chain_wide", "comm_reduce_mode", "fast", "fast_S", "fold2", "fold2_cp", "fold_force_fail_batch", "fuse1d", "fuse_accumulate", "late_sums", "lik_program", "max_batch",
-        "mem_budget_bytes", "mfma", "mfma_S", "mfma_h", "mfma_h_max_cells", "peer_copy_mode", "persist1d", "quiet", "recurrence", "resident",
+        "mem_budget_bytes", "mfma", "mfma_S", "mfma_h", "mfma_h_max_cells", "peer_copy_mode", "persist1d", "predictive", "quiet", "recurrence", "resident",
         "resident_force_abort", "resident_lag", "resident_probe", "resident_probe_force_busy", "resident_probe_interval_s", "resident_probe_timeout_s",
         "resident_table", "resident_timeout_s", "share_prefix", "short_first_batch", "skip_prefix", "trace", "wide_h",
         "wide_h_fused_max", "wide_h_split", "wide_v"};
@@ -1033,6 +1034,124 @@ int blhip_posterior_time_average(blhip_ctx *ctx, int source, int64_t chain, doub
         BL_LAUNCH(time_average_kernel, dim3((unsigned)std::min<long long>((G + NTHREADS - 1) / NTHREADS, 4096)),
                            dim3(NTHREADS), 0, st, v.p, d_out, G, (int)v.T);
         HIPCHECK(hipMemcpyAsync(host_out, d_out, (size_t)G * 8, hipMemcpyDeviceToHost, st));
+        sync_stream(ctx, st);
+    });
+}
+
+int blhip_host_predictive_plan(int64_t G, int64_t T, int64_t X, int average, double budget, int64_t *plan_out) {
+    if (!plan_out) return -1;
+    blpp::PredPlan P;
+    const bool ok = blpp::predictive_plan(G, T, X, average != 0, budget, P);
+    if (!ok && P.min_budget_bytes == 0) return -1;
+    plan_out[0] = P.slab; plan_out[1] = P.n_slabs; plan_out[2] = P.rows_per_chunk; plan_out[3] = P.n_chunks;
+    plan_out[4] = P.workspace_bytes; plan_out[5] = P.min_budget_bytes;
+    return ok ? 0 : 1;
+}
+
+int blhip_posterior_predictive(blhip_ctx *ctx, int source, int64_t chain, int64_t t0, int64_t t1, int average, const blhip_problem *model,
+                               const double *x, int64_t n_x, const double *x_step, const double *host_rows, double *host_out) {
+    return guarded(ctx, [&] {
+        if (!model) fail("blhip_posterior_predictive: model is NULL");
+        if (!host_out) fail("blhip_posterior_predictive: host_out is NULL");
+        if (n_x < 1 || n_x > (1ll << 31)) fail("blhip_posterior_predictive: n_x = %lld", (long long)n_x);
+        if (!host_rows && !x) fail("blhip_posterior_predictive: x is NULL");
+        HIPCHECK(hipSetDevice(ctx->device));
+        const SeqView v = sequence_view(ctx, source, chain);
+        if (t0 < 0 || t1 > v.T || t0 >= t1 || t1 - t0 >= (1ll << 31)) fail("blhip_posterior_predictive: bad range [%lld, %lld) of %lld steps", (long long)t0, (long long)t1, (long long)v.T);
+        const long long G = (long long)v.n0 * v.n1;
+        const int ndim = model->ndim, om = model->obs_model;
+        if (ndim < 1 || ndim > BLHIP_MAX_DIM) fail("blhip_posterior_predictive: ndim = %d", ndim);
+        long long Gm = 1;
+        for (int k = 0; k < ndim; ++k) {
+            if (model->n[k] < 1 || model->n[k] > (1ll << 30)) fail("blhip_posterior_predictive: bad grid axis %d", k);
+            Gm *= model->n[k];
+        }
+        if (Gm != G) fail("blhip_posterior_predictive: the grid of the model (%lld cells) does not match the sequence (%lld cells)", Gm, G);
+        // ---- where the likelihood rows come from
+        enum { ROWS_HOST, ROWS_FORMULA, ROWS_TABLE, ROWS_PROGRAM } how = ROWS_HOST;
+        if (!host_rows) {
+            if (om == BLHIP_OM_GAUSSIAN || om == BLHIP_OM_POISSON) how = ROWS_FORMULA;
+            else if (om == BLHIP_OM_BERNOULLI || om == BLHIP_OM_LAPLACE || om == BLHIP_OM_WHITE_NOISE) how = ROWS_TABLE;
+            else if (om == BLHIP_OM_PROGRAM) how = ROWS_PROGRAM;
+            else fail("blhip_posterior_predictive: observation model %d has no likelihood rows on the device: host_rows is required", om);
+            const int want_dim = (om == BLHIP_OM_GAUSSIAN || om == BLHIP_OM_LAPLACE) ? 2 : 1;
+            if (how != ROWS_PROGRAM && ndim != want_dim) fail("blhip_posterior_predictive: observation model %d has %d parameter(s), the grid %d", om, want_dim, ndim);
+            for (int k = 0; k < ndim; ++k)
+                if (!model->marginal[k]) fail("blhip_posterior_predictive: marginal[%d] is NULL", k);
+            for (int64_t j = 0; j < n_x; ++j)
+                if (!std::isfinite(x[j])) fail("blhip_posterior_predictive: x[%lld] is not finite (host_rows takes such values)", (long long)j);
+            if (om == BLHIP_OM_POISSON) {
+                if (!x_step) fail("blhip_posterior_predictive: Poisson needs k! of every value in x_step");
+                for (int64_t j = 0; j < n_x; ++j)
+                    if (x[j] < 0.0 || x[j] != std::floor(x[j]) || !std::isfinite(x_step[j]) || !(x_step[j] >= 1.0))
+                        fail("blhip_posterior_predictive: Poisson value x[%lld] = %g is outside the direct formula (host_rows takes it)", (long long)j, x[j]);
+            }
+            if (how == ROWS_PROGRAM && ctx->likprog.armed && ctx->likprog.n_step > 0 && !x_step) fail("blhip_posterior_predictive: the armed program has STEP values, x_step is NULL");
+        }
+        // ---- the plan: what of the budget the rows of a chunk and the partial results take
+        const int64_t Tr = t1 - t0, Tn = average ? 1 : Tr;
+        size_t free_b = 0, total_b = 0;
+        HIPCHECK(hipMemGetInfo(&free_b, &total_b));
+        const double budget = std::min((double)free_b + (double)ctx->predws.cap, ctx->option("mem_budget_bytes", 0.70 * (double)total_b)) * 0.9;
+        blpp::PredPlan PL;
+        if (!blpp::predictive_plan(G, Tn, n_x, average != 0, budget, PL))
+            fail("blhip_posterior_predictive: a workspace budget of %.0f bytes is below the %lld bytes the smallest plan needs", budget, PL.min_budget_bytes);
+        ctx->predws.ensure((size_t)PL.workspace_bytes);
+        char *ws = ctx->predws.as<char>();
+        double *d_out = reinterpret_cast<double *>(ws + PL.off_out), *d_avg = reinterpret_cast<double *>(ws + PL.off_avg);
+        double *d_rows = reinterpret_cast<double *>(ws + PL.off_rows), *d_part = reinterpret_cast<double *>(ws + PL.off_part);
+        hipStream_t st = ctx->stream;
+        // ---- x, k!, the marginal grids
+        double *d_x = nullptr, *d_kf = nullptr;
+        const double *dm[BLHIP_MAX_DIM] = {nullptr, nullptr, nullptr, nullptr};
+        if (how != ROWS_HOST) {
+            size_t xb = 2 * carve_size((size_t)n_x * 8);
+            for (int k = 0; k < ndim; ++k) xb += carve_size(8 * (size_t)model->n[k]);
+            ctx->predx.ensure(xb);
+            char *cur = ctx->predx.as<char>();
+            d_x = carve<double>(cur, (size_t)n_x);
+            d_kf = carve<double>(cur, (size_t)n_x);
+            HIPCHECK(hipMemcpyAsync(d_x, x, (size_t)n_x * 8, hipMemcpyHostToDevice, st));
+            if (om == BLHIP_OM_POISSON) HIPCHECK(hipMemcpyAsync(d_kf, x_step, (size_t)n_x * 8, hipMemcpyHostToDevice, st));
+            for (int k = 0; k < ndim; ++k) {
+                double *d = carve<double>(cur, (size_t)model->n[k]);
+                HIPCHECK(hipMemcpyAsync(d, model->marginal[k], 8 * (size_t)model->n[k], hipMemcpyHostToDevice, st));
+                dm[k] = d;
+            }
+        }
+        // ---- the left operand
+        const double *d_post = v.p + (size_t)t0 * G;
+        if (average) {
+            BL_LAUNCH(blpp::average_rows_kernel, dim3((unsigned)std::min<long long>((G + 255) / 256, 4096)), dim3(256), 0, st, d_post, d_avg, G, (int)Tr);
+            d_post = d_avg;
+        }
+        const long long ttiles = (Tn + blpp::TM - 1) / blpp::TM;
+        const int n1 = (int)model->n[ndim - 1];
+        const unsigned gx = (unsigned)std::min<long long>((G + NTHREADS - 1) / NTHREADS, 2048);
+        for (int64_t c0 = 0; c0 < n_x; c0 += PL.rows_per_chunk) {
+            const int xc = (int)std::min<int64_t>(PL.rows_per_chunk, n_x - c0);
+            if (how == ROWS_HOST) {
+                HIPCHECK(hipMemcpyAsync(d_rows, host_rows + (size_t)c0 * G, (size_t)xc * G * 8, hipMemcpyHostToDevice, st));
+            } else if (how == ROWS_FORMULA) {
+                BL_LAUNCH(blpp::tabulate_rows_kernel, dim3(gx, (unsigned)xc), dim3(256), 0, st, om, d_rows, G, n1, dm[0], dm[ndim - 1], d_x + c0, d_kf + c0);
+            } else if (how == ROWS_TABLE) {
+                BL_LAUNCH(lik_table_kernel, dim3(gx, (unsigned)xc), dim3(NTHREADS), 0, st, om, d_rows, G, n1, ndim, dm[0],
+                          dm[ndim - 1], d_x + c0, 1, 1);
+            } else {
+                build_program_table(ctx, ndim, model->n, dm, xc, 1, x + c0, d_rows, x_step ? x_step + (size_t)c0 * ctx->likprog.n_step : nullptr);
+            }
+            blpp::ContractParams Q{};
+            Q.post = d_post; Q.rows = d_rows; Q.part = d_part; Q.G = G; Q.slab = PL.slab; Q.T = (int)Tn; Q.xc = xc;
+            Q.wide = (G % 2 == 0 && ((uintptr_t)d_post & 15) == 0 && ((uintptr_t)d_rows & 15) == 0) ? 1 : 0;
+            for_grid_y(ctx, ttiles, [&](long long y0, unsigned ny) {
+                Q.tile0 = y0;
+                BL_LAUNCH(blpp::contract_kernel, dim3((unsigned)PL.n_slabs, ny), dim3(64), 0, st, Q);
+            });
+            BL_LAUNCH(blpp::combine_kernel, dim3((unsigned)(((long long)Tn * xc + 255) / 256)), dim3(256), 0, st, d_part, d_out, (int)PL.n_slabs, (long long)Tn, xc,
+                      (long long)n_x, (long long)c0);
+        }
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpyAsync(host_out, d_out, (size_t)Tn * n_x * 8, hipMemcpyDeviceToHost, st));
         sync_stream(ctx, st);
     });
 }

@@ -181,8 +181,10 @@ RowRecurrence plan_recurrence(blhip_ctx *ctx, const blhip_problem *p, int n0, in
 // ---- BLHIP_OM_PROGRAM: the (T, G) likelihood table from the program the context is armed with (bllp::lik_program_kernel) ---------------------
 // d_marginal: the marginal grids on the device, n[k] values each; data: (T, data_dim) on the host; d_lik: (T, G) on the device.  The
 // program's arrays, the step values and the data go into one buffer of the context; queued on the context's stream, not waited for.
+// step_values: (T, data_dim, n_step) STEP values that go with THIS data instead of the armed ones (the posterior predictive tabulates the
+// program for observation values that are no data of the fit); NULL: the armed ones.
 void build_program_table(blhip_ctx *ctx, int ndim, const int64_t *n, const double *const *d_marginal, int64_t T, int data_dim,
-                         const double *data, double *d_lik) {
+                         const double *data, double *d_lik, const double *step_values = nullptr) {
     const blhip_ctx::LikProgram &LP = ctx->likprog;
     if (ctx->option("lik_program", 1.0) == 0.0) fail("BLHIP_OM_PROGRAM: option lik_program = 0 keeps the caller-evaluated table (BLHIP_OM_TABLE)");
     if (!LP.armed) fail("BLHIP_OM_PROGRAM: no likelihood program is armed (blhip_set_lik_program)");
@@ -190,7 +192,8 @@ void build_program_table(blhip_ctx *ctx, int ndim, const int64_t *n, const doubl
     const int64_t n_ops = (int64_t)LP.ops.size() / 2, n_consts = (int64_t)LP.consts.size();
     char msg[256] = "";
     if (bllp::check_program(LP.ops.data(), n_ops, n_consts, LP.n_step, ndim, msg, (int)sizeof msg) != 0) fail("%s", msg);
-    if ((int64_t)LP.step.size() != T * data_dim * LP.n_step)
+    const size_t n_stepv = (size_t)(T * data_dim * LP.n_step);
+    if (!step_values && (int64_t)LP.step.size() != T * data_dim * LP.n_step)
         fail("BLHIP_OM_PROGRAM: the armed program carries %lld step values, the problem needs (T, data_dim, n_step) = (%lld, %d, %lld)",
              (long long)LP.step.size(), (long long)T, data_dim, (long long)LP.n_step);
     long long G = 1;
@@ -205,14 +208,14 @@ void build_program_table(blhip_ctx *ctx, int ndim, const int64_t *n, const doubl
     hipStream_t st = ctx->stream;
     const size_t nd = (size_t)T * data_dim;
     ctx->likprog_dev.ensure(carve_size(LP.ops.size() * 4) + carve_size(std::max<size_t>(1, LP.consts.size()) * 8) +
-                            carve_size(std::max<size_t>(1, LP.step.size()) * 8) + carve_size(nd * 8));
+                            carve_size(std::max<size_t>(1, n_stepv) * 8) + carve_size(nd * 8));
     char *cur = ctx->likprog_dev.as<char>();
     bllp::Instr *d_ops = carve<bllp::Instr>(cur, (size_t)n_ops);
-    double *d_consts = carve<double>(cur, std::max<size_t>(1, LP.consts.size())), *d_step = carve<double>(cur, std::max<size_t>(1, LP.step.size())),
+    double *d_consts = carve<double>(cur, std::max<size_t>(1, LP.consts.size())), *d_step = carve<double>(cur, std::max<size_t>(1, n_stepv)),
            *d_data = carve<double>(cur, nd);
     HIPCHECK(hipMemcpyAsync(d_ops, LP.ops.data(), LP.ops.size() * 4, hipMemcpyHostToDevice, st));
     if (!LP.consts.empty()) HIPCHECK(hipMemcpyAsync(d_consts, LP.consts.data(), LP.consts.size() * 8, hipMemcpyHostToDevice, st));
-    if (!LP.step.empty()) HIPCHECK(hipMemcpyAsync(d_step, LP.step.data(), LP.step.size() * 8, hipMemcpyHostToDevice, st));
+    if (n_stepv) HIPCHECK(hipMemcpyAsync(d_step, step_values ? step_values : LP.step.data(), n_stepv * 8, hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(d_data, data, nd * 8, hipMemcpyHostToDevice, st));
     bllp::LikProgParams P{};
     P.ops = d_ops; P.consts = d_consts; P.G = G; P.n_ops = (int)n_ops; P.n_step = (int)LP.n_step; P.dd = data_dim; P.ndim = ndim;

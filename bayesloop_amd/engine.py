@@ -117,6 +117,78 @@ class DevicePosterior:
     def time_average(self):
         return self.engine.time_average(self.source, self.chain, self.grid_size)
 
+    HOST_ROW_BYTES = 1 << 28     # likelihood rows evaluated on the host travel in pieces of at most this many bytes
+
+    def _program(self, om):
+        """The density of `om` as a likelihood program the engine takes, or None (as Study._likelihoodProgram)."""
+        eng = self.engine
+        if not getattr(eng, 'lik_programs', False) or getattr(eng, 'options', {}).get('lik_program', 1.0) == 0:
+            return None
+        if om.segmentLength != 1 or not om.multiplyLikelihoods:
+            return None
+        make = getattr(om, 'likelihoodProgram', None)
+        return make() if make is not None else None
+
+    def __getattr__(self, name):
+        # `predictive` exists where the engine contracts on the device: Study.simulate asks with hasattr, as it does for row / time_average,
+        # and an engine without it (the test doubles) leaves simulate on the host path
+        if name == 'predictive' and hasattr(self.__dict__.get('engine'), 'predictive'):
+            return self._predictive
+        raise AttributeError(name)
+
+    def _predictive(self, om, marginal, x, index=None, grid=None):
+        """sum over the grid of om.pdf(grid, [x_j]) * posterior -- the sum inside Study.simulate (reference core.py:566-597) -- for the 1-D
+        array of finite observation values `x`, contracted on the device: nothing but the result leaves it.  index: a row of the sequence
+        -> (len(x),); None / 'avg': its time average -> (len(x),); 'all': every row -> (T, len(x)).  The likelihood rows are built on the
+        device where the library has the density (built-in models, likelihood programs) and with ``om.pdf`` on the host otherwise."""
+        from .observationModels import device_code
+        x = _f64(x).ravel()
+        marginal = [_f64(m) for m in marginal]
+        if index is None or (isinstance(index, str) and index == 'avg'):
+            rng, shape = (0, self.T, True), (x.size,)
+        elif isinstance(index, str) and index == 'all':
+            rng, shape = (0, self.T, False), (self.T, x.size)
+        else:
+            rng, shape = (int(index), int(index) + 1, False), (x.size,)
+        out = np.empty((self.T if len(shape) == 2 else 1, x.size))
+        if x.size == 0:
+            return out.reshape(shape)
+        code = device_code(om)
+        device = np.ones(x.size, dtype=bool)          # values whose likelihood row the device builds
+        x_step, problem_code = None, code
+        if code == _abi.OM_TABLE:
+            prog = self._program(om)
+            if prog is not None:
+                problem_code = _abi.OM_PROGRAM
+                ops, consts = prog.bind(marginal)
+                self.engine.set_lik_program(ops, consts, np.zeros((0, 1, prog.n_step)))      # (the STEP values travel with x)
+                x_step = prog.step_values(x.reshape(-1, 1)).reshape(x.size, -1)
+            else:
+                device[:] = False
+        elif code == _abi.OM_POISSON:
+            # the direct formula lambda ** k exp(-lambda) / k! with k! as a double: whole, non-negative counts up to 170 (171! is no double)
+            device = (x >= 0) & (x == np.floor(x)) & (x <= 170)
+            import math
+            x_step = np.array([float(math.factorial(int(k))) if ok else 0.0 for k, ok in zip(x, device)])
+        elif code not in (_abi.OM_GAUSSIAN, _abi.OM_BERNOULLI, _abi.OM_LAPLACE, _abi.OM_WHITE_NOISE):
+            device[:] = False
+        on = np.flatnonzero(device)
+        if on.size:
+            xs = None if x_step is None else np.ascontiguousarray(x_step[on])
+            out[:, on] = self.engine.predictive(self.source, self.chain, marginal, problem_code, np.ascontiguousarray(x[on]), rng[0], rng[1], rng[2], x_step=xs)
+        off = np.flatnonzero(~device)
+        if off.size:
+            if grid is None:
+                grid = [m for m in np.meshgrid(*marginal, indexing='ij')]
+            G = int(np.prod(self.grid_size))
+            step = max(1, self.HOST_ROW_BYTES // (8 * G))
+            for a in range(0, off.size, step):
+                cols = off[a:a + step]
+                rows = np.array([np.asarray(om.pdf(grid, [xi]), dtype=float) * np.ones(self.grid_size) for xi in x[cols]]).reshape(len(cols), G)
+                out[:, cols] = self.engine.predictive(self.source, self.chain, marginal, _abi.OM_TABLE, np.ascontiguousarray(x[cols]), rng[0], rng[1], rng[2],
+                                                      host_rows=rows)
+        return out.reshape(shape)
+
 
 class _PinnedPool:
     """Result arrays of the big read-backs (posteriorSequence: (T, *gridSize) float64, 16 GiB for BASELINE C3) in PAGE-LOCKED host
@@ -450,6 +522,39 @@ class HipEngine:
         out = np.empty(list(grid_size))
         self._check(self.lib.blhip_posterior_time_average(self.ctx, source, chain, _abi.dptr(out)))
         return out
+
+    def predictive(self, source, chain, marginal, obs_model, x, t0, t1, average, x_step=None, host_rows=None):
+        """(t1 - t0, len(x)) -- or (1, len(x)) with `average` -- sums over the grid of L(x_j | cell) * sequence[t][cell]
+        (blhip_posterior_predictive, include/blhip.h).  marginal / obs_model: the grid and the C-ABI code of the observation model;
+        x_step: k! per value (Poisson) or the (len(x), n_step) STEP values of the armed program; host_rows: (len(x), G) likelihood rows the
+        caller evaluated."""
+        x = _f64(x).ravel()
+        ms = [_f64(m) for m in marginal]
+        cp = _abi.Problem()
+        cp.ndim, cp.obs_model = len(ms), int(obs_model)
+        for k, m in enumerate(ms):
+            cp.n[k] = len(m)
+            cp.marginal[k] = _abi.dptr(m)
+        xs = None if x_step is None else _f64(x_step)
+        rows = None
+        if host_rows is not None:
+            rows = _f64(host_rows)
+            if rows.size != x.size * int(np.prod([len(m) for m in ms])):
+                raise BackendError('predictive: host_rows is not (len(x), G)')
+        out = np.empty((1 if average else int(t1) - int(t0), x.size))
+        self._check(self.lib.blhip_posterior_predictive(self.ctx, int(source), int(chain), int(t0), int(t1), 1 if average else 0, C.byref(cp), _abi.dptr(x),
+                                                        x.size, _abi.dptr(xs), _abi.dptr(rows), _abi.dptr(out)))
+        return out
+
+    @staticmethod
+    def predictive_plan(G, T, X, average=False, budget=float(1 << 62)):
+        """blhip_host_predictive_plan as a dict (no GPU needed); None for a budget below the plan's minimum."""
+        out = (C.c_int64 * 6)()
+        rc = _abi.load().blhip_host_predictive_plan(int(G), int(T), int(X), 1 if average else 0, float(budget), out)
+        if rc < 0:
+            raise BackendError('predictive_plan: bad arguments')
+        plan = dict(zip(('slab', 'n_slabs', 'rows_per_chunk', 'n_chunks', 'workspace_bytes', 'min_budget_bytes'), [int(v) for v in out]))
+        return plan if rc == 0 else None
 
     def release_posterior(self, owner=None):
         """Forget who owns the device-resident results (they will not be copied to the host when overwritten)."""

@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define BLHIP_ABI_VERSION 9
+#define BLHIP_ABI_VERSION 10
 
 typedef struct blhip_ctx blhip_ctx;
 
@@ -269,6 +269,34 @@ int blhip_posterior_release(blhip_ctx *ctx);
 int blhip_posterior_marginal(blhip_ctx *ctx, int source, int64_t chain, int keep_axis, double *host_out);
 /* host_out is (G,): mean over time steps of the posterior. */
 int blhip_posterior_time_average(blhip_ctx *ctx, int source, int64_t chain, double *host_out);
+
+/* ---- posterior predictive (ABI v10; Study.simulate, bayesloop/core.py:566-597) ------------------------------------------------------
+ *   host_out[t - t0][j] = sum over the grid cells of  L(x_j | cell) * sequence[t][cell]          t0 <= t < t1,  0 <= j < n_x
+ * or, with average != 0, ONE row: the same sum against the mean of the rows [t0, t1) of the sequence (the whole sequence: t0 = 0, t1 = T).
+ * Probabilities times likelihood values: no lattice constant, no normalisation over x -- the caller's, as in the reference.
+ * source / chain: as blhip_posterior_marginal.  The contraction runs on the fp64 matrix pipe (blhip_predictive.hpp), split over slabs of
+ * cells whose partial results are added in a fixed order: two calls on the same inputs return the same bits.
+ * model: only obs_model, ndim, n[] and marginal[] are read (and the program the context is armed with, for BLHIP_OM_PROGRAM); the product
+ * of n[] must be the number of cells of the sequence.  Where the likelihood rows L(x_j | .) come from:
+ *   host_rows != NULL                      the caller's, (n_x, G) doubles on the host (any ObservationModel.pdf); uploaded chunk by chunk
+ *   BLHIP_OM_GAUSSIAN, BLHIP_OM_POISSON    tabulated on the device from the formulas of observationModels.py:502 / :566-567.  Poisson: x_step
+ *                                          holds k! of every value as a double, (n_x); values whose k! is no finite double, that are
+ *                                          negative or no whole numbers belong to host_rows (the call refuses them)
+ *   BLHIP_OM_BERNOULLI / _LAPLACE / _WHITE_NOISE   the kernel that builds their likelihood table for a fit, with x as the data
+ *   BLHIP_OM_PROGRAM                       the armed program with x as the data; x_step: its STEP values, (n_x, n_step) (NULL: n_step = 0)
+ *   anything else                          host_rows is required
+ * The rows of a chunk of x values and the partial results live in a workspace of the context that stays within option mem_budget_bytes
+ * (blhip_host_predictive_plan); x itself must be finite unless host_rows is given (then it is not read and may be NULL).
+ * Errors (return -1, blhip_last_error; the context stays usable): no posterior kept / chain out of range / accumulator not finalised,
+ * t0 < 0 or t1 > T or t0 >= t1, n_x < 1, a grid that does not match the sequence, a NULL model / x / host_out, a model that needs
+ * host_rows, a budget below the plan's minimum. */
+int blhip_posterior_predictive(blhip_ctx *ctx, int source, int64_t chain, int64_t t0, int64_t t1, int average, const blhip_problem *model,
+                               const double *x, int64_t n_x, const double *x_step, const double *host_rows, double *host_out);
+/* The plan of such a call, host-only (no GPU, no context): G cells, T output rows (1 with average), X values, `budget` bytes.
+ * plan_out (6 values): cells per slab of the split over the cell axis, slabs (= blocks along it), x values per chunk, chunks, workspace
+ * bytes (<= budget), the smallest budget accepted.  Slab s covers the cells [s * slab, min(G, (s + 1) * slab)), chunk c the values
+ * [c * rows, min(X, (c + 1) * rows)).  Returns 0; -1 for bad arguments; 1 for a budget below the minimum (plan_out[5] is still written). */
+int blhip_host_predictive_plan(int64_t G, int64_t T, int64_t X, int average, double budget, int64_t *plan_out);
 
 /* ---- evidence-weighted average posterior (HyperStudy) ----------------------------------------------------------- */
 /* The accumulator holds  A[t, cell] = sum_h exp(logE_h + log prior_h - log_ref) * max(post_h[t, cell], 1e-300)
