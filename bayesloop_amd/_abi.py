@@ -12,7 +12,7 @@ import os
 from .exceptions import BackendError
 
 LIB_NAME = 'libblhip.so'
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 OM_POISSON, OM_GAUSSIAN, OM_GAUSSIAN_MEAN, OM_TABLE = 1, 2, 3, 100
 OM_BERNOULLI, OM_LAPLACE, OM_WHITE_NOISE, OM_AR1, OM_SCALED_AR1 = 4, 5, 6, 7, 8
@@ -131,6 +131,12 @@ PROTOTYPES = {
     'blhip_host_lik_program_check': (C.c_int, [C.POINTER(C.c_int32), C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_char_p, C.c_int]),
     'blhip_lik_program_eval': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(c_double_p), C.c_int64, C.c_int, c_double_p,
                                          c_double_p]),
+    'blhip_mix_sequence': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, c_double_p, C.c_int]),
+    'blhip_mix_means': (C.c_int, [C.c_void_p, C.POINTER(Problem), c_double_p]),
+    'blhip_mix_read': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, c_double_p]),
+    'blhip_carry_copy': (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    'blhip_mem_budget': (C.c_int, [C.c_void_p, c_double_p]),
+    'blhip_host_online_block_plan': (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int64, C.c_double, C.POINTER(C.c_int64)]),
     'blhip_host_taps': (C.c_int64, [C.c_int, C.c_int64, c_double_p, C.c_int, c_double_p, C.c_int64, C.POINTER(C.c_int)]),
 }
 

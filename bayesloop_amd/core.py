@@ -1379,6 +1379,7 @@ class OnlineStudy(HyperStudy):
         for history in ('hyperParameterSequence', 'transitionModelSequence', 'localTransitionModelSequence'):
             setattr(self, history, [])
         self._slots = []            # carry slot of every transition model in the engine's context
+        self._backupSlots = []      # ... and the slots stepMany keeps the states in that a time chunk resumed from
         self._device = []           # per transition model: (ops, op_values, reset prior, indep prior)
         if not silent:
             print('  --> Online study')
@@ -1395,7 +1396,7 @@ class OnlineStudy(HyperStudy):
     def __del__(self):
         try:
             eng = _engine_mod.get_engine()
-            for s in self._slots:          # (every instance allocates its own slots: a copy never shares them)
+            for s in self._slots + self.__dict__.get('_backupSlots', []):          # (every instance allocates its own slots: a copy never shares them)
                 eng.carry_release(s)
         except Exception:
             pass
@@ -1412,6 +1413,7 @@ class OnlineStudy(HyperStudy):
                        for s, c in zip(self._slots, self.tmCounts)]
         state['_carried'] = carried
         state['_slots'] = []
+        state['_backupSlots'] = []
         return state
 
     def __setstate__(self, state):
@@ -1598,6 +1600,237 @@ class OnlineStudy(HyperStudy):
             self.localTransitionModelSequence.append(self.localTransitionModelDistribution.copy())
         if self.firstStep:
             self.firstStep = False
+
+    # ---- a block of data points (a recorded series replayed through the online study) ------------------------------------
+    BLOCK_MIN_POINTS = 4        # fewer points to filter than this: stepMany is the loop over step
+
+    def stepMany(self, dataPoints):
+        """Update every chain with a block of data points: ``dataPoints`` of shape (N,) -- (N, d) for multi-dimensional data -- leaves the
+        study where ``for d in dataPoints: self.step(d)`` leaves it, histories included.
+
+        Every chain is an independent forward filter; the competing models meet only in the evidence bookkeeping and in the
+        evidence-weighted mixture.  So per transition model the block is ONE resumed, carried fit over its steps (no host round trip
+        between steps): evidence-only, or forward-only with the sequence kept on the device when the study stores its history -- the
+        mixtures of all steps are then formed there (``HipEngine.mix_sequence``) and read back once.  A block whose sequence does not fit
+        the memory budget is cut along time; the carried states make the seam exact.  A chunk in which a chain meets a zero normaliser
+        is repeated point by point through :meth:`step` from the states carried into it.  Engine option ``online_block = 0``, or fewer than
+        ``BLOCK_MIN_POINTS`` points to filter: the loop."""
+        pts = np.asarray(dataPoints)
+        N = len(pts)
+        if N == 0:
+            return
+        eng = _engine_mod.get_engine()
+        if getattr(eng, 'options', {}).get('online_block', 1.0) == 0:
+            for d in pts:
+                self.step(d)
+            return
+        start, waited = 0, False
+        if self.tmCount is None or len(self.rawData) == 0:
+            # the first point of a stream goes through step's own bookkeeping: its checks, its messages, the start of the raw series
+            self._takeDataPoint(pts[0])
+            if len(self.rawData) >= self.observationModel.segmentLength:
+                # (a point the block filters: taken back, the block below puts it behind the raw series again)
+                self.rawData, self.rawTimestamps = self.rawData[:-1], self.rawTimestamps[:-1]
+            else:
+                start, waited = 1, True
+        om = self.observationModel
+        L = om.segmentLength
+        # points in front of a full segment only wait, as in step: they join the raw series and nothing else happens
+        k = min(N - start, max(0, L - 1 - len(self.rawData)))
+        if k > 0:
+            self._appendRaw(pts[start:start + k])
+            start, waited = start + k, True
+        if waited:
+            print('+ Not enough data points to start analysis. Will wait for more data.')
+        pts = pts[start:]
+        N = len(pts)
+        if N < self.BLOCK_MIN_POINTS:
+            # (a block has a fixed cost -- the block programs, the copy of the carried states, the ranged read-backs -- that the loop has
+            #  not: measured break-even between 2 and 4 points, profiles/online_block_notes.md)
+            for d in pts:
+                self.step(d)
+            return
+        n0 = len(self.rawData)
+        # the raw series with the block behind it, and the block's data segments as Study._formatData forms them
+        raw_all = np.append(self.rawData, pts, axis=0)
+        ts_all = np.append(self.rawTimestamps, (self.rawTimestamps[-1] + 1 if n0 > 0 else 0) + np.arange(N))
+        segments = movingWindow(raw_all[n0 - (L - 1):], L)
+        nTM = len(self.transitionModels)
+
+        if self.firstStep:
+            if not 1 <= len(self.gridSize) <= _abi.MAX_DIM:
+                raise ConfigurationError('The MI355X engine supports observation models with 1 to {} parameters '
+                                         '(got {}).'.format(_abi.MAX_DIM, len(self.gridSize)))
+            self._prior = self._computePrior(silent=False)
+            if self.transitionModelPrior is None:
+                self.transitionModelPrior = np.ones(nTM) / nTM
+                if nTM > 1:
+                    print('    + Set flat transition model prior.')
+            dV = np.prod(self.latticeConstant)
+            self.logEvidenceList = [np.zeros(tmc) + np.log(dV) for tmc in self.tmCounts]
+            self.hyperLogEvidenceList = np.array([0. for tmc in self.tmCounts])
+            self.hyperParameterDistribution = [np.zeros(tmc) for tmc in self.tmCounts]
+            self.transitionModelDistribution = np.zeros(nTM)
+            self.localTransitionModelDistribution = np.zeros(nTM)
+            self._compileModels()
+
+        # time chunks: the kept sequence of the widest model + the history planes within the memory budget
+        planes = 0 if not self.storeHistory else (1 if nTM == 1 else 1 + nTM)
+        per_chunk = max(1, int(eng.online_block_steps(self.gridSize, max(self.tmCounts), planes, N)))
+        backup = self.__dict__.setdefault('_backupSlots', [])      # (a study pickled before it had any)
+        programs = {}
+        t = 0
+        while t < N:
+            Tc = min(per_chunk, N - t)
+            if Tc not in programs:
+                programs[Tc] = self._compileBlock(Tc)
+            # the states this chunk resumes from stay until it is done (a zero normaliser repeats it through step)
+            if not self.firstStep:
+                while len(backup) < nTM:
+                    OnlineStudy._slot_counter[0] += 1
+                    backup.append(OnlineStudy._slot_counter[0])
+                for s, b in zip(self._slots, backup):
+                    eng.carry_copy(s, b)
+            ok = self._stepChunk(eng, programs[Tc], segments[t:t + Tc], planes, last=t + Tc == N)
+            if ok:
+                self.rawData, self.rawTimestamps = raw_all[:n0 + t + Tc], ts_all[:n0 + t + Tc]
+                self.formattedTimestamps.extend(ts_all[n0 + t:n0 + t + Tc])
+                self.firstStep = False
+            else:
+                self.rawData, self.rawTimestamps = raw_all[:n0 + t], ts_all[:n0 + t]
+                if self.firstStep:
+                    for s in self._slots:          # (step compiles the models, and takes slots, itself)
+                        eng.carry_release(s)
+                    self._slots = []
+                else:
+                    for s, b in zip(self._slots, backup):
+                        eng.carry_copy(b, s)
+                for d in pts[t:t + Tc]:
+                    self.step(d)
+            t += Tc
+
+    def _appendRaw(self, pts):
+        if len(pts) > 0:
+            self.rawData = np.append(self.rawData, pts, axis=0)
+            self.rawTimestamps = np.append(self.rawTimestamps, self.rawTimestamps[-1] + 1 + np.arange(len(pts)))
+
+    def _compileBlock(self, T):
+        """Per transition model: (ops, op values) of a T-step block.  Every transition of an online study is evaluated at time stamp -1
+        (step: ``resume_time=-1.0``), so every time stamp of the block is -1 too: a ChangePoint whose value lies inside the block's index
+        range restarts nothing, a Deterministic model shifts by the same amount at every step."""
+        om = self.observationModel
+        out = []
+        for tm, hpv in zip(self.transitionModels, self.hyperParameterValues):
+            self.setTransitionModel(tm, silent=True)
+            program = self._expandProgram(tm._program(om.parameterNames), T)
+            op_values = self._opValueMatrix(program, np.asarray(hpv, dtype=float) if len(hpv) > 0 else np.zeros((1, 0)),
+                                            timestamps=np.full(T, -1.0), resume_time=-1.0)
+            out.append(([(op[0], op[1], op[4], op[5]) for op in program], op_values))
+        return out
+
+    def _stepChunk(self, eng, programs, segments, planes, last):
+        """One time chunk of a block: the fits, the evidence bookkeeping of step (reference core.py:2167-2214) vectorised over the chunk's
+        steps in the loop's order of operations, the mixtures.  -> False (and nothing of the study touched but the carried states) when a
+        chain met a zero normaliser."""
+        om = self.observationModel
+        T = len(segments)
+        nTM = len(self.transitionModels)
+        data = np.asarray(segments, dtype=float)
+        # the likelihood as Study.fit builds it: in-kernel models, device-built tables, likelihood programs; a host table otherwise
+        code = device_code(om)
+        lik = lik_program = None
+        prog = self._likelihoodProgram(om) if code == _abi.OM_TABLE else None
+        if prog is not None:
+            code = _abi.OM_PROGRAM
+            lp_ops, lp_consts = prog.bind(self.marginalGrid)
+            lik_program = (lp_ops, lp_consts, prog.step_values(data.reshape(len(data), -1)))
+        elif code == _abi.OM_TABLE:
+            lik = np.array([np.asarray(om.processedPdf(self.grid, seg), dtype=float) * np.ones(self.gridSize) for seg in segments])
+        dV = np.prod(self.latticeConstant)
+        history = self.storeHistory
+        stamps = np.full(T, -1.0)
+
+        def fit(i):
+            ops, op_values = programs[i]
+            _, _, reset, indep = self._device[i]
+            problem = FitProblem(obs_model=code, marginal=self.marginalGrid, lattice=self.latticeConstant, data=data, timestamps=stamps,
+                                 prior=self._prior, ops=ops, reset_prior=reset, indep_prior=indep, lik=lik, lik_program=lik_program,
+                                 seg_len=om.segmentLength, resume_time=-1.0, carry_slot=self._slots[i])
+            res = eng.fit(problem, op_values, evidence_only=not history, forward_only=history, keep_posterior=history,
+                          resume=not self.firstStep, carry=True)
+            return None if np.any(res.abort_step >= 0) else res
+
+        def book(i, local):
+            """-> (logEvidenceList, hyperLogEvidenceList, hyper-parameter distributions) of model i at every step: (T, C), (T,), (T, C)"""
+            with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+                lni = np.log(np.ascontiguousarray(local.T) / dV)                                                      # core.py:2167
+                LE = np.add.accumulate(np.concatenate((self.logEvidenceList[i][None, :], lni), axis=0), axis=0)[1:]   # :2170, in step order
+                x = LE + np.log(self.hyperPriorValues[i])[None, :]                                                   # :2171
+                m = np.amax(x, axis=1)
+                hle = np.where(np.isfinite(m), m, 0.0)
+                hle = hle + np.log(np.sum(np.exp(x - hle[:, None]), axis=1))                                          # :2178 logsumexp
+                hpd = np.exp(x - m[:, None])                                                                         # :2184-2186
+                hpd /= np.sum(hpd, axis=1)[:, None]
+                if len(self.hyperGridConstants[i]) > 0:
+                    hpd /= np.prod(self.hyperGridConstants[i])                                                       # :2187-2188
+            return LE, hle, hpd
+
+        def finish(books):
+            """The bookkeeping across models (:2179-2181, :2199-2214) -> (T, nTM) distributions and the (T,) evidences."""
+            with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+                hle = np.ascontiguousarray(np.array([b[1] for b in books]).T)                                        # (T, nTM)
+                old = np.concatenate((np.asarray(self.hyperLogEvidenceList, dtype=float)[None, :], hle[:-1]), axis=0)
+                ltd = hle - old + np.log(self.transitionModelPrior)[None, :]
+                tmd = np.exp(hle - np.amax(hle, axis=1)[:, None])
+                tmd /= np.sum(tmd, axis=1)[:, None]
+                ltd = np.exp(ltd - np.amax(ltd, axis=1)[:, None])
+                ltd /= np.sum(ltd, axis=1)[:, None]
+                x = hle + np.log(self.transitionModelPrior)[None, :]
+                m = np.amax(x, axis=1)
+                logE = m + np.log(np.sum(np.exp(x - m[:, None]), axis=1))
+            return hle, tmd, ltd, logE
+
+        scale = [np.prod(self.hyperGridConstants[i]) for i in range(nTM)]
+        books = []
+        for i in range(nTM):
+            res = fit(i)
+            if res is None:
+                return False
+            books.append(book(i, res.local_evidence))
+            if history and nTM > 1:
+                # the next model's fit overwrites the kept sequence, and the distribution over models needs every model's evidence: one
+                # history plane per model, weighted with the model's own hyper-parameter distribution (known now) ...
+                eng.mix_sequence(books[i][2] * scale[i], plane=1 + i, n_planes=1 + nTM)
+        hle, tmd, ltd, logE = finish(books)
+        if history and nTM > 1:
+            eng.mix_sequence(tmd, plane=0, n_planes=1 + nTM, source=1)          # ... and the planes mixed with the distribution over models
+        elif history:
+            eng.mix_sequence(books[0][2] * scale[0] * tmd[:, [0]])              # (one model: its probability is 1, or NaN where the loop's is)
+
+        for i in range(nTM):
+            self.logEvidenceList[i] = books[i][0][-1].copy()
+            self.hyperParameterDistribution[i] = books[i][2][-1].copy()
+        self.hyperLogEvidenceList = hle[-1].copy()
+        self.transitionModelDistribution = tmd[-1].copy()
+        self.localTransitionModelDistribution = ltd[-1].copy()
+        self.logEvidence = float(logE[-1])
+
+        if history:
+            seq = eng.mix_read(T, self.gridSize)
+            means = eng.mix_means(self.marginalGrid, T)
+            self.marginalizedPosterior = seq[-1].copy()
+            for k in range(T):
+                self.posteriorMeanValues.append(means[k].copy())
+                self.posteriorSequence.append(seq[k].copy())
+                self.hyperParameterSequence.append([b[2][k].copy() for b in books])
+                self.transitionModelSequence.append(tmd[k].copy())
+                self.localTransitionModelSequence.append(ltd[k].copy())
+        elif last:
+            for i in range(nTM):
+                w = self.hyperParameterDistribution[i] * scale[i] * self.transitionModelDistribution[i]
+                eng.carry_mix(self._slots[i], w, accumulate=i > 0)
+            self.marginalizedPosterior = eng.carry_read(0, -1, self.gridSize)
+        return True
 
     # ---- device-resident per-chain results, fetched on demand -----------------------------------------------------------
     @property

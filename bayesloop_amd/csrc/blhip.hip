@@ -47,6 +47,7 @@
 #include "blhip_chain_nd.hpp"
 #include "blhip_likprog.hpp"
 #include "blhip_predictive.hpp"
+#include "blhip_online.hpp"
 
 using namespace blk;
 
@@ -627,7 +628,7 @@ void blhip_destroy(blhip_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     (void)blhip_comm_destroy(ctx);
-    ctx->commbuf.release(); ctx->pinC.release(); ctx->resx.release(); ctx->postpad.release(); ctx->accw.release(); ctx->accpart.release(); ctx->xch.release(); ctx->axlik.release(); ctx->anchbuf.release(); ctx->probebuf.release(); ctx->p1d.release(); ctx->p1w.release(); ctx->lik1d.release(); ctx->likprog_dev.release(); ctx->predws.release(); ctx->predx.release();
+    ctx->commbuf.release(); ctx->pinC.release(); ctx->resx.release(); ctx->postpad.release(); ctx->accw.release(); ctx->accpart.release(); ctx->xch.release(); ctx->axlik.release(); ctx->anchbuf.release(); ctx->probebuf.release(); ctx->p1d.release(); ctx->p1w.release(); ctx->lik1d.release(); ctx->likprog_dev.release(); ctx->predws.release(); ctx->predx.release(); ctx->mixseq.release(); ctx->mixw.release();
     for (DevBuf *b : {&ctx->state, &ctx->post, &ctx->psumF, &ctx->psumB, &ctx->redF, &ctx->redB, &ctx->meta,
                       &ctx->tables, &ctx->likbuf, &ctx->small, &ctx->accum_own, &ctx->stats, &ctx->mix, &ctx->unit, &ctx->databuf, &ctx->postinv})
         b->release();
@@ -809,7 +810,7 @@ int blhip_set_option(blhip_ctx *ctx, const char *key, double value) {
     static const char *const known[] = {
         "carry_partials", "chain1d", "chain1d_clamp", "chain1d_long", "chain1d_shift", "chain_ax1", "chain_clamp", "chain_depad", "chain_prof", "chain_resident", "chain_resident_lag",
         "chain_force_fail_batch", "chain_force_fail_stage", "chain_nd", "chain_table", "chain_wide", "comm_reduce_mode", "fast", "fast_S", "fold2", "fold2_cp", "fold_force_fail_batch", "fuse1d", "fuse_accumulate", "late_sums", "lik_program", "max_batch",
-        "mem_budget_bytes", "mfma", "mfma_S", "mfma_h", "mfma_h_max_cells", "peer_copy_mode", "persist1d", "predictive", "quiet", "recurrence", "resident",
+        "mem_budget_bytes", "mfma", "mfma_S", "mfma_h", "mfma_h_max_cells", "online_block", "peer_copy_mode", "persist1d", "predictive", "quiet", "recurrence", "resident",
         "resident_force_abort", "resident_lag", "resident_probe", "resident_probe_force_busy", "resident_probe_interval_s", "resident_probe_timeout_s",
         "resident_table", "resident_timeout_s", "share_prefix", "short_first_batch", "skip_prefix", "trace", "wide_h",
         "wide_h_fused_max", "wide_h_split", "wide_v"};
@@ -1306,18 +1307,17 @@ namespace {
 // behind them); d_inv: T doubles of device scratch
 struct RowStats { double *red, *d_inv; };      // red: (T, RS_W) page-locked, + T spare doubles behind it
 constexpr int RS_W = 1 + bln::MAXD;
-RowStats accum_row_stats(blhip_ctx *ctx, const blhip_problem *p) {
-    if (!ctx->acc_active) fail("no active accumulator");
+// (A: any (T, G) array on the device -- the accumulator, or plane 0 of the history of an online block)
+RowStats seq_row_stats(blhip_ctx *ctx, const blhip_problem *p, const double *A, int64_t T, int64_t G) {
     if (!p) fail("problem is NULL");
     HIPCHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const int64_t T = ctx->acc_T, G = ctx->acc_G;
     bln::NdGrid ng{};
     ng.ndim = p->ndim;
     long long Gp = 1;
     for (int k = p->ndim - 1; k >= 0; --k) { ng.n[k] = (int)p->n[k]; ng.stride[k] = Gp; Gp *= p->n[k]; }
     ng.G = Gp;
-    if (Gp != G) fail("accumulator / grid mismatch");
+    if (Gp != G) fail("sequence / grid mismatch: the problem's grid has %lld cells, the rows %lld", Gp, (long long)G);
     const unsigned gx = (unsigned)std::min<long long>((G + NTHREADS - 1) / NTHREADS, 256);
     size_t bytes = carve_size((size_t)T * RS_W * gx * 8) + carve_size((size_t)T * RS_W * 8) + carve_size((size_t)T * 8);
     for (int k = 0; k < p->ndim; ++k) bytes += carve_size(8 * (size_t)p->n[k]);
@@ -1332,16 +1332,22 @@ RowStats accum_row_stats(blhip_ctx *ctx, const blhip_problem *p) {
         ng.m[k] = dm;
     }
     for_grid_y(ctx, T, [&](long long t0, unsigned nt) {
-        BL_LAUNCH(bln::row_stats_kernel, dim3(gx, nt), dim3(NTHREADS), 0, st, ctx->acc + (size_t)t0 * G, ng, d_part + (size_t)t0 * 5 * gx);
+        BL_LAUNCH(bln::row_stats_kernel, dim3(gx, nt), dim3(NTHREADS), 0, st, A + (size_t)t0 * G, ng, d_part + (size_t)t0 * 5 * gx);
     });
     BL_LAUNCH(reduce_partials_kernel, dim3((unsigned)(T * RS_W)), dim3(NTHREADS), 0, st, d_part, d_red, (int)gx, 0);
     ctx->pinS.ensure((size_t)T * (RS_W + 1) * 8);
     double *red = ctx->pinS.as<double>();
     HIPCHECK(hipMemcpyAsync(red, d_red, (size_t)T * RS_W * 8, hipMemcpyDeviceToHost, st));
     sync_stream(ctx, st);
-    ctx->acc_n0 = p->ndim == 1 ? 1 : (int)p->n[0];
-    ctx->acc_n1 = (int)(G / ctx->acc_n0);
     return RowStats{red, d_inv};
+}
+RowStats accum_row_stats(blhip_ctx *ctx, const blhip_problem *p) {
+    if (!ctx->acc_active) fail("no active accumulator");
+    if (!p) fail("problem is NULL");
+    const RowStats rs = seq_row_stats(ctx, p, ctx->acc, ctx->acc_T, ctx->acc_G);
+    ctx->acc_n0 = p->ndim == 1 ? 1 : (int)p->n[0];
+    ctx->acc_n1 = (int)(ctx->acc_G / ctx->acc_n0);
+    return rs;
 }
 }  // namespace
 
@@ -1400,6 +1406,121 @@ int blhip_accum_end(blhip_ctx *ctx) {
     return guarded(ctx, [&] {
         ctx->acc_active = false;
         ctx->acc = nullptr;
+    });
+}
+
+// ---- blocks of an online study (blhip_online.hpp) ---------------------------------------------------------------------------------
+int blhip_host_online_block_plan(int ndim, const int64_t *n, int64_t chains, int64_t planes, int64_t N, double budget, int64_t *plan_out) {
+    if (!plan_out) return -1;
+    blo::BlockPlan P;
+    const bool ok = blo::online_block_plan(ndim, n, chains, planes, N, budget, P);
+    if (!ok && P.min_budget_bytes == 0) return -1;
+    plan_out[0] = P.steps; plan_out[1] = P.n_chunks; plan_out[2] = P.chunk_bytes; plan_out[3] = P.min_budget_bytes;
+    return ok ? 0 : 1;
+}
+
+int blhip_mem_budget(blhip_ctx *ctx, double *bytes_out) {
+    return guarded(ctx, [&] {
+        if (!bytes_out) fail("blhip_mem_budget: bytes_out is NULL");
+        HIPCHECK(hipSetDevice(ctx->device));
+        size_t free_b = 0, total_b = 0;
+        HIPCHECK(hipMemGetInfo(&free_b, &total_b));
+        // (as chains_per_batch: the context's reusable buffers count as available; the history planes are part of what a block plans)
+        *bytes_out = std::min((double)free_b + (double)ctx->state.cap + (double)ctx->post.cap + (double)ctx->accpart.cap + (double)ctx->mixseq.cap,
+                              ctx->option("mem_budget_bytes", 0.70 * (double)total_b)) * 0.9;
+    });
+}
+
+int blhip_mix_sequence(blhip_ctx *ctx, int source, int64_t plane, int64_t n_planes, int64_t n_chains, int64_t T, const double *weights, int accumulate) {
+    return guarded(ctx, [&] {
+        if (!weights) fail("blhip_mix_sequence: weights is NULL");
+        if (n_planes < 1 || plane < 0 || plane >= n_planes) fail("blhip_mix_sequence: plane %lld of %lld", (long long)plane, (long long)n_planes);
+        HIPCHECK(hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        const double *seq = nullptr;
+        long long cs = 0;
+        int64_t B = 0, Ts = 0, G = 0;
+        if (source == 0) {
+            if (!ctx->post_valid) fail("blhip_mix_sequence: no posterior kept (run blhip_fit with BLHIP_FORWARD_ONLY | BLHIP_KEEP_POSTERIOR)");
+            ensure_post_scaled(ctx);             // (a fit normalises the rows it keeps before it returns: the lazy row scale is 1 here)
+            B = ctx->post_chains; Ts = ctx->post_T; G = ctx->post_G;
+            seq = ctx->post.as<double>(); cs = (long long)Ts * G;
+        } else if (source == 1) {
+            if (plane != 0 || n_planes < 2) fail("blhip_mix_sequence: the planes 1 .. n_planes - 1 are mixed into plane 0");
+            if (ctx->mixseq_planes != n_planes || ctx->mixseq_T < 1) fail("blhip_mix_sequence: the history holds %lld planes, the call names %lld", (long long)ctx->mixseq_planes, (long long)n_planes);
+            B = n_planes - 1; Ts = ctx->mixseq_T; G = ctx->mixseq_G;
+            cs = (long long)Ts * G; seq = ctx->mixseq.as<double>() + cs;
+        } else fail("blhip_mix_sequence: bad source %d", source);
+        if (B != n_chains || Ts != T) fail("blhip_mix_sequence: the sequence has %lld chains x %lld steps, the weights %lld x %lld", (long long)B, (long long)Ts, (long long)n_chains, (long long)T);
+        if (B >= (1ll << 31) || T >= (1ll << 31)) fail("blhip_mix_sequence: too many chains / steps");
+        const bool same = ctx->mixseq_planes == n_planes && ctx->mixseq_T == T && ctx->mixseq_G == G && ctx->mixseq.p;
+        if (!same) {
+            // a new history: nothing of an old one can be accumulated onto or read as another plane
+            if (accumulate || source == 1) fail("blhip_mix_sequence: no history of %lld planes x %lld steps x %lld cells to accumulate onto", (long long)n_planes, (long long)T, (long long)G);
+            ctx->mixseq.ensure((size_t)n_planes * T * G * 8);
+            ctx->mixseq_planes = n_planes; ctx->mixseq_T = T; ctx->mixseq_G = G;
+        }
+        ctx->mixw.ensure((size_t)T * B * 8);
+        HIPCHECK(hipMemcpyAsync(ctx->mixw.p, weights, (size_t)T * B * 8, hipMemcpyHostToDevice, st));
+        blo::MixParams Q{};
+        Q.seq = seq; Q.chain_stride = cs; Q.H = ctx->mixseq.as<double>() + (size_t)plane * T * G; Q.w = ctx->mixw.as<double>();
+        Q.G = G; Q.B = (int)B; Q.accumulate = accumulate ? 1 : 0;
+        // 16-byte loads where every row base allows them: G even makes every row offset (b T + t) G even
+        const bool wide = (G % 2 == 0) && ((uintptr_t)Q.seq & 15) == 0 && ((uintptr_t)Q.H & 15) == 0;
+        const long long per_row = wide ? G / 2 : G;
+        const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((per_row + NTHREADS - 1) / NTHREADS, 4096));
+        for_grid_y(ctx, T, [&](long long y0, unsigned ny) {
+            Q.t0 = y0;
+            if (wide) BL_LAUNCH(blo::mix_sequence_kernel<true>, dim3(gx, ny), dim3(NTHREADS), 0, st, Q);
+            else BL_LAUNCH(blo::mix_sequence_kernel<false>, dim3(gx, ny), dim3(NTHREADS), 0, st, Q);
+        });
+        HIPCHECK(hipGetLastError());
+        sync_stream(ctx, st);                    // (the caller's weights go out of use)
+    });
+}
+
+int blhip_mix_means(blhip_ctx *ctx, const blhip_problem *p, double *host_out) {
+    return guarded(ctx, [&] {
+        if (!host_out) fail("blhip_mix_means: host_out is NULL");
+        if (!p) fail("blhip_mix_means: problem is NULL");
+        if (ctx->mixseq_planes < 1 || !ctx->mixseq.p) fail("blhip_mix_means: no history (blhip_mix_sequence)");
+        if (p->ndim < 1 || p->ndim > BLHIP_MAX_DIM) fail("blhip_mix_means: ndim = %d", p->ndim);
+        for (int k = 0; k < p->ndim; ++k)
+            if (!p->marginal[k] || p->n[k] < 1) fail("blhip_mix_means: bad grid axis %d", k);
+        const int64_t T = ctx->mixseq_T;
+        const double *red = seq_row_stats(ctx, p, ctx->mixseq.as<double>(), T, ctx->mixseq_G).red;
+        for (int64_t t = 0; t < T; ++t)
+            for (int k = 0; k < p->ndim; ++k) host_out[t * p->ndim + k] = red[t * RS_W + 1 + k];
+    });
+}
+
+int blhip_mix_read(blhip_ctx *ctx, int64_t plane, int64_t t0, int64_t t1, double *host_out) {
+    return guarded(ctx, [&] {
+        if (ctx->mixseq_planes < 1 || !ctx->mixseq.p) fail("blhip_mix_read: no history (blhip_mix_sequence)");
+        if (plane < 0 || plane >= ctx->mixseq_planes || t0 < 0 || t1 > ctx->mixseq_T || t0 > t1 || !host_out) fail("blhip_mix_read: bad range");
+        HIPCHECK(hipSetDevice(ctx->device));
+        const int64_t G = ctx->mixseq_G;
+        const char *src = reinterpret_cast<const char *>(ctx->mixseq.as<double>() + ((size_t)plane * ctx->mixseq_T + t0) * G);
+        for_pinned_pieces(host_out, (size_t)(t1 - t0) * G * 8, [&](char *dst, size_t n) {
+            HIPCHECK(hipMemcpyAsync(dst, src + (dst - (char *)host_out), n, hipMemcpyDeviceToHost, ctx->stream));
+        });
+        sync_stream(ctx, ctx->stream);
+    });
+}
+
+int blhip_carry_copy(blhip_ctx *ctx, int src_slot, int dst_slot) {
+    return guarded(ctx, [&] {
+        if (dst_slot < 0 || src_slot == dst_slot) fail("blhip_carry_copy: bad slots %d -> %d", src_slot, dst_slot);
+        auto it = ctx->carry.find(src_slot);
+        if (it == ctx->carry.end() || !it->second.valid) fail("blhip_carry_copy: carry slot %d holds no state", src_slot);
+        HIPCHECK(hipSetDevice(ctx->device));
+        blhip_ctx::Carry &dst = ctx->carry[dst_slot];          // (std::map: inserting leaves `it` valid)
+        const blhip_ctx::Carry &src = it->second;
+        const size_t bytes = (size_t)src.chains * src.G * 8;
+        dst.buf.ensure(bytes);
+        HIPCHECK(hipMemcpyAsync(dst.buf.p, src.buf.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        sync_stream(ctx, ctx->stream);
+        dst.chains = src.chains; dst.G = src.G; dst.maxv = src.maxv; dst.valid = true;
     });
 }
 

@@ -316,6 +316,8 @@ constexpr int CHAIN_R0_MAX = 80;               // widest band of the chain-resid
 constexpr int CHAIN_TALL_ROWS = 1024;         // ... and the one geometry beyond 512 rows: grids of 513 .. 1024 rows (option chain_tall = 0: off)
 inline bool chain_rows_ok(int n0) { return n0 >= CHAIN_MIN_ROWS && n0 <= CHAIN_TALL_ROWS; }
 inline bool chain_tall(int n0) { return n0 > 512 && n0 <= CHAIN_TALL_ROWS; }
+static_assert(blo::PAD_ROWS_MIN == CHAIN_MIN_ROWS && blo::PAD_ROWS_MAX == CHAIN_TALL_ROWS && blo::PAD_COLS == blc::WCOL && blo::PAD_ROWS == 128,
+              "blo::online_block_plan counts a chain's cells as chains_per_batch does");
 
 int64_t chains_per_batch(blhip_ctx *ctx, const blhip_problem *p, const Geometry &g, const FitFlags &ff, int64_t n_chains) {
     const int64_t T = p->T;
@@ -465,7 +467,10 @@ GeometryPlan plan_geometry(blhip_ctx *ctx, const blhip_problem *p, const Geometr
         const bool c1d_fits = long_row ? g.n1 <= bl1c::NMAX_LONG && ctx->option("chain1d_long", 1.0) != 0.0 &&
                                              bl1c::lds_doubles_long(g.n1, prog.LW1, shift1d) * 8 <= 150 * 1024
                                        : bl1c::lds_doubles(g.n1, prog.LW1, shift1d) * 8 <= 150 * 1024;
-        if (gp.fused1d && c1d_mode != 0.0 && !resume && !carry && prog.LW1 < g.n1 && c1d_fits) {
+        // (resumed / carried fits -- blocks of an online study: the forward flavours without clamp stages read step 0 from the carried states
+        //  and leave the last step's row where store_carry takes it; T >= 2 only, so that every one-step call keeps the route it had)
+        const bool c1d_stream_ok = (!resume && !carry) || (T >= 2 && !shift1d);
+        if (gp.fused1d && c1d_mode != 0.0 && c1d_stream_ok && prog.LW1 < g.n1 && c1d_fits) {
             // microseconds per time step of the whole batch, fitted to tools/probe.py chain1d (profiles/r04_notes.md): a block's step =
             // 1.5 us + 1.0 ns per cell (likelihood from the shared table; 2.2 ns with Poisson's pow() in the kernel) + 44 ps per cell and
             // tap (the stencil's operand pairs come out of ONE CU's LDS at ~9 per clock), blocks beyond the chip's capacity queue up;

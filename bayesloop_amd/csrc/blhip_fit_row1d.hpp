@@ -140,6 +140,10 @@ private:
         Q.store = (bwd || !E.ff.evidence_only) ? 1 : 0; Q.means = bwd ? 1 : (E.ff.forward_only ? 1 : 0);
         Q.post = (bwd || !E.ff.evidence_only) ? E.d_post : nullptr; Q.post_stride = (long long)T * E.G;
         Q.src = nullptr; Q.src_stride = 0; Q.dst = nullptr; Q.dst_stride = 0;
+        // a resumed pass: step 0 (source kind SRC_PREV) consumes the carried states, normalised -- the kernel's scale is 1 there; a carried
+        // pass that stores no sequence leaves the last step's row where finish_batch takes it for store_carry (K = 1: the parity of T - 1)
+        if (!bwd && E.ff.resume) { Q.src = E.d_carry_src; Q.src_stride = E.G; }
+        if (!bwd && E.ff.carry && E.ff.evidence_only) { Q.dst = E.d_pp[(T - 1) & 1]; Q.dst_stride = E.G; }
         Q.fwd_sums = bwd ? d_fwd_sums : nullptr;      // (where the forward launch wrote them: the same layout)
         launch_chain1d(E.st, d_lik1 ? BLHIP_OM_TABLE : E.p->obs_model, Q, bwd, 2);
     }

@@ -106,6 +106,10 @@ struct blhip_ctx {
     PinBuf pinA;                 // weights of the average-posterior folds
     PinBuf pinF, pinB, pinS;     // host staging of the reduced sums (forward, backward) and of small read-backs
     int64_t mix_G = 0;
+    // blocks of an online study (blhip_online.hpp): history planes [plane][t][cell] -- plane 0 is the mixture over every chain of every
+    // transition model, the others one model's mixture each -- and the device copy of a call's weights
+    DevBuf mixseq, mixw;
+    int64_t mixseq_T = 0, mixseq_G = 0, mixseq_planes = 0;
     // multi-GPU exchange (blhip_comm.hpp): RCCL communicator of this context's device, staging buffers
     void *comm = nullptr;        // ncclComm_t
     int comm_world = 1, comm_rank = 0;

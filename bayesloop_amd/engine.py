@@ -489,6 +489,65 @@ class HipEngine:
     def carry_release(self, slot=-1):
         self._check(self.lib.blhip_carry_release(self.ctx, int(slot)))
 
+    def carry_copy(self, src_slot, dst_slot):
+        """The carried states of `src_slot` -> `dst_slot`, on the device."""
+        self._check(self.lib.blhip_carry_copy(self.ctx, int(src_slot), int(dst_slot)))
+
+    # ---- blocks of an online study (OnlineStudy.stepMany) ----------------------------------------------------------
+    def mix_sequence(self, weights, plane=0, n_planes=1, source=0, accumulate=False):
+        """history[plane][t] = (accumulate ? history[plane][t] : 0) + sum_b weights[t][b] * seq[b][t]  (blhip_mix_sequence): seq is the
+        sequence the last forward-only fit(keep_posterior=True) left on the device (source 0) or the planes 1 .. n_planes - 1 of the history
+        (source 1, into plane 0).  weights: (T, n_chains)."""
+        w = _f64(weights)
+        if w.ndim != 2:
+            raise BackendError('mix_sequence: weights must be (T, n_chains)')
+        self._check(self.lib.blhip_mix_sequence(self.ctx, int(source), int(plane), int(n_planes), w.shape[1], w.shape[0], _abi.dptr(w),
+                                                1 if accumulate else 0))
+
+    def mix_means(self, marginal, T):
+        """(T, ndim) sums over the grid of history[0][t] * grid_k, reduced on the device."""
+        ms = [_f64(m) for m in marginal]
+        cp = _abi.Problem()
+        cp.ndim = len(ms)
+        for k, m in enumerate(ms):
+            cp.n[k] = len(m)
+            cp.marginal[k] = _abi.dptr(m)
+        out = np.empty((int(T), len(ms)))
+        self._check(self.lib.blhip_mix_means(self.ctx, C.byref(cp), _abi.dptr(out)))
+        return out
+
+    def mix_read(self, T, grid_size, t0=0, t1=None, plane=0):
+        """The rows t0 .. t1-1 of a plane of the history as (t1 - t0, *grid_size): one ranged copy."""
+        t1 = T if t1 is None else t1
+        out = self._pinned.empty([t1 - t0] + list(grid_size))
+        try:
+            self._check(self.lib.blhip_mix_read(self.ctx, int(plane), int(t0), int(t1), _abi.dptr(out)))
+        finally:
+            self._pinned.copied()
+        return out
+
+    def online_block_steps(self, grid_size, chains, planes, N):
+        """Steps per time chunk of a block of N steps whose widest transition model has `chains` chains and whose history takes
+        `planes` planes (0: no history), for this context's memory budget (blhip_host_online_block_plan)."""
+        budget = C.c_double()
+        self._check(self.lib.blhip_mem_budget(self.ctx, C.byref(budget)))
+        plan = self.online_block_plan(grid_size, chains, planes, N, budget.value)
+        if plan is None:
+            raise BackendError('online block: a memory budget of %.0f bytes is below one step of %d chain(s) on this grid '
+                               '(option mem_budget_bytes)' % (budget.value, chains))
+        return plan['steps']
+
+    @staticmethod
+    def online_block_plan(grid_size, chains, planes, N, budget):
+        """blhip_host_online_block_plan as a dict (no GPU needed); None for a budget below one step."""
+        n = (C.c_int64 * len(grid_size))(*[int(v) for v in grid_size])
+        out = (C.c_int64 * 4)()
+        rc = _abi.load().blhip_host_online_block_plan(len(grid_size), n, int(chains), int(planes), int(N), float(budget), out)
+        if rc < 0:
+            raise BackendError('online_block_plan: bad arguments')
+        plan = dict(zip(('steps', 'n_chunks', 'chunk_bytes', 'min_budget_bytes'), [int(v) for v in out]))
+        return plan if rc == 0 else None
+
     def bandwidth_probe(self, nbytes=1 << 30, iterations=20):
         """GB/s (read + write) of a streaming copy on this GPU: the calibrated roofline beside the 8 TB/s spec peak."""
         out = C.c_double()

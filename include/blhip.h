@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define BLHIP_ABI_VERSION 10
+#define BLHIP_ABI_VERSION 11
 
 typedef struct blhip_ctx blhip_ctx;
 
@@ -444,6 +444,37 @@ int blhip_carry_read(blhip_ctx *ctx, int slot, int64_t chain, double *host_out);
  * reference fileIO.py:10-37): host_in is (n_chains, G), every row a normalised distribution. */
 int blhip_carry_write(blhip_ctx *ctx, int slot, int64_t n_chains, int64_t G, const double *host_in);
 int blhip_carry_release(blhip_ctx *ctx, int slot);   /* slot < 0: all slots and the mix buffer */
+
+/* ---- blocks of an online study (ABI v11; OnlineStudy.stepMany of bayesloop_amd: N data points of a recorded series in one call) -------
+ * Every chain of an online study is an independent forward filter, so a block of N points is, per transition model, ONE blhip_fit of N
+ * steps with BLHIP_RESUME | BLHIP_CARRY (every time stamp and resume_time = -1: OnlineStudy evaluates each transition there,
+ * core.py:2164-2165) -- evidence-only, or BLHIP_FORWARD_ONLY | BLHIP_KEEP_POSTERIOR when the study stores its history.  What the
+ * reference forms once per data point (core.py:2194-2211) is then a mixture over chains whose weights change with the time step:
+ *   H[plane][t][cell] = (accumulate ? H[plane][t][cell] : 0) + sum_b weights[t][b] * seq[b][t][cell]      (b ascending, no atomics:
+ *                                                                                     two calls on the same inputs return the same bits)
+ * into a history of n_planes planes of (T, G) cells the context owns.  source 0: seq = the normalised sequence the last forward-only
+ * BLHIP_KEEP_POSTERIOR fit left in the context (n_chains and T must be its chains and steps); source 1: seq = the planes 1 .. n_planes - 1
+ * of the history itself, mixed into plane 0 (n_chains = n_planes - 1) -- a study of M > 1 transition models keeps one plane per model
+ * (weights: the model's hyper-parameter distribution, known once ITS fit is done) and mixes them with the transition-model distribution
+ * when the last model is done.  weights: (T, n_chains) on the host.  A call whose n_planes, T or grid differ from the history's starts a
+ * new one (then accumulate must be 0 and source 0).
+ * blhip_mix_means: host_out (T, ndim) = sum over the cells of plane 0 of H * grid_k (only ndim, n[] and marginal[] of the problem are read).
+ * blhip_mix_read: the rows [t0, t1) of a plane, one ranged copy.
+ * blhip_carry_copy: the carried states of src_slot -> dst_slot on the device (the states a block resumed from, kept until the block is done).
+ * blhip_mem_budget: the bytes a fit's memory plan works with on this context right now (0.9 x min(free + reusable buffers, option
+ * mem_budget_bytes)): what blhip_host_online_block_plan is asked with.
+ * blhip_host_online_block_plan (host only, no GPU, no context): a resumed fit needs all chains of a model in one batch, so a long block is
+ * cut along TIME.  plan_out (4 values): the largest number of steps per chunk for which the kept sequence of a model of `chains` chains
+ * (as a fit's memory plan counts it) plus `planes` history planes fit in `budget` bytes, the number of chunks of a block of N steps, the
+ * bytes of such a chunk, the bytes of a one-step chunk.  Returns 0; -1 for bad arguments; 1 for a budget below one step (plan_out[3] is
+ * still written). */
+int blhip_mix_sequence(blhip_ctx *ctx, int source, int64_t plane, int64_t n_planes, int64_t n_chains, int64_t T, const double *weights,
+                       int accumulate);
+int blhip_mix_means(blhip_ctx *ctx, const blhip_problem *problem, double *host_out);
+int blhip_mix_read(blhip_ctx *ctx, int64_t plane, int64_t t0, int64_t t1, double *host_out);
+int blhip_carry_copy(blhip_ctx *ctx, int src_slot, int dst_slot);
+int blhip_mem_budget(blhip_ctx *ctx, double *bytes_out);
+int blhip_host_online_block_plan(int ndim, const int64_t *n, int64_t chains, int64_t planes, int64_t N, double budget, int64_t *plan_out);
 
 #ifdef __cplusplus
 }
