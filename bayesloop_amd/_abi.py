@@ -12,7 +12,7 @@ import os
 from .exceptions import BackendError
 
 LIB_NAME = 'libblhip.so'
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 OM_POISSON, OM_GAUSSIAN, OM_GAUSSIAN_MEAN, OM_TABLE = 1, 2, 3, 100
 OM_BERNOULLI, OM_LAPLACE, OM_WHITE_NOISE, OM_AR1, OM_SCALED_AR1 = 4, 5, 6, 7, 8
@@ -21,6 +21,8 @@ OM_PROGRAM = 9      # the density as a postfix program (likprogram.py), evaluate
 (LP_CONST, LP_PARAM, LP_DATA, LP_STEP, LP_AXIS, LP_ADD, LP_MUL, LP_DIV, LP_NEG, LP_ABS, LP_SQRT, LP_EXP, LP_LOG, LP_POW, LP_COS, LP_SIN,
  LP_POWI, LP_LT, LP_LE, LP_EQ, LP_AND, LP_SELECT) = range(22)
 LP_MAX_OPS, LP_MAX_STACK, LP_MAX_POWI = 256, 16, 64
+QP_BCOL = 32        # BLHIP_QP_BCOL: the push of a query program for a column of its second space
+QR_LT, QR_LE, QR_EQ, QR_GT, QR_GE = range(5)      # BLHIP_QR_*: the relation of a query against 0
 OP_STATIC, OP_GRW, OP_CHANGEPOINT, OP_REGIMESWITCH, OP_INDEPENDENT, OP_BREAKPOINT, OP_NOTEQUAL = 0, 1, 2, 3, 4, 5, 6
 OP_BIVARIATE, OP_BIVARIATE_ARG, OP_ALPHASTABLE, OP_ALPHASTABLE_ARG = 7, 8, 9, 10
 OP_DETERMINISTIC, OP_DETERMINISTIC_ARG = 11, 12
@@ -75,6 +77,20 @@ class Timing(C.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class Query(C.Structure):
+    """blhip_query: a probability query at many time steps (blhip_posterior_query)."""
+    _fields_ = [
+        ('n_ops', C.c_int32), ('n_consts', C.c_int32), ('n_series', C.c_int32), ('relation', C.c_int32),
+        ('ops', C.POINTER(C.c_int32)), ('consts', c_double_p), ('series', c_double_p),
+        ('ndim', C.c_int32), ('b_const', C.c_int32),
+        ('n', C.c_int64 * MAX_DIM),
+        ('marginal', c_double_p * MAX_DIM),
+        ('n_b', C.c_int64),
+        ('n_bcols', C.c_int32), ('reserved0', C.c_int32),
+        ('b_values', c_double_p), ('b_prob', c_double_p),
+    ]
 
 
 # name -> (restype, argtypes); the single source of truth checked against include/blhip.h by tests/test_abi.py
@@ -137,6 +153,9 @@ PROTOTYPES = {
     'blhip_carry_copy': (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     'blhip_mem_budget': (C.c_int, [C.c_void_p, c_double_p]),
     'blhip_host_online_block_plan': (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int64, C.c_double, C.POINTER(C.c_int64)]),
+    'blhip_posterior_query': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int64), C.c_int64, C.POINTER(Query), c_double_p]),
+    'blhip_host_query_check': (C.c_int, [C.POINTER(Query), C.c_int64, C.c_char_p, C.c_int]),
+    'blhip_host_query_plan': (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_double, C.POINTER(C.c_int64)]),
     'blhip_host_taps': (C.c_int64, [C.c_int, C.c_int64, c_double_p, C.c_int, c_double_p, C.c_int64, C.POINTER(C.c_int)]),
 }
 

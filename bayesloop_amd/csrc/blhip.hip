@@ -48,6 +48,7 @@
 #include "blhip_likprog.hpp"
 #include "blhip_predictive.hpp"
 #include "blhip_online.hpp"
+#include "blhip_query.hpp"
 
 using namespace blk;
 
@@ -628,7 +629,7 @@ void blhip_destroy(blhip_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     (void)blhip_comm_destroy(ctx);
-    ctx->commbuf.release(); ctx->pinC.release(); ctx->resx.release(); ctx->postpad.release(); ctx->accw.release(); ctx->accpart.release(); ctx->xch.release(); ctx->axlik.release(); ctx->anchbuf.release(); ctx->probebuf.release(); ctx->p1d.release(); ctx->p1w.release(); ctx->lik1d.release(); ctx->likprog_dev.release(); ctx->predws.release(); ctx->predx.release(); ctx->mixseq.release(); ctx->mixw.release();
+    ctx->commbuf.release(); ctx->pinC.release(); ctx->resx.release(); ctx->postpad.release(); ctx->accw.release(); ctx->accpart.release(); ctx->xch.release(); ctx->axlik.release(); ctx->anchbuf.release(); ctx->probebuf.release(); ctx->p1d.release(); ctx->p1w.release(); ctx->lik1d.release(); ctx->likprog_dev.release(); ctx->predws.release(); ctx->predx.release(); ctx->queryws.release(); ctx->mixseq.release(); ctx->mixw.release();
     for (DevBuf *b : {&ctx->state, &ctx->post, &ctx->psumF, &ctx->psumB, &ctx->redF, &ctx->redB, &ctx->meta,
                       &ctx->tables, &ctx->likbuf, &ctx->small, &ctx->accum_own, &ctx->stats, &ctx->mix, &ctx->unit, &ctx->databuf, &ctx->postinv})
         b->release();
@@ -810,7 +811,7 @@ int blhip_set_option(blhip_ctx *ctx, const char *key, double value) {
     static const char *const known[] = {
         "carry_partials", "chain1d", "chain1d_clamp", "chain1d_long", "chain1d_shift", "chain_ax1", "chain_clamp", "chain_depad", "chain_prof", "chain_resident", "chain_resident_lag",
         "chain_force_fail_batch", "chain_force_fail_stage", "chain_nd", "chain_table", "chain_wide", "comm_reduce_mode", "fast", "fast_S", "fold2", "fold2_cp", "fold_force_fail_batch", "fuse1d", "fuse_accumulate", "late_sums", "lik_program", "max_batch",
-        "mem_budget_bytes", "mfma", "mfma_S", "mfma_h", "mfma_h_max_cells", "online_block", "peer_copy_mode", "persist1d", "predictive", "quiet", "recurrence", "resident",
+        "mem_budget_bytes", "mfma", "mfma_S", "mfma_h", "mfma_h_max_cells", "online_block", "parser_device", "parser_pair_max", "peer_copy_mode", "persist1d", "predictive", "quiet", "recurrence", "resident",
         "resident_force_abort", "resident_lag", "resident_probe", "resident_probe_force_busy", "resident_probe_interval_s", "resident_probe_timeout_s",
         "resident_table", "resident_timeout_s", "share_prefix", "short_first_batch", "skip_prefix", "trace", "wide_h",
         "wide_h_fused_max", "wide_h_split", "wide_v"};
@@ -1154,6 +1155,97 @@ int blhip_posterior_predictive(blhip_ctx *ctx, int source, int64_t chain, int64_
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipMemcpyAsync(host_out, d_out, (size_t)Tn * n_x * 8, hipMemcpyDeviceToHost, st));
         sync_stream(ctx, st);
+    });
+}
+
+int blhip_host_query_check(const blhip_query *query, int64_t n_steps, char *err, int errlen) { return blq::check_query(query, n_steps, err, errlen); }
+
+int blhip_host_query_plan(int64_t G, int64_t n_steps, int64_t n_series, int64_t n_b, int b_const, int64_t fixed_bytes, double budget, int64_t *plan_out) {
+    if (!plan_out) return -1;
+    blq::QueryPlan P;
+    const bool ok = blq::query_plan(G, n_steps, n_series, n_b, b_const != 0, fixed_bytes, budget, P);
+    if (!ok && P.min_budget_bytes == 0) return -1;
+    plan_out[0] = P.slab; plan_out[1] = P.n_slabs; plan_out[2] = P.steps_per_chunk; plan_out[3] = P.n_chunks;
+    plan_out[4] = P.workspace_bytes; plan_out[5] = P.min_budget_bytes;
+    return ok ? 0 : 1;
+}
+
+int blhip_posterior_query(blhip_ctx *ctx, int source, int64_t chain, const int64_t *steps, int64_t n_steps, const blhip_query *query, double *host_out) {
+    return guarded(ctx, [&] {
+        // ---- everything that can be refused is refused before the first launch
+        if (!host_out) fail("blhip_posterior_query: host_out is NULL");
+        if (!steps) fail("blhip_posterior_query: steps is NULL");
+        char msg[256] = "";
+        if (blq::check_query(query, n_steps, msg, (int)sizeof msg) != 0) fail("blhip_posterior_query: %s", msg);
+        const blhip_query &q = *query;
+        HIPCHECK(hipSetDevice(ctx->device));
+        const SeqView v = sequence_view(ctx, source, chain);
+        for (int64_t s = 0; s < n_steps; ++s)
+            if (steps[s] < 0 || steps[s] >= v.T) fail("blhip_posterior_query: steps[%lld] = %lld is outside the %lld rows of the sequence", (long long)s, (long long)steps[s], (long long)v.T);
+        const long long G = (long long)v.n0 * v.n1;
+        long long Gq = 1;
+        for (int k = 0; k < q.ndim; ++k) Gq *= q.n[k];
+        if (Gq != G) fail("blhip_posterior_query: the grid of the query (%lld cells) does not match the sequence (%lld cells)", Gq, G);
+        const bool pairs = q.n_b > 0, b_const = q.b_const != 0, with_series = q.n_series > 0;
+        // ---- the plan: what does not depend on the step, then the steps of a chunk
+        const size_t nc = (size_t)std::max(1, q.n_consts), nbv = pairs ? std::max<size_t>(1, (size_t)q.n_bcols * q.n_b) : 1;
+        size_t fixed = carve_size((size_t)q.n_ops * 8) + carve_size(nc * 8) + carve_size(nbv * 8) + carve_size((pairs && b_const ? (size_t)q.n_b : 1) * 8);
+        for (int k = 0; k < q.ndim; ++k) fixed += carve_size(8 * (size_t)q.n[k]);
+        size_t free_b = 0, total_b = 0;
+        HIPCHECK(hipMemGetInfo(&free_b, &total_b));
+        const double budget = std::min((double)free_b + (double)ctx->queryws.cap, ctx->option("mem_budget_bytes", 0.70 * (double)total_b)) * 0.9;
+        blq::QueryPlan PL;
+        if (!blq::query_plan(G, n_steps, q.n_series, pairs ? q.n_b : 0, b_const, (long long)fixed, budget, PL))
+            fail("blhip_posterior_query: a workspace budget of %.0f bytes is below the %lld bytes the smallest plan needs", budget, PL.min_budget_bytes);
+        if (PL.n_slabs > 0x7fffffffLL || (PL.steps_per_chunk + blq::SB - 1) / blq::SB > ctx->max_grid_y) fail("blhip_posterior_query: the plan's grid does not fit one launch");
+        ctx->queryws.ensure((size_t)PL.workspace_bytes);
+        char *ws = ctx->queryws.as<char>(), *cur = ws;
+        hipStream_t st = ctx->stream;
+        blq::QueryParams P{};
+        {
+            bllp::Instr *d_ops = carve<bllp::Instr>(cur, (size_t)q.n_ops);
+            double *d_consts = carve<double>(cur, nc), *d_bval = carve<double>(cur, nbv), *d_bconst = carve<double>(cur, pairs && b_const ? (size_t)q.n_b : 1);
+            HIPCHECK(hipMemcpyAsync(d_ops, q.ops, (size_t)q.n_ops * 8, hipMemcpyHostToDevice, st));
+            if (q.n_consts > 0) HIPCHECK(hipMemcpyAsync(d_consts, q.consts, (size_t)q.n_consts * 8, hipMemcpyHostToDevice, st));
+            if (pairs && q.n_bcols > 0) HIPCHECK(hipMemcpyAsync(d_bval, q.b_values, (size_t)q.n_bcols * q.n_b * 8, hipMemcpyHostToDevice, st));
+            if (pairs && b_const) HIPCHECK(hipMemcpyAsync(d_bconst, q.b_prob, (size_t)q.n_b * 8, hipMemcpyHostToDevice, st));
+            for (int k = 0; k < q.ndim; ++k) {
+                double *d = carve<double>(cur, (size_t)q.n[k]);
+                HIPCHECK(hipMemcpyAsync(d, q.marginal[k], 8 * (size_t)q.n[k], hipMemcpyHostToDevice, st));
+                P.m[k] = d;
+                P.n[k] = (int)q.n[k];
+            }
+            P.ops = d_ops; P.consts = d_consts; P.bval = d_bval; P.bprob = d_bconst;
+        }
+        if ((size_t)(cur - ws) != fixed) fail("blhip_posterior_query: internal: the fixed uploads take %lld bytes, planned %lld", (long long)(cur - ws), (long long)fixed);
+        long long *d_steps = reinterpret_cast<long long *>(ws + PL.off_steps);
+        double *d_series = reinterpret_cast<double *>(ws + PL.off_series), *d_bprob = reinterpret_cast<double *>(ws + PL.off_bprob);
+        double *d_part = reinterpret_cast<double *>(ws + PL.off_part), *d_out = reinterpret_cast<double *>(ws + PL.off_out);
+        P.series = d_series; P.steps = d_steps; P.post = v.p; P.part = d_part;
+        P.G = G; P.slab = PL.slab; P.nb = pairs ? q.n_b : 0;
+        P.n_ops = q.n_ops; P.n_series = q.n_series; P.ndim = q.ndim; P.rel = q.relation; P.b_const = b_const ? 1 : 0;
+        if (pairs && !b_const) P.bprob = d_bprob;
+        static_assert(sizeof(long long) == sizeof(int64_t), "steps are uploaded as they come");
+        for (int64_t c0 = 0; c0 < n_steps; c0 += PL.steps_per_chunk) {
+            const int S = (int)std::min<int64_t>(PL.steps_per_chunk, n_steps - c0);
+            HIPCHECK(hipMemcpyAsync(d_steps, steps + c0, (size_t)S * 8, hipMemcpyHostToDevice, st));
+            if (with_series) HIPCHECK(hipMemcpyAsync(d_series, q.series + (size_t)c0 * q.n_series, (size_t)S * q.n_series * 8, hipMemcpyHostToDevice, st));
+            if (pairs && !b_const) HIPCHECK(hipMemcpyAsync(d_bprob, q.b_prob + (size_t)c0 * q.n_b, (size_t)S * q.n_b * 8, hipMemcpyHostToDevice, st));
+            P.S = S;
+            const unsigned ny = (unsigned)((S + blq::SB - 1) / blq::SB);      // (the plan keeps a chunk's step blocks within one launch)
+            const dim3 grid((unsigned)PL.n_slabs, ny);
+            if (pairs) {
+                if (with_series) BL_LAUNCH(blq::query_pairs_kernel<true>, grid, dim3(blq::NT), 0, st, P);
+                else BL_LAUNCH(blq::query_pairs_kernel<false>, grid, dim3(blq::NT), 0, st, P);
+            } else {
+                if (with_series) BL_LAUNCH(blq::query_rows_kernel<true>, grid, dim3(blq::NT), 0, st, P);
+                else BL_LAUNCH(blq::query_rows_kernel<false>, grid, dim3(blq::NT), 0, st, P);
+            }
+            BL_LAUNCH(blq::combine_kernel, dim3((unsigned)((S + blq::NT - 1) / blq::NT)), dim3(blq::NT), 0, st, d_part, d_out, (int)PL.n_slabs, S, pairs ? 1 : 0);
+            HIPCHECK(hipGetLastError());
+            HIPCHECK(hipMemcpyAsync(host_out + c0, d_out, (size_t)S * 8, hipMemcpyDeviceToHost, st));
+            sync_stream(ctx, st);       // (the chunk's uploads are overwritten by the next one)
+        }
     });
 }
 

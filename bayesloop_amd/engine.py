@@ -134,7 +134,13 @@ class DevicePosterior:
         # and an engine without it (the test doubles) leaves simulate on the host path
         if name == 'predictive' and hasattr(self.__dict__.get('engine'), 'predictive'):
             return self._predictive
+        if name == 'query' and hasattr(self.__dict__.get('engine'), 'posterior_query'):      # (the same for the parser's vector of time stamps)
+            return self._query
         raise AttributeError(name)
+
+    def _query(self, steps, ops, consts, relation, marginal, **spaces):
+        """Probabilities of a parser query at the rows `steps` of this sequence, summed on the device (HipEngine.posterior_query)."""
+        return self.engine.posterior_query(self.source, self.chain, steps, ops, consts, relation, marginal, **spaces)
 
     def _predictive(self, om, marginal, x, index=None, grid=None):
         """sum over the grid of om.pdf(grid, [x_j]) * posterior -- the sum inside Study.simulate (reference core.py:566-597) -- for the 1-D
@@ -613,6 +619,49 @@ class HipEngine:
         if rc < 0:
             raise BackendError('predictive_plan: bad arguments')
         plan = dict(zip(('slab', 'n_slabs', 'rows_per_chunk', 'n_chunks', 'workspace_bytes', 'min_budget_bytes'), [int(v) for v in out]))
+        return plan if rc == 0 else None
+
+    def posterior_query(self, source, chain, steps, ops, consts, relation, marginal, series=None, b_values=None, b_prob=None, b_const=False):
+        """(len(steps),) probabilities of ``f REL 0`` at the rows `steps` of a device-resident sequence (blhip_posterior_query,
+        include/blhip.h): ops (n_ops, 2) int32 and consts are the program f, relation a _abi.QR_* code, marginal the grid of the sequence;
+        series (len(steps), n_series) its STEP values; b_values (n_bcols, n_b) / b_prob ((1 if b_const else len(steps)), n_b) the second,
+        independent space of a pair query."""
+        steps = np.ascontiguousarray(steps, dtype=np.int64).ravel()
+        ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 2)
+        consts = _f64(consts).ravel()
+        ms = [_f64(m) for m in marginal]
+        q = _abi.Query()
+        q.n_ops, q.n_consts, q.relation = len(ops), consts.size, int(relation)
+        q.ops, q.consts = ops.ctypes.data_as(C.POINTER(C.c_int32)), _abi.dptr(consts)
+        q.ndim = len(ms)
+        for k, m in enumerate(ms):
+            q.n[k] = len(m)
+            q.marginal[k] = _abi.dptr(m)
+        keep = [ops, consts, ms]
+        if series is not None:
+            series = _f64(series).reshape(steps.size, -1)
+            q.n_series, q.series = series.shape[1], _abi.dptr(series)
+            keep.append(series)
+        if b_prob is not None:
+            b_prob = _f64(b_prob)
+            b_prob = b_prob.reshape(1 if b_const else steps.size, -1)
+            b_values = _f64(np.zeros((0, b_prob.shape[1])) if b_values is None else b_values).reshape(-1, b_prob.shape[1])
+            q.n_b, q.n_bcols, q.b_const = b_prob.shape[1], b_values.shape[0], 1 if b_const else 0
+            q.b_values, q.b_prob = _abi.dptr(b_values), _abi.dptr(b_prob)
+            keep += [b_values, b_prob]
+        out = np.empty(steps.size)
+        self._check(self.lib.blhip_posterior_query(self.ctx, int(source), int(chain), steps.ctypes.data_as(C.POINTER(C.c_int64)), steps.size, C.byref(q),
+                                                   _abi.dptr(out)))
+        return out
+
+    @staticmethod
+    def query_plan(G, n_steps, n_series=0, n_b=0, b_const=False, fixed_bytes=0, budget=float(1 << 62)):
+        """blhip_host_query_plan as a dict (no GPU needed); None for a budget below the plan's minimum."""
+        out = (C.c_int64 * 6)()
+        rc = _abi.load().blhip_host_query_plan(int(G), int(n_steps), int(n_series), int(n_b), 1 if b_const else 0, int(fixed_bytes), float(budget), out)
+        if rc < 0:
+            raise BackendError('query_plan: bad arguments')
+        plan = dict(zip(('slab', 'n_slabs', 'steps_per_chunk', 'n_chunks', 'workspace_bytes', 'min_budget_bytes'), [int(v) for v in out]))
         return plan if rc == 0 else None
 
     def release_posterior(self, owner=None):

@@ -22,6 +22,13 @@ Semantics kept from the reference (file:line refer to bayesloop/parser.py):
 
 Not kept: the reference prints debugging output while binning (:404-406) and needs ``pyparsing``; only the time steps a query
 selects are copied from the GPU (``DevicePosterior.row``) instead of the whole posterior sequence.
+
+Added: ``t='all'`` or a list / tuple / 1-D array of time stamps evaluates a query at every one of them in ONE call, and
+``series={name: values}`` binds a name to a number per time stamp -- the loops of the reference's tutorials
+(``[P('rho < 0.', t=t, silent=True) for t in range(1, 389)]``, ``P('(mu - ' + str(mu0[t]) + ')/sigma > 1', t=t, silent=True)``).
+Entry i of the result is by definition ``P(query, t=t[i], silent=True)``.  A probability query whose plan has one or two index
+spaces is summed on the GPU while the posterior sequence lives there (the plan: further down; the kernels:
+bayesloop_amd/csrc/blhip_query.hpp); every other query is the loop over the scalar call.
 """
 from __future__ import annotations
 
@@ -71,7 +78,8 @@ class _Quantity:
         return q
 
 
-def _tokenize(text, names, functions):
+def _tokenize(text, names, functions, numbers=None):
+    """numbers: names bound to a number for this call (the series of a vector-t query at one step); they shadow functions."""
     tokens, i = [], 0
     while i < len(text):
         ch = text[i]
@@ -90,7 +98,9 @@ def _tokenize(text, names, functions):
         m = _NAME.match(text, i)
         if m:
             word = m.group(0)
-            if word in names:
+            if numbers and word in numbers:
+                tokens.append(('num', numbers[word]))
+            elif word in names:
                 tokens.append(('name', word))
             elif word in functions:
                 tokens.append(('func', word))
@@ -230,10 +240,7 @@ class Parser:
         if kind == 'func':
             fn = getattr(np, val) if hasattr(np, val) and callable(getattr(np, val)) else getattr(_sp, val)
             operand, pos = self._applied(tokens, pos + 1, quantities)
-            if isinstance(operand, _Quantity):
-                with np.errstate(all='ignore'):
-                    return operand.with_values(fn(operand.values)), pos
-            return fn(operand), pos
+            return self._apply(fn, val, operand), pos
         if kind == 'num':
             return val, pos + 1
         if kind == 'name':
@@ -246,6 +253,12 @@ class Parser:
         if (kind, val) in (('op', '+'), ('op', '-')):                        # a sign directly behind a function / "@"
             return self._signed(tokens, pos, quantities)
         raise ConfigurationError('Unexpected "{}" in query.'.format(val))
+
+    def _apply(self, fn, name, operand):
+        if isinstance(operand, _Quantity):
+            with np.errstate(all='ignore'):
+                return operand.with_values(fn(operand.values))
+        return fn(operand)
 
     def _arith(self, sym, a, b):
         op = _ARITH[sym]
@@ -278,14 +291,25 @@ class Parser:
         return True
 
     # ---- queries -----------------------------------------------------------------------------------------------------
-    def __call__(self, query, t=None, silent=False):
+    def __call__(self, query, t=None, silent=False, series=None):
+        """t: a time stamp, None, 'all' (every time stamp of the first study) or a list / tuple / 1-D array of time stamps.  With a vector
+        of time stamps a probability query returns the (len(t),) array whose entry i is ``self(query, t=t[i], silent=True)``, a
+        distribution query the list of those results.  series: {name: array of len(t)} binds names to a number that changes with the time
+        stamp (entry i at t[i]) -- the numeric token a loop over time stamps would format into the query."""
+        if _is_vector(t):
+            return self._call_many(query, t, silent, series)
+        if series is not None:
+            raise ConfigurationError('series binds a name to one number per time stamp: it needs t="all" or a sequence of time stamps.')
+        return self._call_one(query, t, silent)
+
+    def _call_one(self, query, t, silent, numbers=None):
         quantities = self._load(t)
         parts = re.split('>=|<=|==|>|<', query)
         if len(parts) > 2:
             raise ConfigurationError('Use exactly one operator out of (<, >, <=, >=, ==) to obtain probability value, '
                                      'or none to obtain derived distribution.')
         reduced = query if len(parts) == 1 else '-1*(' + parts[1] + ')+' + parts[0]
-        tokens = _tokenize(reduced, set(self.names), self.functions)
+        tokens = _tokenize(reduced, set(self.names), self.functions, numbers)
         derived, pos = self._expression(tokens, 0, quantities)
         if pos != len(tokens):
             raise ConfigurationError('Cannot parse query behind "{}".'.format(tokens[pos][1]))
@@ -317,6 +341,407 @@ class Parser:
         ok = ~np.isnan(values) & (index >= 0) & (index < n_bins - 1)
         binned = np.bincount(index[ok], weights=prob[ok], minlength=max(n_bins - 1, 0))[:max(n_bins - 1, 0)]
         return bins[:-1] + (bins[1] - bins[0]), binned
+
+    # ---- a vector of time stamps ---------------------------------------------------------------------------------------
+    def _stamps(self, t):
+        if isinstance(t, str):
+            return list(self.studies[0].formattedTimestamps)                  # 'all': the first study's stamps, the rule for t (:291)
+        return np.asarray(t).ravel().tolist() if isinstance(t, np.ndarray) else list(t)
+
+    def _series(self, series, n):
+        out = {}
+        for name, values in (series or {}).items():
+            if name in self.names:
+                raise ConfigurationError('Series name "{}" collides with a (hyper-)parameter name.'.format(name))
+            if not _NAME.fullmatch(str(name)):
+                raise ConfigurationError('Series name "{}" is no name the query language can use.'.format(name))
+            v = np.asarray(values, dtype=float)
+            if v.ndim != 1 or v.size != n:
+                raise ConfigurationError('Series "{}" needs one value per time stamp ({}), got shape {}.'.format(name, n, v.shape))
+            if not np.all(np.isfinite(v)):
+                raise ConfigurationError('Series "{}" contains values that are not finite.'.format(name))
+            if name in self.functions:
+                print('! WARNING: Function "{}" will not be available in this query, as it collides with a series name.'.format(name))
+            out[name] = v
+        return out
+
+    def _loop(self, query, stamps, series):
+        """The scalar call at every time stamp: the definition of the vector call and the path of every query the device does not take."""
+        return [self._call_one(query, ts, True, {k: float(v[i]) for k, v in series.items()} or None) for i, ts in enumerate(stamps)]
+
+    def plan(self, query, t='all', series=None, pair_max=None):
+        """The query plan of a probability query with a vector of time stamps (:class:`QueryPlan`); ``plan.reason`` says why a query
+        stays on the host loop (None: the device takes it if the sequence of ``plan.study`` is resident there)."""
+        stamps = self._stamps(t)
+        return _plan(self, query, stamps, self._series(series, len(stamps)), pair_max)
+
+    def _call_many(self, query, t, silent, series):
+        stamps = self._stamps(t)
+        series = self._series(series, len(stamps))
+        relational = len(re.split('>=|<=|==|>|<', query)) == 2
+        out = None
+        if relational and len(stamps) > 0:
+            out = self._device_query(query, stamps, series)
+        if out is None:
+            out = self._loop(query, stamps, series)
+            if relational:
+                out = np.array(out, dtype=float)
+        if not silent:
+            if relational and len(stamps) > 0:
+                print('P({}) at {} time steps: min = {}, max = {}'.format(query, len(stamps), np.nanmin(out), np.nanmax(out)))
+            else:
+                print('+ Computed {} at {} time steps'.format(query, len(stamps)))
+        return out
+
+    def _device_query(self, query, stamps, series):
+        """The probabilities from the device, or None: the plan does not fit it, no study of the plan has its sequence there, or the
+        engine has no such path (option parser_device = 0, the test doubles)."""
+        candidates = [getattr(s, '_posterior_pending', None) for s in self.studies]
+        candidates = [p for p in candidates if p is not None and hasattr(p, 'query')]
+        if not candidates:
+            return None
+        options = getattr(getattr(candidates[0], 'engine', None), 'options', {})
+        if options.get('parser_device', 1.0) == 0:
+            return None
+        try:
+            plan = _plan(self, query, stamps, series, options.get('parser_pair_max', PAIR_MAX))
+        except (ConfigurationError, ValueError):
+            return None                              # (the loop raises what the scalar call raises)
+        if plan.reason is not None:
+            return None
+        pending = getattr(plan.study, '_posterior_pending', None)
+        if pending is None or not hasattr(pending, 'query') or list(pending.grid_size) != [len(m) for m in plan.marginal]:
+            return None
+        return pending.query(plan.steps, plan.ops, plan.consts, plan.relation, plan.marginal, **plan.spaces_kwargs())
+
+
+def _is_vector(t):
+    if isinstance(t, str):
+        return t == 'all'
+    if isinstance(t, np.ndarray):
+        if t.ndim > 1:
+            raise ConfigurationError('t takes a 1-D array of time stamps, got shape {}.'.format(t.shape))
+        return t.ndim == 1
+    return isinstance(t, (list, tuple))
+
+
+# ---- the plan of a probability query at many time stamps ---------------------------------------------------------------------------------
+# A vector-t probability query is a weighted count: the sum, over the product of its index spaces, of the product of the spaces'
+# probabilities wherever lhs - rhs REL 0 holds.  The plan walks the expression ONCE with symbolic quantities through the very
+# precedence-climbing and the very _arith / _independent rules of the scalar call, and assigns every node an index space:
+#   * the parameters of one study (at the one time stamp of the step) share the space of that study's grid;
+#   * the hyper-parameters of one study share the space of its hyper-grid (an OnlineStudy: one space per transition model);
+#   * every outer product opens a new space, and -- the scalar call's quirk, kept -- anything combined with a derived quantity is
+#     independent of it: a third space.
+# The device (bayesloop_amd/csrc/blhip_query.hpp) takes one space (A, a parameter grid whose sequence is resident there) or two (A x B, B
+# held by the host).  Every maximal subtree that depends on ONE axis of A, on B alone or on the series alone is evaluated HERE, with the
+# NumPy / scipy.special calls the scalar call uses, and enters the program as a table; only nodes that mix axes or spaces are interpreted on
+# the device, and only + - * / ^ abs sqrt exp log cos sin can be.  Everything else stays on the loop over the scalar call.
+# default of engine option parser_pair_max, the largest G_a * G_b the pair kernel takes: the largest pair space measured (8000 x 8000 cells;
+# the kernel was 13 to 326 times faster than the loop at every size from 50 x 50 up, profiles/parser_query_notes.md) -- no break-even was found
+PAIR_MAX = 6.4e7
+_DEVICE_FUNCS = {'abs': 'ABS', 'absolute': 'ABS', 'fabs': 'ABS', 'sqrt': 'SQRT', 'exp': 'EXP', 'log': 'LOG', 'cos': 'COS', 'sin': 'SIN'}
+_REL_CODES = {'<': 0, '<=': 1, '==': 2, '>': 3, '>=': 4}
+_SET = object()                # stands for "probabilities selected" in a symbolic quantity
+
+
+class _NoPlan(Exception):
+    def __init__(self, reason, n_spaces=None):
+        Exception.__init__(self, reason)
+        self.reason, self.n_spaces = reason, n_spaces
+
+
+class _Steps:
+    """A number that changes with the step: one Python float per step, combined float by float, as the loop over scalar calls does."""
+
+    def __init__(self, v):
+        self.v = [float(x) for x in v]
+
+
+def _number_node(x):
+    return ('steps', x.v) if isinstance(x, _Steps) else ('const', x)
+
+
+class _Sym(_Quantity):
+    """A quantity of the plan: its expression tree and index space instead of values and probabilities."""
+
+    def __init__(self, node, space, name, kind, study, time):
+        _Quantity.__init__(self, np.zeros(1), prob=_SET, name=name, time=time, study=study, kind=kind)
+        self.node, self.space = node, space
+
+    def copy(self):
+        return _Sym(self.node, self.space, self.name, self.kind, self.study, self.time)
+
+    def over(self, node):
+        return _Sym(node, self.space, self.name, self.kind, self.study, self.time)
+
+
+class _Planner(Parser):
+    def __init__(self, parser):
+        self.studies, self.names, self.functions = parser.studies, parser.names, parser.functions
+        self.pair = None           # the two spaces of the one outer product a device plan may hold
+
+    def _apply(self, fn, name, operand):
+        if isinstance(operand, _Sym):
+            return operand.over(('fn', name, fn, operand.node))
+        if isinstance(operand, _Steps):
+            with np.errstate(all='ignore'):
+                return _Steps([fn(x) for x in operand.v])
+        return fn(operand)
+
+    def _arith(self, sym, a, b):
+        op = _ARITH[sym]
+        qa, qb = isinstance(a, _Sym), isinstance(b, _Sym)
+        if not qa and not qb:
+            with np.errstate(all='ignore'):
+                if isinstance(a, _Steps) or isinstance(b, _Steps):
+                    n = len(a.v) if isinstance(a, _Steps) else len(b.v)
+                    va, vb = (a.v if isinstance(a, _Steps) else [a] * n), (b.v if isinstance(b, _Steps) else [b] * n)
+                    return _Steps([op(x, y) for x, y in zip(va, vb)])
+                return op(a, b)
+        if qa and qb:
+            node = ('op', sym, a.node, b.node)
+            if self._independent(a, b):
+                if self.pair is not None or a.space == b.space:
+                    raise _NoPlan('three or more index spaces', 3)
+                self.pair = (a.space, b.space)
+                return _Sym(node, 'pair', '_derived', 'derived', None, None)
+            if a.space != b.space:
+                raise _NoPlan('hyper-parameters of two transition models of an OnlineStudy combined element by element')
+            return a.over(node)
+        if qa:
+            return a.over(('op', sym, a.node, _number_node(b)))
+        return b.over(('op', sym, _number_node(a), b.node))
+
+
+def _node_text(node):
+    kind = node[0]
+    if kind == 'const':
+        return repr(float(node[1]))
+    if kind == 'steps':
+        return '<series>'
+    if kind == 'leaf':
+        return node[1]
+    if kind == 'fn':
+        return '{}({})'.format(node[1], _node_text(node[3]))
+    return '({} {} {})'.format(_node_text(node[2]), node[1], _node_text(node[3]))
+
+
+def _node_eval(node, env, step=None):
+    """The subtree with the calls of the scalar path: leaves from env (name -> array), a series at `step`."""
+    kind = node[0]
+    if kind == 'const':
+        return node[1]
+    if kind == 'steps':
+        return node[1][step]
+    if kind == 'leaf':
+        return env[node[1]]
+    with np.errstate(all='ignore'):
+        if kind == 'fn':
+            return node[2](_node_eval(node[3], env, step))
+        return _ARITH[node[1]](_node_eval(node[2], env, step), _node_eval(node[3], env, step))
+
+
+class QueryPlan:
+    """What a vector-t probability query needs from the device.  reason: None, or why the query stays on the host loop; n_spaces: index
+    spaces of the query (None: not counted); study: whose parameter grid is space A; steps: rows of its sequence; ops / consts / relation /
+    marginal / series / b_values / b_prob / b_const: the arguments of HipEngine.posterior_query; tables: (kind, text of the subtree) of every
+    subtree evaluated on the host -- kind 'axis<k>', 'b', 'series' or 'const'."""
+
+    def __init__(self, reason=None, n_spaces=None):
+        self.reason, self.n_spaces = reason, n_spaces
+        self.study = None
+        self.steps = self.ops = self.consts = self.relation = self.marginal = self.series = self.b_values = self.b_prob = None
+        self.b_const, self.tables, self.spaces = False, [], []
+
+    def spaces_kwargs(self):
+        kw = {}
+        if self.series is not None:
+            kw['series'] = self.series
+        if self.b_prob is not None:
+            kw.update(b_values=self.b_values, b_prob=self.b_prob, b_const=self.b_const)
+        return kw
+
+
+def _plan(parser, query, stamps, series, pair_max=None):
+    from . import _abi
+    parts = re.split('>=|<=|==|>|<', query)
+    if len(parts) != 2:
+        return QueryPlan('no probability query')
+    try:
+        return _plan_relational(parser, query, parts, stamps, series, pair_max, _abi)
+    except _NoPlan as e:
+        return QueryPlan(e.reason, e.n_spaces)
+
+
+def _plan_relational(parser, query, parts, stamps, series, pair_max, _abi):
+    n_steps = len(stamps)
+    stamps0 = list(parser.studies[0].formattedTimestamps)
+    first = {}
+    for i, ts in enumerate(stamps0):
+        first.setdefault(ts, i)
+    try:
+        steps = np.array([first[ts] for ts in stamps], dtype=np.int64)
+    except (KeyError, TypeError):
+        steps = np.array([stamps0.index(ts) for ts in stamps], dtype=np.int64)      # (ValueError for an unknown stamp, as the scalar call)
+    # ---- symbolic quantities: what _load(t) gives for a scalar t, without values
+    leaves, quantities = {}, {}
+    for study in parser.studies:
+        online = _is_online(study)
+        if online and not getattr(study, 'storeHistory', True):
+            raise _NoPlan('an OnlineStudy without history')
+        for index, name in enumerate(study.observationModel.parameterNames):
+            space = ('param', id(study))
+            leaves[name] = dict(space=space, study=study, axis=index)
+            quantities[name] = _Sym(('leaf', name), space, name, 'param', study, 0)
+        if online:
+            for j, names in enumerate(study.hyperParameterNames):
+                for k, name in enumerate(names):
+                    space = ('hyper', id(study), j)
+                    leaves[name] = dict(space=space, study=study, model=j, values=np.asarray(study.hyperParameterValues[j], dtype=float)[:, list(names).index(name)])
+                    quantities[name] = _Sym(('leaf', name), space, name, 'hyper', study, 0)
+        elif hasattr(study, 'flatHyperParameterNames'):
+            for name in study.flatHyperParameterNames:
+                k = study._getHyperParameterIndex(study.transitionModel, name)
+                grid = getattr(study, 'allHyperGridValues', None)
+                if grid is None or len(grid) == 0:
+                    grid = study.hyperGridValues
+                space = ('hyper', id(study), 0)
+                leaves[name] = dict(space=space, study=study, model=None, values=np.asarray(grid, dtype=float)[:, k])
+                quantities[name] = _Sym(('leaf', name), space, name, 'hyper', study, None)
+    # ---- the expression, walked once
+    planner = _Planner(parser)
+    reduced = '-1*(' + parts[1] + ')+' + parts[0]
+    numbers = {name: _Steps(v) for name, v in series.items()}
+    tokens = _tokenize(reduced, set(parser.names), parser.functions, numbers or None)
+    derived, pos = planner._expression(tokens, 0, quantities)
+    if pos != len(tokens) or not isinstance(derived, _Sym):
+        raise ConfigurationError('Cannot parse query.')                             # (the scalar call says what is wrong)
+    spaces = list(planner.pair) if derived.space == 'pair' else [derived.space]
+    a_space = None
+    for want_resident in (True, False):
+        for sp in spaces:
+            if sp[0] != 'param' or a_space is not None:
+                continue
+            study = next(s for s in parser.studies if id(s) == sp[1])
+            pending = getattr(study, '_posterior_pending', None)
+            if not want_resident or (pending is not None and hasattr(pending, 'query')):
+                a_space = sp
+    if a_space is None:
+        raise _NoPlan('no parameter grid among the index spaces', len(spaces))
+    b_space = next((sp for sp in spaces if sp != a_space), None)
+    plan = QueryPlan(None, len(spaces))
+    plan.spaces = [a_space] + ([b_space] if b_space is not None else [])
+    plan.study = A = next(s for s in parser.studies if id(s) == a_space[1])
+    plan.steps = steps
+    plan.relation = _REL_CODES[next(sym for sym, _ in _RELATIONS if sym in query)]
+    plan.marginal = [np.asarray(m, dtype=float) for m in A.marginalGrid]
+    n_a = [len(m) for m in plan.marginal]
+    if len(n_a) > _abi.MAX_DIM:
+        raise _NoPlan('a grid of more than {} parameters'.format(_abi.MAX_DIM), len(spaces))
+    T_a = len(A.formattedTimestamps)
+    if n_steps and (steps.min() < 0 or steps.max() >= T_a):
+        raise _NoPlan('a time stamp of the first study beyond the sequence of the study queried', len(spaces))
+    n_b = 0
+    if b_space is not None:
+        B = next(s for s in parser.studies if id(s) == b_space[1])
+        n_b = int(np.prod(B.gridSize)) if b_space[0] == 'param' else len(next(l['values'] for l in leaves.values() if l['space'] == b_space))
+        if pair_max is not None and float(np.prod(n_a)) * n_b > pair_max:
+            raise _NoPlan('a pair space of {} x {} cells, above parser_pair_max'.format(int(np.prod(n_a)), n_b), 2)
+
+    # ---- what every node depends on: axes of A, B, the series
+    def deps(node):
+        kind = node[0]
+        if kind == 'const':
+            return frozenset()
+        if kind == 'steps':
+            return frozenset(['S'])
+        if kind == 'leaf':
+            leaf = leaves[node[1]]
+            return frozenset([('A', leaf['axis'])]) if leaf['space'] == a_space else frozenset(['B'])
+        if kind == 'fn':
+            return deps(node[3])
+        return deps(node[2]) | deps(node[3])
+
+    def b_column(name):
+        leaf = leaves[name]
+        return np.ravel(leaf['study'].grid[leaf['axis']]) if leaf['space'][0] == 'param' else leaf['values']
+
+    ops, consts, series_cols, b_cols = [], [], [], []
+
+    def push_const(x):
+        consts.append(float(x))
+        ops.append((_abi.LP_CONST, len(consts) - 1))
+
+    def emit(node):
+        """-> the stack depth the code of this node needs"""
+        d = deps(node)
+        if not d:
+            value = _node_eval(node, {})
+            if node[0] != 'const':
+                plan.tables.append(('const', _node_text(node)))
+            push_const(value)
+            return 1
+        if d == {'S'}:
+            with np.errstate(all='ignore'):
+                series_cols.append([float(_node_eval(node, {}, i)) for i in range(n_steps)])
+            plan.tables.append(('series', _node_text(node)))
+            ops.append((_abi.LP_STEP, len(series_cols) - 1))
+            return 1
+        if d == {'B'}:
+            env = {name: b_column(name) for name, leaf in leaves.items() if leaf['space'] == b_space}
+            b_cols.append(np.asarray(_node_eval(node, env), dtype=float) * np.ones(n_b))
+            plan.tables.append(('b', _node_text(node)))
+            ops.append((_abi.QP_BCOL, len(b_cols) - 1))
+            return 1
+        if len(d) == 1:
+            (_, axis), = d
+            if node[0] == 'leaf':
+                ops.append((_abi.LP_PARAM, axis))
+                return 1
+            env = {name: plan.marginal[axis] for name, leaf in leaves.items() if leaf['space'] == a_space and leaf['axis'] == axis}
+            table = np.asarray(_node_eval(node, env), dtype=float) * np.ones(n_a[axis])
+            plan.tables.append(('axis%d' % axis, _node_text(node)))
+            ops.append((_abi.LP_AXIS, axis | (len(consts) << 2)))
+            consts.extend(table.tolist())
+            return 1
+        if node[0] == 'fn':
+            code = _DEVICE_FUNCS.get(node[1])
+            if code is None or getattr(np, node[1], None) is not node[2]:
+                raise _NoPlan('function "{}" over more than one axis or space'.format(node[1]), len(spaces))
+            depth = emit(node[3])
+            ops.append((getattr(_abi, 'LP_' + code), 0))
+            return depth
+        sym, left, right = node[1], node[2], node[3]
+        if sym == '^' and right[0] == 'const' and right[1] == 2.0:
+            depth = emit(left)                        # NumPy squares by one multiplication
+            ops.append((_abi.LP_POWI, 2))
+            return depth
+        depth = max(emit(left), 1 + emit(right))
+        if sym == '-':
+            ops.append((_abi.LP_NEG, 0))              # a - b = a + (-b), exactly
+        ops.append(({'+': _abi.LP_ADD, '-': _abi.LP_ADD, '*': _abi.LP_MUL, '/': _abi.LP_DIV, '^': _abi.LP_POW}[sym], 0))
+        return depth
+
+    depth = emit(derived.node)
+    if depth > _abi.LP_MAX_STACK or len(ops) > _abi.LP_MAX_OPS:
+        raise _NoPlan('a program of {} ops and stack depth {}'.format(len(ops), depth), len(spaces))
+    plan.ops = np.array(ops, dtype=np.int32).reshape(-1, 2)
+    plan.consts = np.array(consts, dtype=float)
+    if series_cols:
+        plan.series = np.ascontiguousarray(np.array(series_cols, dtype=float).T)
+    # ---- B: its columns and its probabilities at the steps
+    if b_space is not None:
+        plan.b_values = np.array(b_cols, dtype=float).reshape(len(b_cols), n_b)
+        if b_space[0] == 'param':
+            plan.b_prob = np.array([np.ravel(_posterior_row(B, int(i))) for i in steps], dtype=float).reshape(n_steps, n_b)
+        elif _is_online(B):
+            seq, j = B.hyperParameterSequence, b_space[2]
+            plan.b_prob = np.array([np.asarray(seq[int(i)][j], dtype=float) / np.sum(seq[int(i)][j]) for i in steps]).reshape(n_steps, n_b)
+        else:
+            d = np.asarray(B.hyperParameterDistribution, dtype=float)
+            plan.b_prob, plan.b_const = (d / d.sum()).reshape(1, n_b), True
+    return plan
 
 
 def _is_online(study):

@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define BLHIP_ABI_VERSION 11
+#define BLHIP_ABI_VERSION 12
 
 typedef struct blhip_ctx blhip_ctx;
 
@@ -475,6 +475,51 @@ int blhip_mix_read(blhip_ctx *ctx, int64_t plane, int64_t t0, int64_t t1, double
 int blhip_carry_copy(blhip_ctx *ctx, int src_slot, int dst_slot);
 int blhip_mem_budget(blhip_ctx *ctx, double *bytes_out);
 int blhip_host_online_block_plan(int ndim, const int64_t *n, int64_t chains, int64_t planes, int64_t N, double budget, int64_t *plan_out);
+
+/* ---- probability queries at many time steps (ABI v12; bl.Parser / Study.eval with a vector of time stamps, bayesloop/parser.py:256-440,
+ *      core.py:604-621) ----------------------------------------------------------------------------------------------------------------
+ *   one space  (n_b = 0):  host_out[s] = sum over the cells c of A with  f(c, s) REL 0  of  sequence[steps[s]][c]
+ *   two spaces (n_b > 0):  host_out[s] = sum over the pairs (c, j) with  f(c, j, s) REL 0  of  sequence[steps[s]][c] * b_prob[s][j]
+ *                                        divided by  (sum_c sequence[steps[s]][c]) (sum_j b_prob[s][j])        (parser.py:239-243)
+ * A is the parameter grid of the sequence (source / chain: as blhip_posterior_marginal), B a second, independent quantity the caller holds.
+ * f is a postfix program in the instruction set of the likelihood programs (BLHIP_LP_*; no DATA, AND, SELECT) that leaves one value:
+ *   PARAM k   the marginal grid value of parameter k of A at the cell          AXIS   as in a likelihood program: a table along ONE axis of A
+ *   STEP j    series[s][j], the value of the step                               CONST  consts[i]
+ *   BLHIP_QP_BCOL k   b_values[k][j]: a value column of B, or a function of B alone the caller tabulated
+ * One IEEE operation per op, nothing contracted; a NaN compares false.  relation: BLHIP_QR_*.  steps: rows of the sequence in any order,
+ * repeats allowed.  The uploads and the per-slab partial sums live in a workspace of the context that stays within option
+ * mem_budget_bytes (blhip_host_query_plan); a call that does not fit is cut along the steps.  Partial sums are added in a fixed order: two
+ * calls on the same inputs return the same bits.
+ * Validation happens on the host before anything is launched (blhip_host_query_check: the same checks without a context).
+ * Errors (return -1, blhip_last_error; the context stays usable): no posterior kept / chain out of range / accumulator not finalised, a
+ * step out of range, a grid that does not match the sequence, stack or index violations of the program, a NULL pointer, a series value
+ * that is not finite, a budget below the plan's minimum. */
+#define BLHIP_QP_BCOL 32
+enum { BLHIP_QR_LT = 0, BLHIP_QR_LE = 1, BLHIP_QR_EQ = 2, BLHIP_QR_GT = 3, BLHIP_QR_GE = 4 };
+typedef struct blhip_query {
+    int32_t        n_ops, n_consts, n_series, relation;
+    const int32_t *ops;                       /* (n_ops, 2) {code, arg}                                          */
+    const double  *consts;                    /* (n_consts) constants and AXIS tables                            */
+    const double  *series;                    /* (n_steps, n_series) STEP values (NULL: n_series = 0)            */
+    int32_t        ndim, b_const;             /* b_const != 0: b_prob is ONE row, the same at every step         */
+    int64_t        n[BLHIP_MAX_DIM];          /* the grid of A; the product must be the cells of the sequence    */
+    const double  *marginal[BLHIP_MAX_DIM];
+    int64_t        n_b;                       /* cells of B; 0: one space                                        */
+    int32_t        n_bcols, reserved0;
+    const double  *b_values;                  /* (n_bcols, n_b)                                                  */
+    const double  *b_prob;                    /* (b_const ? 1 : n_steps, n_b)                                    */
+} blhip_query;
+int blhip_posterior_query(blhip_ctx *ctx, int source, int64_t chain, const int64_t *steps, int64_t n_steps, const blhip_query *query,
+                          double *host_out);
+/* The checks of a query that need no sequence, host-only (no GPU, no context): 0, or -1 with the message in err. */
+int blhip_host_query_check(const blhip_query *query, int64_t n_steps, char *err, int errlen);
+/* The plan of such a call, host-only: G cells of A, n_steps steps, n_series STEP values per step, n_b cells of B (0: one space), b_const,
+ * fixed_bytes of uploads that do not depend on the step (program, constants, grids, B's columns, a constant b_prob), `budget` bytes.
+ * plan_out (6 values): cells of A per slab, slabs (= blocks along the cells), steps per chunk, chunks, workspace bytes (<= budget), the
+ * smallest budget accepted.  Slab k covers the cells [k * slab, min(G, (k + 1) * slab)), chunk c the steps [c * spc, min(n_steps,
+ * (c + 1) * spc)).  Returns 0; -1 for bad arguments; 1 for a budget below the minimum (plan_out[5] is still written). */
+int blhip_host_query_plan(int64_t G, int64_t n_steps, int64_t n_series, int64_t n_b, int b_const, int64_t fixed_bytes, double budget,
+                          int64_t *plan_out);
 
 #ifdef __cplusplus
 }
