@@ -23,10 +23,14 @@ runs a small forward-backward pass with a running bound for tests/test_likelihoo
 The fourth part restates the host's TAP TABLES (SciPy's Gaussian weights, the alpha-stable and the bivariate kernel, the cardinal-spline weights
 of a small shift) with the bound of a float64 builder, the zero-boundary, dense and small-shift stages with the stencil's truncation term, and
 generalises the small pass to a per-step stage program (transition_fit) for tests/test_step_transitions.py.
+For tests/test_long_series.py the passes take the family's SCALE RULE (tests/scale_rules.py; ScaleHistory): the subnormal step through the scale
+the rule gives a lazily normalised state, and in transition_fit a projective bound that grows linearly along time beside the running one.
 """
 import math
 
 import numpy as np
+
+import scale_rules as sr
 
 U = 2.0 ** -53
 TINY = 2.0 ** -1074      # the subnormal step: below the normal range (2 ** -1022) a rounded product or quotient is off by up to half of it, whatever
@@ -548,6 +552,47 @@ PI_LD = LD(4) * np.arctan(LD(1))
 LAZY_LAG = 4      # steps a kernel's normaliser may lag behind (gaussian_fit: lazy)
 
 
+class ScaleHistory:
+    """The lazy() term of transition_fit (and, through it, gaussian_fit) under a NAMED scale rule (tests/scale_rules.py: 'step', 'launch(K)', 'norm_lag(lag)',
+    'sum_lag(lag)'): TINY / min(1, state scale) wherever a value waits un-normalised, the state scale computed from the reference's own
+    longdouble normalisers by the family's documented rule -- never from a device's output.  Three places, as in the unnamed term:
+        forward_term     the product v L of step k, held at S_k / n_k (its own sum enters in normalise_stage: together TINY / S_k);
+        posterior_term   the STORED forward row of step t (sums to S_t of the forward history) times the backward message (sums to the S of
+                         the backward history's latest step);
+        backward_term    the product beta L of the backward step, as forward_term, along the backward pass's own history.
+    The backward history counts the kernels' steps k = T - 1 - t: step 0 holds the uniform message (normaliser 1).
+    Leaves in out['scale'] what the rule predicts the kernels' sums to be: fwd [T] (S_k), bwd (pass order), post {t: S_t S_bwd sum(alpha_t beta_t)}."""
+
+    def __init__(self, rule, out):
+        self.rule = sr.parse_rule(rule)
+        self.F, self.B = sr.History(self.rule), sr.History(self.rule)
+        self.B.push(LD(1))
+        self.post = {}
+        out['scale'] = dict(rule=self.rule, fwd=self.F.S, bwd=self.B.S, post=self.post)
+
+    @staticmethod
+    def _term(scale):
+        return LD(TINY) / min(LD(1), scale)
+
+    def forward_term(self, fresh, clamped):
+        return self._term(self.F.pre(fresh, clamped))
+
+    def forward_done(self, N, fresh, clamped):
+        self.F.push(N, fresh, clamped)
+
+    def posterior_term(self, t):
+        return LD(TINY) / (min(LD(1), self.F.S[t]) * min(LD(1), self.B.last()))
+
+    def posterior_done(self, t, D):
+        self.post[t] = self.F.S[t] * self.B.last() * D
+
+    def backward_term(self, fresh, clamped):
+        return self._term(self.B.pre(fresh, clamped))
+
+    def backward_done(self, Bt, fresh, clamped):
+        self.B.push(Bt, fresh, clamped)
+
+
 def _values(record):
     return [float(x) for x in np.asarray(record, dtype=np.float64).reshape(-1) if x == x]
 
@@ -666,15 +711,21 @@ def product_stage(a, ea, b, eb, ops=C_CELL):
     return r, e
 
 
-def gaussian_fit(prior, liks, walks, grids, lattice, nblk=1, full=True, clamp=None):
+def gaussian_fit(prior, liks, walks, grids, lattice, nblk=1, full=True, clamp=None, scale=None):
     """core.py:372-470 in longdouble with a running bound.  prior (n0, n1) float64 (taken as given); liks: per step (L, bound of L); walks:
     [(axis, float64 taps)] applied in list order between steps, in both directions (transitionModels.py:107-118); grids: the two marginal
     grids; lattice: the lattice constants; clamp: log10 pMin of a RegimeSwitch behind the walks (:405-412), or None.  -> dict of (value, bound) pairs, bounds WITHOUT SLACK:
         'alpha' [T] normalised forward states, 'norm' [T], 'local_fwd' [T] (norm dV), 'log_evidence',
         full: 'post' [T], 'local' [T] (1 / (sum(post / L) dV); value NaN where a likelihood rounds to 0 in float64), 'means' [T] of (2,)
-        forward-only: 'means' from alpha."""
+        forward-only: 'means' from alpha.
+    scale: None -- the unnamed lazy() term below --, or the family's scale rule (tests/scale_rules.py): the pass is then transition_fit's, over the one
+    program (the walks, then the clamp) for every step, with its term from the rule's state scale, its projective bound and out['scale']."""
     _need_extended()
     T = len(liks)
+    if scale is not None:
+        dV0 = float(np.prod(np.asarray(lattice, dtype=np.float64)))
+        prog = ('prev', [('walk', axis, taps) for axis, taps in walks] + ([('rs', float(10.0 ** clamp * dV0))] if clamp is not None else []))
+        return transition_fit(prior, liks, [dict(fwd=prog, bwd=prog)] * T, grids, lattice, nblk=nblk, full=full, scale=scale)
     dV = LD(float(np.prod(np.asarray(lattice, dtype=np.float64))))
     u = LD(U)
     g = [_ld(_grid_values(grids, k, np.shape(prior))) for k in range(2)]
@@ -1030,13 +1081,43 @@ def apply_stage(st, v, e, nblk=1, sums=None):
     return r, er
 
 
-def transition_fit(prior, liks, steps, grids, lattice, nblk=1, full=True, shared=None):
+def _proj(eps):
+    """the projective (Hilbert) distance log(max x^/x) - log(min x^/x) that a relative perturbation of up to eps per cell can open:
+    log((1 + eps) / (1 - eps)); unbounded from eps = 1"""
+    eps = LD(eps)
+    return np.log1p(eps) - np.log1p(-eps) if eps < 1 else LD(np.inf)
+
+
+def _rel(own, value):
+    """max over the occupied cells of own / |value|.  A cell that is exactly 0 here is exactly 0 in a float64 evaluation too (sums and products
+    of zeros under positive weights and likelihoods), so it opens no distance."""
+    value = np.abs(_ld(value))
+    own = _ld(np.broadcast_to(own, value.shape))
+    m = value > 0
+    return np.max(own[m] / value[m]) if m.any() else LD(0)
+
+
+def _stage_distance(st, vin, vout):
+    """what one stage adds to the projective distance between the device's state and the reference's, or inf where the stage is not a positive
+    linear map (then only the running bound holds).  A walk with positive taps on a non-negative state is one (Birkhoff: it does not expand the
+    distance); its float64 evaluation perturbs every output relatively by (taps + 2) u, by the taps' own relative bound, and by a subnormal
+    step per tap."""
+    if st[0] != 'walk':
+        return LD(np.inf)
+    w = _ld(np.asarray(st[2], dtype=np.float64).reshape(-1))
+    if not (np.all(w > 0) and np.all(_ld(vin) >= 0)):
+        return LD(np.inf)
+    ew = LD(0) if len(st) <= 3 or st[3] is None else np.max(_ld(np.nextafter(np.asarray(st[3], dtype=np.float64), np.inf)).reshape(-1) / w)
+    return _proj((len(w) + 2) * LD(U) + ew + _rel(len(w) * LD(TINY), vout))
+
+
+def transition_fit(prior, liks, steps, grids, lattice, nblk=1, full=True, shared=None, scale=None):
     """core.py:372-470 in longdouble with a running bound, over a per-step stage program (gaussian_fit with one walk list for every step is the
     special case).  prior float64 on the grid (any number of parameters: every stage works along an axis moved to the front); liks: per step (L, bound of L); steps: per step t a dict
         fwd: (source, stages) of the transition INTO step t from t - 1 (unused for t = 0), bwd: the same INTO step t from t + 1 (unused for T - 1)
     source: 'prev' (the neighbour's state), 'reset' / 'indep' (shared[source], float64, as given: transitionModels.py:300-312, :351-360);
     stages: apply_stage's, in list order (:645-649).  -> the dict of gaussian_fit: (value, bound) pairs, bounds WITHOUT SLACK; and 'sums': (D, bound of D) of every renormalising
-    sum of a shift, zero-boundary or dense stage, in the order of the pass."""
+    sum of a shift, zero-boundary or dense stage, in the order of the pass.  scale: as gaussian_fit's; a step whose source is not 'prev' is a restart."""
     _need_extended()
     T = len(liks)
     dV = LD(float(np.prod(np.asarray(lattice, dtype=np.float64))))
@@ -1048,13 +1129,25 @@ def transition_fit(prior, liks, steps, grids, lattice, nblk=1, full=True, shared
     liks = [(L, np.zeros(np.shape(L), dtype=LD) if eL is None else eL) for L, eL in liks]
     out = dict(alpha=[], norm=[], local_fwd=[], post=[], local=[], means=[], sums=[])
 
-    def transition(prog, v, e):
+    def transition(prog, v, e, d=None):
+        """-> (v, e, d): d (only under a named scale rule) is the projective distance of the state, see tighten()"""
         source, stages = prog
         if source != 'prev':
-            v, e = _ld(shared[source]), None
+            v, e, d = _ld(shared[source]), None, (None if d is None else LD(0))
         for st in stages:
+            vin = v
             v, e = apply_stage(st, v, e, nblk, out['sums'])
-        return v, e
+            if d is not None:
+                d = d + _stage_distance(st, vin, v)
+        return v, e, d
+
+    def tighten(r, er, d):
+        """Under a named scale rule the running bound is joined by a second one, and a cell takes the smaller.  The running bound treats the error
+        of every cell as free in sign, and the division by the sum then doubles a relative error at every step (2^13 behind 14 steps) although a
+        common factor cancels there.  In the projective metric a positive linear map does not expand, a product with a positive likelihood and
+        the division by the sum are isometries and the distances of two factors add: the distance d only collects what each step's OWN rounded
+        operations open, and a normalised state is off by at most r (exp(d) - 1) per cell."""
+        return er if not np.isfinite(d) else np.minimum(er, np.abs(r) * np.expm1(d))
 
     def means_of(p, ep):
         m, em = [], []
@@ -1071,17 +1164,38 @@ def transition_fit(prior, liks, steps, grids, lattice, nblk=1, full=True, shared
             worst_p = min(worst_p, prod)
         return LD(1) / worst_p
 
+    sh = None if scale is None else ScaleHistory(scale, out)
+
+    def clamped(prog):
+        """a step whose program clamps (RegimeSwitch, NotEqual) waits for the sum before it: under the lagged-normaliser rule it runs at the exact
+        scale (blhip_chainclamp.hpp, scheme 2); the other rules have no such step"""
+        return sh is not None and sh.rule[0] == 'norm_lag' and prog is not None and any(st[0] in ('rs', 'ne') for st in prog[1])
+
     v, e = _ld(prior), None
     logE, elogE = LD(0), LD(0)
     Ns = []
+    d = None if sh is None else LD(0)                                   # projective distance of the forward state (tighten)
+    dalpha = []
     with np.errstate(under='ignore', over='ignore', invalid='ignore', divide='ignore'):
         for t in range(T):
             if t > 0:
-                v, e = transition(steps[t]['fwd'], v, e)
+                v, e, d = transition(steps[t]['fwd'], v, e, d)
             a, ea = product_stage(v, e, liks[t][0], liks[t][1])
-            ea = ea + LD(TINY) * lazy(Ns[::-1][:LAZY_LAG - 1])
+            fresh = t > 0 and steps[t]['fwd'][0] != 'prev'
+            if sh is None:
+                ea = ea + LD(TINY) * lazy(Ns[::-1][:LAZY_LAG - 1])
+            else:
+                cl = t > 0 and clamped(steps[t]['fwd'])
+                term = sh.forward_term(fresh, cl)
+                ea = ea + term
+                d = d + _proj(C_CELL * u + _rel(liks[t][1], liks[t][0]) + _rel(LD(TINY) + term, a))
             r, er, N, eN = normalise_stage(a, ea, nblk)
             Ns.append(N)
+            if sh is not None:
+                sh.forward_done(N, fresh, cl)
+                d = d + _proj(2 * u + _rel(LD(TINY), r))
+                er = tighten(r, er, d)
+                dalpha.append(d)
             out['alpha'].append((r, er))
             out['norm'].append((N, eN))
             out['local_fwd'].append((N * dV, eN * dV + 2 * u * N * dV))
@@ -1096,11 +1210,17 @@ def transition_fit(prior, liks, steps, grids, lattice, nblk=1, full=True, shared
         beta, eb = np.full(np.shape(prior), LD(1) / LD(G), dtype=LD), np.full(np.shape(prior), u / LD(G), dtype=LD)
         post, local, means = [None] * T, [None] * T, [None] * T
         Bs = []
+        db = None if sh is None else _proj(u)                           # projective distance of the backward message
         for t in range(T - 1, -1, -1):
             L, eL = _ld(liks[t][0]), _ld(liks[t][1])
             p, ep = product_stage(out['alpha'][t][0], out['alpha'][t][1], beta, eb)
-            ep = ep + LD(TINY) * lazy(Ns[:t + 1][::-1]) * lazy(Bs[::-1])
-            p, ep = normalise_stage(p, ep, nblk)[:2]
+            if sh is not None:
+                dp = dalpha[t] + db + _proj(C_CELL * u + _rel(LD(TINY) + sh.posterior_term(t), p))
+            ep = ep + (LD(TINY) * lazy(Ns[:t + 1][::-1]) * lazy(Bs[::-1]) if sh is None else sh.posterior_term(t))
+            p, ep, Dp = normalise_stage(p, ep, nblk)[:3]
+            if sh is not None:
+                sh.posterior_done(t, Dp)
+                ep = tighten(p, ep, dp + _proj(2 * u + _rel(LD(TINY), p)))
             post[t] = (p, ep)
             means[t] = means_of(p, ep)
             if np.any(L.astype(np.float64) == 0.0):
@@ -1115,10 +1235,18 @@ def transition_fit(prior, liks, steps, grids, lattice, nblk=1, full=True, shared
                 local[t] = (val, val * (eS / (S - eS) + 3 * u) + LD(TINY) if S > eS else LD(np.inf))
             if t > 0:
                 b, ebl = product_stage(beta, eb, L, eL)
-                ebl = ebl + LD(TINY) * lazy(Bs[::-1][:LAZY_LAG - 1])
-                b, ebl = transition(steps[t - 1]['bwd'], b, ebl)
+                fresh = steps[t - 1]['bwd'][0] != 'prev'
+                cl = clamped(steps[t - 1]['bwd'])
+                if sh is not None:
+                    db = db + _proj(C_CELL * u + _rel(eL, L) + _rel(LD(TINY) + sh.backward_term(fresh, cl), b))
+                ebl = ebl + (LD(TINY) * lazy(Bs[::-1][:LAZY_LAG - 1]) if sh is None else sh.backward_term(fresh, cl))
+                b, ebl, db = transition(steps[t - 1]['bwd'], b, ebl, db)
                 beta, eb, Bt = normalise_stage(b, ebl, nblk)[:3]
                 Bs.append(Bt)
+                if sh is not None:
+                    sh.backward_done(Bt, fresh, cl)
+                    db = db + _proj(2 * u + _rel(LD(TINY), beta))
+                    eb = tighten(beta, eb, db)
         out['post'], out['local'], out['means'] = post, local, means
     return out
 

@@ -266,9 +266,10 @@ def shifts_of(param, T, driver):
     return fwd, bwd
 
 
-def abi_program(case, driver):
-    """-> (ops, values (chains, n_ops)) in the C-ABI's layout (include/blhip.h)"""
-    T = steps_of(driver)
+def abi_program(case, driver, T=None):
+    """-> (ops, values (chains, n_ops)) in the C-ABI's layout (include/blhip.h); T: the steps, where they are not the driver's own
+    (tests/long_series_cases.py)"""
+    T = steps_of(driver) if T is None else T
     ops, cols = [], []
     for m, seg in zip(case['models'], case['segments']):
         cols.append(len(ops))
@@ -332,9 +333,9 @@ def _taps(kind, *args):
     return _TAPS[key]
 
 
-def stage_program(case, params, driver):
+def stage_program(case, params, driver, T=None):
     """one chain's per-step programs for highprec.transition_fit: [dict(fwd = (source, stages), bwd = (source, stages))] * T"""
-    T, shape = steps_of(driver), case['shape']
+    T, shape = (steps_of(driver) if T is None else T), case['shape']
 
     def program(tau, step, fwd):
         source, stages = 'prev', []

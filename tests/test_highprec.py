@@ -1095,3 +1095,326 @@ def test_what_the_observation_table_leaves_out():
     # every count and every grid the case list has to hold is there
     counts = {int(c) for case in oc.POISSON_CASES for c in oc.poisson_records(case).reshape(-1) if c == c}
     assert {0, 1, 6, 20, 50, 120, 170, 171, 200, 400, 1000, 1000000} <= counts
+
+
+# ---- long series: the scale history as a term of the bound (tests/scale_rules.py, tests/long_series_cases.py, tests/test_long_series.py) -------------
+
+def _small_lazy_problem():
+    rng = np.random.default_rng(791)
+    shape = (6, 5)
+    prior = rng.random(shape)
+    prior /= prior.sum()
+    liks = [((rng.random(shape) + 0.1) * 10.0 ** float(rng.integers(-80, 3)), np.full(shape, 1e-18)) for _ in range(7)]
+    return shape, prior, liks, np.array([0.25, 0.5, 0.25])
+
+
+@needs_extended
+def test_unnamed_lazy_term_is_the_one_before_the_scale_rules():
+    """No bound of an existing test changed: without a `scale` argument gaussian_fit and transition_fit return, bit for bit, the bounds that the
+    file gave BEFORE the argument existed -- recorded then (tests/golden/lazy_term_bounds.npz: every alpha and posterior bound of a 6 x 5 problem
+    over 7 steps whose normalisers reach 1e-80, as float64 (high, low) pairs of the longdouble; sums, products and quotients only, no libm) --
+    and the same for three existing problems of the GPU files."""
+    import os
+    shape, prior, liks, w = _small_lazy_problem()
+    grids = [np.arange(6.0), np.arange(5.0)]
+    a = hp.gaussian_fit(prior, liks, [(0, w), (1, w)], grids, [1.0, 1.0], nblk=2, clamp=-3.0)
+    prog = ('prev', [('walk', 0, w), ('walk', 1, w)])
+    b = hp.transition_fit(prior, liks, [dict(fwd=prog, bwd=prog)] * 7, grids, [1.0, 1.0], nblk=2)
+    then = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'lazy_term_bounds.npz'))
+    for nm, r in (('gaussian', a), ('transition', b)):
+        for key in ('alpha', 'post'):
+            now = np.stack([hp._ld(e) for _, e in r[key]])
+            was = hp._ld(then['%s_%s' % (nm, key)][:, 0]) + hp._ld(then['%s_%s' % (nm, key)][:, 1])
+            assert np.array_equal(now, was), (nm, key)
+    # ... and of three problems of tests/test_step_transitions.py (their `decades` input, where the term is largest): every posterior bound of
+    # the first chain, recorded before the change (tests/golden/lazy_term_bounds_cases.npz)
+    import step_transition_cases as sc
+    then = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'lazy_term_bounds_cases.npz'))
+    for name, kind, driver in (('chain_128x16', 'decades', 'three'), ('resident_32x32', 'decades', 'backward'), ('fused1d_walks_300', 'decades', 'three')):
+        ref = sc.reference(name, kind, driver)[0][0]
+        assert 'scale' not in ref
+        was = then['%s_%s_%s' % (name, kind, driver)]
+        now = np.stack([hp._ld(e) for _, e in ref['post']])
+        assert np.array_equal(now, hp._ld(was[:, 0]) + hp._ld(was[:, 1])), name
+
+
+RULES = [('step',), ('launch', 3), ('launch', 8), ('norm_lag', 2), ('norm_lag', 4), ('sum_lag', 1), ('sum_lag', 2), ('sum_lag', 3)]
+
+
+def _rule_sums_exact(rule, n):
+    """the sums a rule leaves, in rational arithmetic, each from its closed form where it has one (NOT by simulate_sums' recursion)"""
+    T = len(n)
+    if rule[0] == 'step':
+        return list(n)
+    if rule[0] == 'launch':
+        return [math.prod(n[k - k % rule[1]:k + 1]) for k in range(T)]
+    if rule[0] == 'norm_lag':                                   # the product of the last `lag` normalisers (blhip_chainres.hpp)
+        return [math.prod(n[max(0, k - rule[1] + 1):k + 1]) for k in range(T)]
+    S = []
+    for k in range(T):                                          # the lagged sum has no closed form: S_k = S_(k-1) n_k / S_(k-lag)
+        S.append((S[k - 1] if k else F(1)) * n[k] / (S[k - rule[1]] if k >= rule[1] else F(1)))
+    return S
+
+
+@needs_extended
+@pytest.mark.parametrize('rule', RULES, ids=['%s%s' % (r[0], r[1] if len(r) > 1 else '') for r in RULES])
+def test_scale_rule_term_against_exact_arithmetic(rule):
+    """hp.transition_fit on a 3 x 2 grid, T = 8, a walk of three taps, under every scale rule: core.py:372-470 in rational arithmetic from the same float64
+    likelihoods, whose normalisers span 1e-90 .. 1e+40 per step.  The sums the rule predicts (forward, backward in pass order behind the uniform
+    message's 1, and S_fwd S_bwd sum(alpha beta) of every posterior) against their exact values; the three terms TINY / min(1, scale) rebuilt from
+    those exact sums; and every posterior, forward state and local evidence inside its bound."""
+    import scale_rules as sr
+    rng = np.random.default_rng(17)
+    shape, T = (3, 2), 8
+    prior = rng.random(shape)
+    prior /= prior.sum()
+    decades = [-90, 40, -60, -75, 30, -88, 12, -50]
+    liks = [rng.random(shape) * 10.0 ** decades[t] for t in range(T)]
+    grids, lattice = [np.array([-1.0, 0.5, 2.0]), np.array([0.1, 0.7])], [1.5, 1.0]
+    w = np.array([0.25, 0.5, 0.25])
+    static = ('prev', [('walk', 0, w)])                         # (exact taps: the walk of the rational pass below)
+    out = hp.transition_fit(prior, [(L, None) for L in liks], [dict(fwd=static, bwd=static)] * T, grids, lattice, nblk=1, full=True, scale=rule)
+    base = hp.transition_fit(prior, [(L, None) for L in liks], [dict(fwd=static, bwd=static)] * T, grids, lattice, nblk=1, full=True, scale=('step',))
+    P, Ls = _frac(prior), [_frac(L) for L in liks]
+
+    def walk(x):                                                # reflecting, along the first parameter of the 3 x 2 grid (C order)
+        rows = [x[0:2], x[2:4], x[4:6]]
+        ext = [rows[0]] + rows + [rows[2]]
+        return [F(1, 4) * ext[i][j] + F(1, 2) * ext[i + 1][j] + F(1, 4) * ext[i + 2][j] for i in range(3) for j in range(2)]
+    alpha, norms, v = [], [], P
+    for t in range(T):
+        a = [x * l for x, l in zip(walk(v) if t else v, Ls[t])]
+        N = sum(a)
+        v = [x / N for x in a]
+        alpha.append(v)
+        norms.append(N)
+    G = len(P)
+    beta, Bs, Ds, posts = [F(1, G)] * G, [], {}, {}
+    for t in range(T - 1, -1, -1):
+        p = [x * y for x, y in zip(alpha[t], beta)]
+        Ds[t] = sum(p)
+        posts[t] = [x / Ds[t] for x in p]
+        _assert_within(out['post'][t][0], posts[t], hp.SLACK * out['post'][t][1], 'post[%d]' % t)
+        local = 1 / (sum(x / l for x, l in zip(posts[t], Ls[t])) * F(1.5))
+        _assert_within([out['local'][t][0]], [local], [hp.SLACK * out['local'][t][1]], 'local[%d]' % t)
+        if t > 0:
+            b = walk([x * l for x, l in zip(beta, Ls[t])])
+            Bs.append(sum(b))
+            beta = [x / Bs[-1] for x in b]
+    for t in range(T):
+        _assert_within(out['alpha'][t][0], alpha[t], hp.SLACK * out['alpha'][t][1], 'alpha[%d]' % t)
+    SF, SB = _rule_sums_exact(rule, norms), _rule_sums_exact(rule, [F(1)] + Bs)
+    sc_ = out['scale']
+    assert sc_['rule'] == sr.parse_rule(rule) and len(sc_['fwd']) == T and len(sc_['bwd']) == T
+
+    def close(got, want, what):
+        assert abs(F(*hp.LD(got).as_integer_ratio()) / want - 1) < F(1, 10 ** 13), (what, float(got), float(want))
+    for k in range(T):
+        close(sc_['fwd'][k], SF[k], 'forward sum %d' % k)
+        close(sc_['bwd'][k], SB[k], 'backward sum %d' % k)
+        close(sc_['post'][T - 1 - k], SF[T - 1 - k] * SB[k] * Ds[T - 1 - k], 'posterior sum %d' % (T - 1 - k))
+    # the terms, from the exact sums: the un-normalised product of step k is held at S_k / n_k
+    tiny = F(hp.TINY)
+    H = hp.ScaleHistory(rule, {})
+    for k in range(T):
+        close(H.forward_term(False, False), tiny / min(F(1), SF[k] / norms[k]), 'forward term %d' % k)
+        H.forward_done(hp._ld(float(norms[k])), False, False)
+    for k in range(T):
+        t = T - 1 - k
+        close(H.posterior_term(t), tiny / (min(F(1), SF[t]) * min(F(1), SB[k])), 'posterior term %d' % t)
+        if t > 0:
+            close(H.backward_term(False, False), tiny / min(F(1), SB[k + 1] / Bs[k]), 'backward term %d' % t)
+            H.backward_done(hp._ld(float(Bs[k])), False, False)
+    # ... and they are IN the bounds: a rule whose state is smaller than the per-step rule's has the larger bound, cell by cell
+    for t in range(T):
+        smaller = min(F(1), SF[t]) * min(F(1), SB[T - 1 - t]) <= min(F(1), norms[t]) * min(F(1), ([F(1)] + Bs)[T - 1 - t])
+        if smaller:
+            assert np.all(out['post'][t][1] >= base['post'][t][1] * (1 - 1e-12)), t
+
+
+@needs_extended
+def test_scale_history_is_simulate_sums_with_restarts_and_clamped_steps():
+    """the incremental form highprec uses (scale_rules.History) against the restatement tests/test_host_logic.py pins the host's inverse to
+    (scale_rules.simulate_sums), at the schedules of the long series, with restarts behind steps 5 and 9 and clamped steps"""
+    import long_series_cases as ls
+    import scale_rules as sr
+    for schedule in ls.SCHEDULES:
+        n = np.exp2(hp._ld(ls.exponents(schedule))) * hp._ld(np.random.default_rng(3).uniform(0.9, 1.1, ls.steps_of(schedule)))
+        T = len(n)
+        kinds, clamped = np.zeros(T, dtype=np.uint8), np.zeros(T, dtype=np.uint8)
+        kinds[[6, 10]] = 2
+        clamped[[3, 7, 8, 12]] = 1
+        for lag in (1, 2, 3, 4):
+            for scheme, rule in ((0, ('sum_lag', lag)), (1, ('norm_lag', lag)), (2, ('norm_lag', lag))):
+                for kd in (None, kinds):
+                    with np.errstate(over='ignore', under='ignore', invalid='ignore', divide='ignore'):
+                        S, s = sr.simulate_sums(n, lag, scheme, kd, clamped if scheme == 2 else None)
+                        H = sr.History(rule)
+                        for k in range(T):
+                            fresh, cl = kd is not None and bool(kd[k]), scheme == 2 and bool(clamped[k])
+                            pre = H.pre(fresh, cl)
+                            H.push(n[k], fresh, cl)
+                            if np.isfinite(S[k]) and S[k] > 0:
+                                assert abs(H.S[k] / S[k] - 1) < 1e-15 and abs(pre * n[k] / S[k] - 1) < 1e-15, (schedule, lag, scheme, k)
+    assert sr.parse_rule('norm_lag(4)') == ('norm_lag', 4) and sr.parse_rule('step') == ('step',) and sr.parse_rule(('launch', 8)) == ('launch', 8)
+
+
+@needs_extended
+def test_gaussian_fit_under_a_scale_rule_is_transition_fit_with_clamped_steps():
+    """gaussian_fit(scale = rule) is transition_fit over the one program; with a clamp every step behind the first runs at the exact scale
+    (scheme 2): the sums it predicts are simulate_sums(.., 2) of its own normalisers with every step clamped; values as without a rule"""
+    import scale_rules as sr
+    shape, prior, liks, w = _small_lazy_problem()
+    grids = [np.arange(6.0), np.arange(5.0)]
+    plain = hp.gaussian_fit(prior, liks, [(0, w), (1, w)], grids, [1.0, 1.0], nblk=2, clamp=-3.0)
+    for rule, scheme in ((('norm_lag', 2), 2), (('norm_lag', 4), 2), (('sum_lag', 2), 0), (('step',), None)):
+        out = hp.gaussian_fit(prior, liks, [(0, w), (1, w)], grids, [1.0, 1.0], nblk=2, clamp=-3.0, scale=rule)
+        for key in ('alpha', 'post'):
+            for (va, _), (vb, eb) in zip(plain[key], out[key]):
+                assert np.array_equal(np.asarray(va), np.asarray(vb)) and np.all(np.isfinite(np.asarray(eb, dtype=np.float64)))
+        n = hp._ld([N for N, _ in out['norm']])
+        if scheme is None:
+            want = n
+        else:
+            with np.errstate(all='ignore'):
+                want, _ = sr.simulate_sums(n, rule[1], scheme, None, np.ones(len(n), dtype=np.uint8) if scheme == 2 else None)
+        assert np.all(np.abs(hp._ld(out['scale']['fwd']) / want - 1) < 1e-15), rule
+    free = hp.gaussian_fit(prior, liks, [(0, w), (1, w)], grids, [1.0, 1.0], nblk=2, scale='norm_lag(2)')      # no clamp: the lagged rule itself
+    n = hp._ld([N for N, _ in free['norm']])
+    assert np.all(np.abs(hp._ld(free['scale']['fwd']) / sr.simulate_sums(n, 2, 1)[0] - 1) < 1e-15)
+
+
+LONG_ORACLE_WORST, LONG_VERDICTS = {}, {}
+
+
+def _long_families():
+    import long_series_cases as ls
+    return list(ls.FAMILIES)
+
+
+@needs_extended
+@pytest.mark.parametrize('fam', _long_families())
+def test_float64_oracle_is_inside_the_bounds_of_the_long_series_problems(fam):
+    """oracle/bl_oracle.py (NumPy float64; it normalises at every step) on EVERY problem of tests/test_long_series.py -- full fits, forward-only
+    fits, and against the bounds of every rule of the lag sweep -- through the same driver, comparison and bounds.  Prints the worst error / bound."""
+    import long_series_cases as ls
+    import step_transition_cases as sc
+    from oracle_engine import OracleEngine
+    eng = OracleEngine()
+    chk = sc.Check(fam)
+    jobs = [(s, True, None) for f, s in ls.combinations() if f == fam] + [(s, False, None) for f, s in ls.forward_combinations() if f == fam] + \
+           [(s, True, r) for f, s, r in ls.lag_combinations() if f == fam]
+    runs = {}
+    for schedule, full, rule in jobs:
+        R = ls.reference(fam, schedule, full=full, rule=rule)
+        LONG_VERDICTS[(fam, schedule, full, R['rule'])] = (R['verdict'], R['fwd'], R['bwd'], R['keep'], len(R['refs']))
+        assert R['verdict'] != 'refused', (fam, schedule, full, rule)
+        if (schedule, full) not in runs:
+            with np.errstate(all='ignore'):
+                runs[(schedule, full)] = ls.run_problem(eng, fam, schedule, list(range(len(R['refs']))), full=full, one_at_a_time=True)
+        got = runs[(schedule, full)]
+        top = chk.top
+        chk.top = 0.0
+        ls.compare(chk, fam, schedule, R['keep'], {k: [v[b] for b in R['keep']] for k, v in got.items() if k != 'timing'}, R['refs'], full=full)
+        LONG_ORACLE_WORST[(fam, schedule, full, R['rule'])] = chk.top
+        print('float64 oracle, %s %s %s %r (%s): worst error / bound %.4f' % (fam, schedule, 'full' if full else 'forward', R['rule'], R['verdict'], chk.top))
+        chk.top = max(chk.top, top)
+    assert not chk.bad, '\n'.join(chk.bad[:20])
+
+
+@needs_extended
+def test_long_series_schedules_meet_their_conditions():
+    """Conditions, not measurements, from the reference alone: what each family's restated rule predicts its host guard to do on every schedule --
+    the table below is exact --, every prediction a factor 1e6 clear of the threshold that decides it or the combination refused (the exact
+    list), every predicted sum inside (1e-290, 1e290) (asserted where the prediction is formed), no chain dropped; the amplitudes of the resonant
+    schedules as the restated sum_lag(2) rule chooses them; the family that is left out, and that nothing else is."""
+    import long_series_cases as ls
+    import scale_rules as sr
+
+    def verdict(fam, schedule, full=True, rule=None):
+        key = (fam, schedule, full, ls.FAMILIES[fam]['rule'] if rule is None else rule)
+        if key not in LONG_VERDICTS:
+            R = ls.reference(fam, schedule, full=full, rule=rule)
+            LONG_VERDICTS[key] = (R['verdict'], R['fwd'], R['bwd'], R['keep'], len(R['refs']))
+        return LONG_VERDICTS[key]
+
+    assert (ls.RESONANT_IN, ls.RESONANT_OUT) == (27, 41)
+    assert ls.FAMILIES['fused1d']['rule'] == ('launch', 6) and ls.FAMILIES['persist1d']['rule'] == ('launch', 2)
+    assert ls.launch_steps(8, 14, 32) == 8 and ls.launch_steps(8, 3, 5) == 3 and ls.launch_steps(8, 14, 300) == 1
+    assert max(c[0] for c in ls.sc.CASES['fused1d_walks_300']['chains']) == 40
+    for a, lo, hi in ((ls.RESONANT_IN, 110, 120), (ls.RESONANT_OUT, 165, 175)):
+        S, _ = sr.simulate_sums(np.exp2(hp._ld(ls._resonant(a, ls.T_RESONANT))), 2, 0)
+        assert lo <= float(np.max(np.abs(np.log10(S)))) < hi                 # (each step is only 2^+-a = 1e+-8 / 1e+-12)
+        Sc, _ = sr.simulate_sums(np.exp2(hp._ld(ls._resonant(a, ls.T_RESONANT))), 4, 1)
+        assert float(np.max(np.abs(np.log10(Sc)))) < 19                      # the chain rule under the same drive
+    special = {('resident', 'resonant_out'): 'range', ('fused1d', 'ramp'): 'repeat'}
+    special.update({(f, 'burst_out'): 'range' for f in ('chain', 'chain_sources', 'chainax')})
+    special.update({c: 'refused' for c in ls.REFUSED})
+    for fam, schedule in ls.combinations(refused=True):
+        v, fwd, bwd, keep, n = verdict(fam, schedule)
+        assert v == special.get((fam, schedule), 'none'), (fam, schedule, v, fwd, bwd)
+        assert keep == list(range(n)), (fam, schedule, keep)                 # no chain is dropped
+    assert sorted(c for c in ls.combinations(refused=True) if verdict(*c)[0] == 'refused') == sorted(ls.REFUSED)
+    # just inside the time-resident guard: 1e+-110 of 1e+-150; the chain rule stays far inside under both resonant schedules
+    assert 1e108 < verdict('resident', 'resonant_in')[1][1] < 1e112
+    for fam in ('chain', 'chain_sources', 'chainax'):
+        for schedule in ('resonant_in', 'resonant_out'):
+            lo, hi = verdict(fam, schedule)[1]
+            assert 1e-40 < lo and hi < 1e40, (fam, schedule, lo, hi)
+    for fam, schedule in ls.forward_combinations():
+        assert verdict(fam, schedule, full=False)[0] == 'none', (fam, schedule)      # (fused1d, ramp: six steps per launch leave 2.4e-181, no repeat; the full fit's posterior sums repeat it)
+    # the lag sweep: the chain rule at lag 2 and 3, the lagged sum at lag 1 and 3.  Lag 3 of the lagged sum is exponentially unstable
+    # (|roots of r^3 - r^2 + 1| = 1.15): at T = 14 it stays inside the guard on `flat`, and a burst of five sends it beyond
+    for fam, schedule, rule in ls.lag_combinations():
+        want = 'range' if (fam, schedule, rule) == ('resident', 'burst_in', ('sum_lag', 3)) else 'none'
+        assert verdict(fam, schedule, rule=rule)[0] == want, (fam, schedule, rule, verdict(fam, schedule, rule=rule))
+    assert ls.NOT_RUN[:2] == [('chain1d_long', 'resonant_in'), ('chain1d_long', 'resonant_out')]
+    assert sorted(set(f for f, _ in ls.NOT_RUN[2:])) == sorted(set(ls.FAMILIES) - set(ls.LAGGED)) and set(s_ for _, s_ in ls.NOT_RUN[2:]) == {'ramp_80', 'burst_mild'}
+    # the shifts: two per chain keep every renormalising sum conditioned (no chain dropped, above); a shift at EVERY step would not
+    case = ls.case_of('chain1d_shifts', ls.T_LONG)
+    assert all(sum(1 for d in c[0] if d != 0.0) == 2 and len(c[0]) == ls.T_LONG - 1 for c in case['chains']) and len(case['chains']) == 8
+    every = dict(case, chains=[(tuple(c[0][3] if k % 2 == 0 else -c[0][3] for k in range(ls.T_LONG - 1)),) for c in case['chains'][:1]])
+    prior, lik, reset, indep = ls.tables('chain1d_shifts', 'flat')
+    ref = hp.transition_fit(prior, [(L, None) for L in lik], ls.sc.stage_program(every, every['chains'][0], 'three', ls.T_LONG), [np.arange(300.0)], [1.0],
+                            nblk=ls.sc.nblk_of((300,)), full=True, shared=dict(reset=reset, indep=indep), scale=('step',))
+    assert ls.conditioned([ref]) == [False]
+
+
+def _gaussian_long():
+    import long_series_cases as ls
+    return list(ls.GAUSSIAN)
+
+
+@needs_extended
+@pytest.mark.parametrize('fam', _gaussian_long())
+def test_float64_oracle_is_inside_the_bounds_of_the_gaussian_long_series(fam):
+    """oracle/bl_oracle.py on the Gaussian problems of tests/test_long_series.py, full and forward-only, held to the bounds the kernels are held
+    to; the series fall in the classes they are named for, by their longdouble normalisers; none of them leaves a guard of its family's rule"""
+    import long_series_cases as ls
+    import test_likelihood_kernels as tl
+    from oracle import bl_oracle as bo
+    chk = tl.Check('oracle long ' + fam)
+    for name in ls.SERIES:
+        for full in (True, False):
+            problem, values, refs, liks, rec_ok = ls.gaussian_setup(fam, name, full)
+            assert rec_ok and all(tl.aborted_at(r) is None for r in refs)
+            verdict, fwd, bwd = ls.prediction(refs, ls.GAUSSIAN[fam], full)
+            assert verdict == 'none', (fam, name, full, verdict, fwd, bwd)
+            low = min(float(N) for r in refs for N, _ in r['norm'][1:])
+            assert {'calm': low >= ls.CALM, 'jumping': low < ls.JUMP, 'jumping_period6': ls.JUMP <= low < ls.CALM}[name], (fam, name, low)
+            g = bo.Grid(problem.marginal)
+            T = len(problem.data)
+            for c, ref in enumerate(refs):
+                with np.errstate(all='ignore'):
+                    r = bo.fit(g, 'gaussian', problem.data, problem.timestamps, problem.prior, [('grw', op[1]) if op[0] == tl._abi.OP_GRW else ('regimeswitch',) for op in problem.ops], list(values[c]), forward_only=not full)
+                assert r['abort'] is None
+                w = '%s %s chain %d' % (name, 'full' if full else 'forward', c)
+                chk.within([r['logEvidence']], [ref['log_evidence'][0]], [ref['log_evidence'][1]], w + ' logE')
+                for t in range(T):
+                    want = ref['post'][t] if full else ref['alpha'][t]
+                    chk.within(r['posteriorSequence'][t], want[0], want[1], w + ' posterior[%d]' % t)
+                    loc = ref['local'][t] if full else ref['local_fwd'][t]
+                    chk.local(r['localEvidence'][t], loc[0], loc[1], w + ' localEvidence[%d]' % t)
+                    chk.within(np.asarray(r['posteriorMeanValues'])[:, t], ref['means'][t][0], ref['means'][t][1], w + ' means[%d]' % t)
+    print('float64 oracle, gaussian %s: worst error / bound %.4f' % (fam, chk.top))
+    assert not chk.bad, '\n'.join(chk.bad[:20])

@@ -322,16 +322,7 @@ def test_online_study_survives_pickling():
 
 # ---- the scale algebra of the resident kernels (include/blhip.h: blhip_host_unlag) -- pure host code of libblhip.so ---------------------
 
-def _simulate_sums(norms, lag, scheme, kinds=None):
-    """What a resident kernel reports: S_k = (S_(k-1) or 1 at a restart) * s_k * n_k with the kernel's rule for s_k."""
-    T = len(norms)
-    S, s = np.zeros(T), np.ones(T)
-    for k in range(T):
-        if k >= lag:
-            s[k] = 1.0 / S[k - lag] if scheme == 0 else (S[k - lag - 1] if k - lag - 1 >= 0 else 1.0) * s[k - lag] / S[k - lag]
-        fresh = k == 0 or (kinds is not None and kinds[k] != 0)
-        S[k] = (1.0 if fresh else S[k - 1]) * s[k] * norms[k]
-    return S, s
+from scale_rules import simulate_sums as _simulate_sums      # (tests/highprec.py forms its bounds from the same restatement)
 
 
 @pytest.mark.parametrize('scheme,lag', [(0, 1), (0, 2), (1, 2), (1, 3), (1, 4)])
@@ -383,6 +374,85 @@ def test_host_unlag_with_restarts_and_out_of_range_sums():
     bad = S.copy()
     bad[30] = 1e-200                                            # a run of extreme outliers: the fit falls back to the launch-per-step kernels
     assert lib.blhip_host_unlag(1, _abi.dptr(bad), T, lag, None, None) == 1
+
+
+def _long_schedules():
+    import long_series_cases as ls
+    return list(ls.SCHEDULES)
+
+
+@pytest.mark.parametrize('schedule', _long_schedules())
+def test_host_unlag_at_the_long_series_schedules(schedule):
+    """the host's inverse against the restated rules at the normaliser schedules of tests/long_series_cases.py, not only at random ones: the
+    lagged sum (scheme 0), the lagged normaliser (1) and the same with clamped steps at the exact scale (2: bit 6 of a step's kind), each with
+    and without a restart history (change points behind steps 5 and 9).  Where a simulated sum leaves (1e-150, 1e150) the host must say so."""
+    import ctypes
+    import long_series_cases as ls
+    from bayesloop_amd import _abi
+    lib = _abi.load()
+    norms = np.exp2(ls.exponents(schedule).astype(np.float64)) * np.random.default_rng(23).uniform(0.9, 1.1, ls.steps_of(schedule))
+    T = len(norms)
+    restarts, clamped = np.zeros(T, dtype=np.uint8), np.zeros(T, dtype=np.uint8)
+    restarts[[6, 10]] = 2                                        # blk::SRC_RESET
+    clamped[[3, 7, 8, 12]] = 1
+    seen = set()
+    for scheme, lags in ((0, (1, 2, 3)), (1, (2, 3, 4)), (2, (2, 3, 4))):
+        for lag in lags:
+            for kinds in ((None,) if scheme == 0 else (None, restarts)):
+                with np.errstate(over='ignore', invalid='ignore', divide='ignore', under='ignore'):
+                    S, s = _simulate_sums(norms, lag, scheme, kinds, clamped if scheme == 2 else None)
+                packed = None
+                if scheme == 2:
+                    packed = ((np.zeros(T, dtype=np.uint8) if kinds is None else kinds) | (clamped << 6)).astype(np.uint8)
+                elif kinds is not None:
+                    packed = kinds
+                ptr = None if packed is None else packed.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte))
+                ok = True
+                for x in S:                                     # (the host stops at the first sum out of range; the ones behind it may be anything)
+                    if not 1e-150 < x < 1e150:
+                        ok = False
+                        break
+                sums, scales = S.copy(), np.zeros(T)
+                rc = lib.blhip_host_unlag(scheme, _abi.dptr(sums), T, lag, ptr, _abi.dptr(scales))
+                assert rc == (0 if ok else 1), (schedule, scheme, lag, kinds is not None, S)
+                seen.add(ok)
+                if ok:
+                    np.testing.assert_allclose(sums, norms, rtol=1e-12)
+                    np.testing.assert_allclose(scales, s, rtol=1e-12)
+    assert True in seen and (False in seen) == (schedule not in ('flat', 'burst_mild')), (schedule, seen)      # both answers of the host are walked, but on the two mild schedules
+
+
+@pytest.mark.parametrize('schedule', _long_schedules())
+def test_a_changed_scale_rule_moves_the_normalisers_beyond_any_bound(schedule):
+    """Can tests/test_long_series.py fail?  Two of the arithmetic changes a kernel could carry, RESTATED on the sums (no kernel is changed or
+    run): what the host's inverse then makes of them, against the 1e-12 the bounds of logEvidence and local_evidence leave a normaliser.
+      (a) the chain-resident scale without S_(k-lag-1):  s_k = s_(k-lag) / S_(k-lag).  Invisible in three steps (k < lag), wrong from step lag + 1;
+      (b) a K-steps-per-launch pass whose later launches start at scale 1 instead of 1 / S of the step before."""
+    import long_series_cases as ls
+    from bayesloop_amd import _abi
+    lib = _abi.load()
+    norms = np.exp2(ls.exponents(schedule).astype(np.float64)) * np.random.default_rng(23).uniform(0.9, 1.1, ls.steps_of(schedule))
+    T, lag = len(norms), 4
+    S, s = np.zeros(T), np.ones(T)
+    with np.errstate(all='ignore'):
+        for k in range(T):                                          # (a)
+            if k >= lag:
+                s[k] = s[k - lag] / S[k - lag]
+            S[k] = (S[k - 1] if k else 1.0) * s[k] * norms[k]
+    if np.all((S > 1e-150) & (S < 1e150)):
+        sums = S.copy()
+        assert lib.blhip_host_unlag(1, _abi.dptr(sums), T, lag, None, None) == 0
+        err = np.abs(sums / norms - 1.0)
+        assert np.all(err[:lag + 1] < 1e-12) and np.all(err[lag + 1:] > 1e-3), (schedule, err)
+        assert np.all(np.abs(sums[:3] / norms[:3] - 1.0) < 1e-12)       # three steps: nothing to see
+    K = 6                                                           # (b): forward_bookkeeping divides an inner step by the raw sum before it
+    raw = np.array([np.prod(norms[k - k % K:k + 1]) for k in range(T)])
+    wrong = raw.copy()
+    wrong[K:] = [raw[k] * raw[K * (k // K) - 1] for k in range(K, T)]      # the launch went on from the un-normalised state
+    with np.errstate(all='ignore'):
+        got = np.array([wrong[k] if k % K == 0 else wrong[k] / wrong[k - 1] for k in range(T)])
+        err = np.abs(got / norms - 1.0)
+    assert np.all(err[:K] < 1e-12) and np.all(~(err[K::K] <= 1e-3)), (schedule, err)
 
 
 # ---- which Gaussian fits take the likelihood recurrence (include/blhip.h: blhip_host_rec_envelope) -- pure host code of libblhip.so ------
