@@ -61,7 +61,8 @@ namespace {
 #include "blhip_launch.hpp"    // Tile, launch_* (the launch tables), plan_resident
 #include "blhip_batch.hpp"     // plan_batches, upload_tables / _metadata, chains_per_batch, plan_geometry, plan_chainres, folds, results
 #include "blhip_book.hpp"      // resident_unlag / chain_unlag, forward_ / backward_bookkeeping, account
-#include "blhip_fit_nd.hpp"       // do_fit_nd: grids with 3 and 4 parameters
+#include "blhip_nd_program.hpp"   // NdFacts, NdBatchProgram, build_nd_program: the transition program on grids with 3 and 4 parameters (no HIP call)
+#include "blhip_fit_nd.hpp"       // do_fit_nd, NdEnv, nd_step, NdChainRun: grids with 3 and 4 parameters
 #include "blhip_fit_paths.hpp"    // BatchEnv, ResidentRun, ChainRun: the resident paths of a batch
 #include "blhip_fit_row1d.hpp"    // Row1dRun: the 1-D paths of a batch
 #include "blhip_fit_step.hpp"     // StepRun: the launch-per-step path of a batch
@@ -224,8 +225,7 @@ bool run_passes(BatchRun &R, const int64_t K) {
     } else if (forward_only) {
         for (int64_t b = 0; b < B; ++b)
             for (int64_t t = 0; t < T; ++t) {
-                const double n0 = res_now ? RR.rowsumF[t] : (cres_now ? CR.rowsumC[b][t] : redF[((size_t)t * B + b) * NRED]);
-                O.invN[(size_t)b * T + t] = (n0 != 0.0 && std::isfinite(n0)) ? 1.0 / n0 : 0.0;     // (a signed kernel can leave a negative raw sum)
+                O.invN[(size_t)b * T + t] = forward_invN(res_now ? RR.rowsumF[t] : (cres_now ? CR.rowsumC[b][t] : redF[((size_t)t * B + b) * NRED]));
                 if (res_now && t <= T - 1 - RR.RQ.lag) O.invN[(size_t)b * T + t] = 1.0;                // (already normalised by the resident kernel)
             }
     }
@@ -402,16 +402,8 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
         }
         // BLHIP_RESUME: step 0 reads each chain's carried (normalised) state; its "previous partial sums" add up to 1
         if (ff.resume) {
-            E.d_carry_src = ctx->carry[p->carry_slot].buf.as<double>();
-            std::vector<double> unit((size_t)B * NRED * tile.nblk, 0.0);
-            const std::vector<double> &mv = ctx->carry[p->carry_slot].maxv;
-            for (int64_t b = 0; b < B; ++b)
-                for (int k = 0; k < NRED; ++k)       // slot 6 = maximum of the carried state (NotEqual inverts around it)
-                    unit[((size_t)b * NRED + k) * tile.nblk] = (k == 6 && (int64_t)mv.size() == B) ? mv[b] : 1.0;
-            ctx->unit.ensure(unit.size() * 8);
-            HIPCHECK(hipMemcpyAsync(ctx->unit.p, unit.data(), unit.size() * 8, hipMemcpyHostToDevice, st));
-            sync_stream(ctx, st);
-            E.d_unit = ctx->unit.as<double>();
+            E.d_carry_src = carry_source(ctx, p, n_chains, G);
+            E.d_unit = upload_unit_sums(ctx, p, st, B, tile.nblk, true);
         }
         // ---- the paths: 1-D kernels, or the resident ones (single chain: blhip_resident.hpp; batches of chains: blhip_chainres.hpp) with
         //      the launch-per-step kernels as their fall-back -----------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // A batch of chains on the device: batch plan and memory plan, shared tables and per-(step, chain) metadata (uploads), which kernel family runs the
-// batch (plan_geometry, plan_chainres), the average-posterior folds, kept posteriors, carried states, results.
+// batch (plan_geometry, plan_chainres), the average-posterior folds, kept posteriors, carried states (carry_source, upload_unit_sums: also the N-D path's), results.
 // Part of libblhip's host side: included by blhip.hip INSIDE its anonymous namespace (one translation unit; the split is by subject, not by linkage).
 #pragma once
 
@@ -319,6 +319,30 @@ inline bool chain_tall(int n0) { return n0 > 512 && n0 <= CHAIN_TALL_ROWS; }
 static_assert(blo::PAD_ROWS_MIN == CHAIN_MIN_ROWS && blo::PAD_ROWS_MAX == CHAIN_TALL_ROWS && blo::PAD_COLS == blc::WCOL && blo::PAD_ROWS == 128,
               "blo::online_block_plan counts a chain's cells as chains_per_batch does");
 
+// BLHIP_RESUME: the carried states the call continues, (n_chains, G) on the device; refused unless the slot holds that shape
+const double *carry_source(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, long long G) {
+    auto it = ctx->carry.find(p->carry_slot);
+    if (it == ctx->carry.end() || !it->second.valid) fail("BLHIP_RESUME: carry slot %d holds no state", p->carry_slot);
+    if (it->second.chains != n_chains || it->second.G != G)
+        fail("BLHIP_RESUME: carry slot %d holds %lld chains x %lld cells, the call has %lld x %lld", p->carry_slot,
+             (long long)it->second.chains, (long long)it->second.G, (long long)n_chains, (long long)G);
+    return it->second.buf.as<double>();
+}
+
+// BLHIP_RESUME: the carried states are normalised -- the "partial sums of the step before" step 0, [B][NRED][nblk], add up to 1 in every
+// slot.  slot6_max: slot 6 is the maximum of the carried state (1-D / 2-D: NotEqual inverts around it; N-D: a sum like the others)
+const double *upload_unit_sums(blhip_ctx *ctx, const blhip_problem *p, hipStream_t st, int64_t B, int nblk, bool slot6_max) {
+    std::vector<double> unit((size_t)B * NRED * nblk, 0.0);
+    const std::vector<double> &mv = ctx->carry[p->carry_slot].maxv;
+    for (int64_t b = 0; b < B; ++b)
+        for (int k = 0; k < NRED; ++k)
+            unit[((size_t)b * NRED + k) * nblk] = (k == 6 && slot6_max && (int64_t)mv.size() == B) ? mv[b] : 1.0;
+    ctx->unit.ensure(unit.size() * 8);
+    HIPCHECK(hipMemcpyAsync(ctx->unit.p, unit.data(), unit.size() * 8, hipMemcpyHostToDevice, st));
+    sync_stream(ctx, st);
+    return ctx->unit.as<double>();
+}
+
 int64_t chains_per_batch(blhip_ctx *ctx, const blhip_problem *p, const Geometry &g, const FitFlags &ff, int64_t n_chains) {
     const int64_t T = p->T;
     const long long G = g.G;
@@ -358,13 +382,7 @@ int64_t chains_per_batch(blhip_ctx *ctx, const blhip_problem *p, const Geometry 
     Bmax = std::min<int64_t>(Bmax, 65535);
     if (ff.keep && n_chains > Bmax) fail("BLHIP_KEEP_POSTERIOR: %lld chains do not fit in device memory at once", (long long)n_chains);
     if ((ff.resume || ff.carry) && n_chains > Bmax) fail("carried states: %lld chains do not fit in one batch", (long long)n_chains);
-    if (ff.resume) {
-        auto it = ctx->carry.find(p->carry_slot);
-        if (it == ctx->carry.end() || !it->second.valid) fail("BLHIP_RESUME: carry slot %d holds no state", p->carry_slot);
-        if (it->second.chains != n_chains || it->second.G != G)
-            fail("BLHIP_RESUME: carry slot %d holds %lld chains x %lld cells, the call has %lld x %lld", p->carry_slot,
-                 (long long)it->second.chains, (long long)it->second.G, (long long)n_chains, (long long)G);
-    }
+    if (ff.resume) (void)carry_source(ctx, p, n_chains, G);
     return Bmax;
 }
 

@@ -167,6 +167,9 @@ bool backward_bookkeeping(const blhip_problem *p, const ChainProgram &prog, cons
     return raw_ok;
 }
 
+// forward-only fits: the row normaliser of a filtered distribution whose raw sum is n0 (a signed kernel can leave a negative raw sum)
+inline double forward_invN(double n0) { return (n0 != 0.0 && std::isfinite(n0)) ? 1.0 / n0 : 0.0; }
+
 // ---- what the launches move and compute BY CONSTRUCTION (blhip_timing: fwd / bwd _hbm_bytes, _flops) ------------------------------------
 // fp64 flop per cell of the fused epilogues (FMA = 2; ldexp, compare and select count 1): forward  a = v L (1), sum (1), the two
 // recurrence products (2), ldexp (1) + the exponentials of the anchors spread over their rows (2 x ~42 flop per 16 rows: 5);
