@@ -59,7 +59,8 @@ namespace {
 
 #include "blhip_program.hpp"   // TapTable, Geometry, validate, build_records, build_program
 #include "blhip_launch.hpp"    // Tile, launch_* (the launch tables), plan_resident
-#include "blhip_batch.hpp"     // plan_batches, upload_tables / _metadata, chains_per_batch, plan_geometry, plan_chainres, folds, results
+#include "blhip_chain_plan.hpp"   // plan_chainres, ChainFacts / ChainOptions and the stages of the chain-resident route on two-parameter grids (no HIP call)
+#include "blhip_batch.hpp"     // plan_batches, upload_tables / _metadata, chains_per_batch, plan_geometry, folds, results
 #include "blhip_book.hpp"      // resident_unlag / chain_unlag, forward_ / backward_bookkeeping, account
 #include "blhip_nd_program.hpp"   // NdFacts, NdBatchProgram, build_nd_program: the transition program on grids with 3 and 4 parameters (no HIP call)
 #include "blhip_fit_nd.hpp"       // do_fit_nd, NdEnv, nd_step, NdChainRun: grids with 3 and 4 parameters

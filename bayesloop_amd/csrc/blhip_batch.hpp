@@ -1,5 +1,5 @@
 // A batch of chains on the device: batch plan and memory plan, shared tables and per-(step, chain) metadata (uploads), which kernel family runs the
-// batch (plan_geometry, plan_chainres), the average-posterior folds, kept posteriors, carried states (carry_source, upload_unit_sums: also the N-D path's), results.
+// batch (plan_geometry; plan_chainres: blhip_chain_plan.hpp), the average-posterior folds, kept posteriors, carried states (carry_source, upload_unit_sums: also the N-D path's), results.
 // Part of libblhip's host side: included by blhip.hip INSIDE its anonymous namespace (one translation unit; the split is by subject, not by linkage).
 #pragma once
 
@@ -311,11 +311,7 @@ DeviceTables upload_tables(blhip_ctx *ctx, const blhip_problem *p, const Geometr
 }
 
 // memory plan: how many chains fit one batch (state ping-pong + the stored sequence + partial sums per chain within the budget)
-constexpr int CHAIN_MIN_ROWS = 32;            // smallest grid (rows) the chain-resident kernels take (on the 128-row geometry)
-constexpr int CHAIN_R0_MAX = 80;               // widest band of the chain-resident kernels (ring of 44 entries); option chain_wide = 0: FAST_R0_MAX
-constexpr int CHAIN_TALL_ROWS = 1024;         // ... and the one geometry beyond 512 rows: grids of 513 .. 1024 rows (option chain_tall = 0: off)
-inline bool chain_rows_ok(int n0) { return n0 >= CHAIN_MIN_ROWS && n0 <= CHAIN_TALL_ROWS; }
-inline bool chain_tall(int n0) { return n0 > 512 && n0 <= CHAIN_TALL_ROWS; }
+// (the rows the chain-resident kernels take: CHAIN_MIN_ROWS .. CHAIN_TALL_ROWS, blhip_chain_plan.hpp)
 static_assert(blo::PAD_ROWS_MIN == CHAIN_MIN_ROWS && blo::PAD_ROWS_MAX == CHAIN_TALL_ROWS && blo::PAD_COLS == blc::WCOL && blo::PAD_ROWS == 128,
               "blo::online_block_plan counts a chain's cells as chains_per_batch does");
 
@@ -365,7 +361,7 @@ int64_t chains_per_batch(blhip_ctx *ctx, const blhip_problem *p, const Geometry 
             Gk = std::max(Gk, n * n);
         }
     }
-    // the partial accumulators of the fused fold (ChainRun::setup: one (T, G) slot per block column of a launch) come out of the same memory
+    // the partial accumulators of the fused fold (ChainRun::fold_buffers: one (T, G) slot per block column of a launch) come out of the same memory
     // -- only where the chain-resident path can be taken at all (else they are never allocated: a narrow grid with a long series
     //    gave up its whole budget to 128 slots it never used and ran one chain per batch), and never more than half of the budget
     if (ff.accumulate && ff.full && p->ndim == 2 && p->obs_model == BLHIP_OM_GAUSSIAN && chain_rows_ok(g.n0) &&
@@ -866,115 +862,4 @@ void write_results(blhip_result *res, const blhip_problem *p, int64_t c0, int64_
         if (res->posterior_mean && with_means)
             std::memcpy(res->posterior_mean + (size_t)(c0 + b) * p->ndim * T, &out.means[(size_t)b * p->ndim * T], (size_t)p->ndim * T * 8);
     }
-}
-
-// The chain-resident path (blhip_chainres.hpp): which chains of the batch run together, in which order, with which band width.
-struct ChainResPlan {
-    int ntw = 0, strips = 0, cpr = 0;            // product tiles per wave, strips per chain, chains per launch
-    int n0p = 0, n1p = 0;                        // the geometry the kernels work on: rows 128 / 256 / 512, columns a multiple of 16
-    bool pad = false;                            // the grid is smaller than that (padded cells hold zeros; sequences private to the fit only)
-    int r0_max = 40;                             // widest axis-0 radius the launch may carry (set by the caller: 80 for 1024 rows)
-    bool has_reset = false;                      // change points: some steps consume the reset distribution
-    bool mixed = false;                          // ... in chains that also filter (random walk + change point in one model)
-    std::vector<unsigned char> ckF, ckB;         // [T][B] what a step of the chain kernels consumes: SRC_PREV / SRC_RESET (| 0x80: unfiltered)
-    std::vector<int> order, tap_id;              // chains sorted by stencil radius; the chain's axis-0 kernel (-1: none)
-    bool allow_ax1 = false;                      // (set by the caller) walks on the second parameter too may be planned: blc::chainax_kernel
-    bool ax1 = false;                            // ... and some chain has one: the batch runs the transposing kernels (square exact geometry)
-    std::vector<int> tap_id1;                    // the chain's axis-1 kernel (-1: none)
-    std::vector<int> round_start, round_nk;      // launches: order[round_start[r] .. round_start[r + 1]), band blocks NK
-};
-
-// every chain: prior, then the SAME axis-0 kernel at every step, nothing on axis 1 (forward; mirrored backward)
-bool plan_chainres(const Geometry &g, const ChainProgram &prog, const TapTable &taps, int64_t B, int64_t T, bool full, int cus, ChainResPlan &cp) {
-    // any grid of 32 .. 512 rows: the kernels work on the next geometry of 128 / 256 / 384 / 512 rows x a multiple of 16 columns;
-    // 513 .. 1024 rows: 1024 rows x a multiple of 16 columns (one copy of the strip in LDS: blc::chain_kernel TALL; change-point batches keep their state in registers there too)
-    if (!chain_rows_ok(g.n0)) return false;
-    cp.n0p = (g.n0 + 127) / 128 * 128;
-    cp.n1p = (g.n1 + blc::WCOL - 1) / blc::WCOL * blc::WCOL;
-    if (chain_tall(g.n0)) cp.n0p = CHAIN_TALL_ROWS;
-    cp.pad = cp.n0p != g.n0 || cp.n1p != g.n1;
-    cp.strips = cp.n1p / blc::WCOL;
-    cp.ntw = cp.n0p / (blc::NW * blc::TM);
-    if (cp.strips > blc::MAX_STRIPS || cp.strips > cus) return false;
-    cp.cpr = cus / cp.strips;
-    cp.tap_id.assign(B, -1);
-    cp.tap_id1.assign(B, -1);
-    cp.ax1 = false;
-    // walks on both parameters (blhip_chainax.hpp): an exact square geometry (the blocks of a chain change between column strips and row strips)
-    // -- the next square geometry of 128 / 256 / 512 rows = columns that holds the grid (PAD kernels where it is larger)
-    const int ax_n = std::max(g.n0, g.n1) <= 128 ? 128 : (std::max(g.n0, g.n1) <= 256 ? 256 : 512);
-    const bool ax1_geom = cp.allow_ax1 && std::max(g.n0, g.n1) <= 512 && g.n0 >= 32 && g.n1 >= 32 && ax_n / blc::WCOL <= cus;
-    std::vector<int> lw(B, 0);
-    cp.ckF.assign((size_t)T * B, (unsigned char)SRC_PREV);
-    cp.ckB.assign((size_t)T * B, (unsigned char)SRC_PREV);
-    for (int64_t b = 0; b < B; ++b) {
-        if (prog.kindF[b] != SRC_PRIOR || prog.tapF0[b] >= 0 || prog.tapF1[b] >= 0) return false;
-        // the chain's band: the kernel of the first step that filters (every filtering step must use the same one)
-        int k0 = -1, k1 = -1;
-        for (int64_t t = 1; t < T && k0 < 0; ++t) k0 = prog.tapF0[(size_t)t * B + b];
-        for (int64_t t = 0; t + 1 < T && k0 < 0 && full; ++t) k0 = prog.tapB0[(size_t)t * B + b];
-        if (ax1_geom) {
-            for (int64_t t = 1; t < T && k1 < 0; ++t) k1 = prog.tapF1[(size_t)t * B + b];
-            for (int64_t t = 0; t + 1 < T && k1 < 0 && full; ++t) k1 = prog.tapB1[(size_t)t * B + b];
-        }
-        // a step either continues from the previous state through the chain's band, or RESTARTS from the reset distribution (a
-        // change point, transitionModels.py:300-312) -- through the band (the change point comes before the random walk in the
-        // combined model's list) or unfiltered (it comes after: the walk's output is discarded)
-        auto classify = [&](unsigned char kind, int t0, int t1, unsigned char &out) {
-            // (k1 = -1 unless the both-axes kernels may be planned; a restart passes through BOTH of the chain's bands or through none)
-            if (kind == SRC_PREV && t0 == k0 && t1 == k1) { out = (unsigned char)SRC_PREV; return true; }
-            if (kind == SRC_RESET && ((t0 == k0 && t1 == k1) || (t0 < 0 && t1 < 0))) {
-                const bool filters = k0 >= 0 || k1 >= 0;
-                out = (unsigned char)(SRC_RESET | ((filters && t0 < 0 && t1 < 0) ? 0x80 : 0));          // bit 7: no filter at this step
-                cp.has_reset = true;
-                if (filters) cp.mixed = true;
-                return true;
-            }
-            return false;
-        };
-        for (int64_t t = 1; t < T; ++t) {
-            const size_t k = (size_t)t * B + b;
-            if (!classify(prog.kindF[k], prog.tapF0[k], prog.tapF1[k], cp.ckF[k])) return false;
-        }
-        if (full) {
-            const size_t kl = (size_t)(T - 1) * B + b;
-            if (prog.kindB[kl] != SRC_UNIFORM || prog.tapB0[kl] >= 0 || prog.tapB1[kl] >= 0) return false;
-            for (int64_t t = 0; t < T - 1; ++t) {
-                const size_t k = (size_t)t * B + b;
-                if (!classify(prog.kindB[k], prog.tapB0[k], prog.tapB1[k], cp.ckB[k])) return false;
-            }
-        }
-        cp.tap_id[b] = k0;
-        cp.tap_id1[b] = k1;
-        lw[b] = k0 >= 0 ? taps.lw[k0] : 0;
-        if (lw[b] > cp.r0_max || lw[b] >= g.n0) return false;          // (single-period reflection)
-        if (k1 >= 0) {
-            cp.ax1 = true;
-            if (taps.lw[k1] >= g.n1) return false;
-            lw[b] = std::max(lw[b], taps.lw[k1]);                       // (one ring length for both filters: the wider walk's)
-        }
-    }
-    if (cp.ax1) {
-        // the transposing kernels: bands of radius <= 40 on either axis (ring lengths 8 .. 24 in steps of 4; the band's rounded radius inside
-        // the grid: single-period reflection); the square geometry replaces the strip geometry planned above
-        for (int64_t b = 0; b < B; ++b) if (lw[b] > FAST_R0_MAX || (std::max(8, (lw[b] + 7) / 8 * 8)) >= std::min(g.n0, g.n1)) return false;
-        cp.n0p = cp.n1p = ax_n;
-        cp.strips = ax_n / blc::WCOL;
-        cp.ntw = ax_n / (blc::NW * blc::TM);
-        cp.pad = ax_n != g.n0 || ax_n != g.n1;
-        cp.cpr = cus / cp.strips;
-    }
-    cp.order.resize(B);
-    for (int64_t b = 0; b < B; ++b) cp.order[b] = (int)b;
-    std::stable_sort(cp.order.begin(), cp.order.end(), [&](int a, int c) { return lw[a] < lw[c]; });
-    cp.round_start.clear(); cp.round_nk.clear();
-    for (int64_t s0 = 0; s0 < B; s0 += cp.cpr) {
-        const int64_t s1 = std::min<int64_t>(B, s0 + cp.cpr);
-        int r0 = std::max(4, (lw[cp.order[s1 - 1]] + 3) / 4 * 4);             // (a product costs 64 cycles: bands as narrow as the widest chain of the launch allows)
-        if (cp.ax1) r0 = std::max(8, (r0 + 7) / 8 * 8);                        // (ring lengths 8, 12, .. 24)
-        cp.round_start.push_back((int)s0);
-        cp.round_nk.push_back((prog.LW0 == 0 && !cp.ax1) ? 4 : (blc::TM + 2 * r0) / 4);          // (4: the no-stencil kernel)
-    }
-    cp.round_start.push_back((int)B);
-    return true;
 }

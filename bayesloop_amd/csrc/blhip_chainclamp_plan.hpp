@@ -7,7 +7,7 @@ namespace blcp {
 constexpr int ROWS_MIN = 32, ROWS_MAX = 512, COLS_MAX = 1024, RADIUS_MAX = 40, STRIP_COLS = 16;
 constexpr int VARIANT = 11;        // blhip_timing::fwd_kernel_variant / bwd_kernel_variant of a pass on these kernels
 
-// what the decision reads: everything ChainRun::setup (blhip_fit_paths.hpp) knows about the batch before it plans the launches
+// what the decision reads: everything chain_admit (blhip_chain_plan.hpp: clamp_facts) knows about the batch before plan_chainres plans the launches
 struct ClampFacts {
     int ndim = 2;
     bool gaussian_recurrence = true;   // the Gaussian model, evaluated by the likelihood recurrence (no table, no per-cell exponential)

@@ -308,25 +308,66 @@ inline bool chain_forced_fail(const BatchEnv &E, int stage) {
     return (int64_t)E.ctx->option("chain_force_fail_batch", -1.0) == E.bi && (int)E.ctx->option("chain_force_fail_stage", 0.0) == stage;
 }
 
-// what blcp::chain_clamp_envelope reads, from the batch (restarts / same_taps: filled in behind plan_chainres); false: a clamp mode the
-// kernels do not carry
-inline bool clamp_facts(const BatchEnv &E, bool gauss, blcp::ClampFacts &f) {
-    const ChainProgram &prog = *E.prog;
-    f.ndim = E.p->ndim; f.gaussian_recurrence = gauss;
-    f.n0 = E.g.n0; f.n1 = E.g.n1; f.radius0 = prog.LW0; f.radius1 = prog.LW1;
-    f.composed = prog.multi;
-    f.resumed = E.ff.resume; f.carried = E.ff.carry; f.backward_init = E.p->backward_init != nullptr;
-    f.cus = std::min(E.ctx->num_cus, 256);
-    f.regime_switch_only = prog.other_clamp && !prog.dense_clamp && !prog.has_shift;
-    for (size_t e = 0; e < prog.cmodeF.size() && f.regime_switch_only; ++e) f.regime_switch_only = prog.cmodeF[e] <= 2 && prog.cmodeB[e] <= 2;
-    return f.regime_switch_only;
+// What the route of the path reads (blhip_chain_plan.hpp: its decisions are pure functions of these): the options, once per batch ...
+inline ChainOptions chain_options(const blhip_ctx *ctx) {
+    ChainOptions O;
+    auto flag = [&](const char *name) { return ctx->option(name, 1.0) != 0.0; };
+    O.chain_resident = flag("chain_resident"); O.chain_table = flag("chain_table"); O.chain_ax1 = flag("chain_ax1"); O.chain_wide = flag("chain_wide");
+    O.chain_clamp = (int)ctx->option("chain_clamp", 1.0);
+    O.fuse_accumulate = flag("fuse_accumulate"); O.fold2 = flag("fold2"); O.fold2_cp = flag("fold2_cp"); O.chain_depad = flag("chain_depad");
+    O.share_prefix = flag("share_prefix"); O.skip_prefix = flag("skip_prefix"); O.carry_partials = flag("carry_partials");
+    O.chain_resident_lag = std::max(2, std::min(blc::MAXLAG, (int)ctx->option("chain_resident_lag", 4.0)));
+    return O;
+}
+
+// ... and the facts about the batch
+inline ChainFacts chain_facts(const BatchEnv &E, bool fast, bool use_rec) {
+    ChainFacts F;
+    F.ndim = E.p->ndim; F.obs_model = E.p->obs_model; F.use_rec = use_rec; F.d = E.d; F.has_lik_table = E.DT->lik != nullptr;
+    F.fast = fast; F.fast_but_clamp = E.gp->fast_but_clamp;
+    F.has_clamp = E.prog->has_clamp; F.LW0 = E.prog->LW0; F.LW1 = E.prog->LW1;
+    F.resume = E.ff.resume; F.carry = E.ff.carry; F.full = E.ff.full; F.keep = E.ff.keep; F.accumulate = E.ff.accumulate;
+    F.evidence_only = E.ff.evidence_only; F.forward_only = E.ff.forward_only; F.backward_init = E.p->backward_init != nullptr;
+    F.n0 = E.g.n0; F.n1 = E.g.n1; F.G = E.G; F.T = E.T; F.B = E.B;
+    F.chain_means = E.chain_means; F.allow_chainres = E.allow_chainres; F.resident_ok = E.ctx->resident_ok; F.num_cus = E.ctx->num_cus;
+    F.acc_aligned = ((uintptr_t)E.ctx->acc & 15) == 0;
+    return F;
+}
+
+// a memory admission: `need` bytes against a fraction of what is free + what the context already holds for the purpose
+inline bool chain_mem_admits(double need, double fraction, double own_cap) {
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    return chain_admits(need, fraction, (double)free_b, own_cap);
+}
+
+// development: where a step of strip 0 spends its time -- shader-clock cycles between the `n` stamps of a step, waves 0 and 2 (the kernels
+// wrote them to blhip_ctx::small: chain_prof_arm)
+inline void chain_prof_arm(blhip_ctx *ctx, hipStream_t st, blc::ChainParams &Q) {
+    ctx->small.ensure(2 * 16 * 16 * 8);
+    HIPCHECK(hipMemsetAsync(ctx->small.p, 0, 2 * 16 * 16 * 8, st));
+    Q.prof = ctx->small.as<unsigned long long>();
+}
+inline void chain_prof_dump(blhip_ctx *ctx, hipStream_t st, const char *tag, bool bwd, int nk, const char *const *names, int n) {
+    unsigned long long hh[2 * 16 * 16];
+    HIPCHECK(hipMemcpyAsync(hh, ctx->small.p, sizeof hh, hipMemcpyDeviceToHost, st));
+    sync_stream(ctx, st);
+    for (int wvi = 0; wvi < 2; ++wvi) {
+        const unsigned long long *h = hh + wvi * 256;
+        double acc[16] = {0}; int cnt = 0;
+        for (int q = 0; q < 16; ++q) { if (!h[q * 16 + n - 1] || !h[q * 16]) continue; ++cnt; for (int i = 1; i < n; ++i) acc[i] += (double)(h[q * 16 + i] - h[q * 16 + i - 1]); }
+        std::fprintf(stderr, "[%s %s NK %d wave %d] %d steps:", tag, bwd ? "bwd" : "fwd", nk, wvi ? 2 : 0, cnt);
+        double tot = 0; for (int i = 1; i < n; ++i) { std::fprintf(stderr, " %s %.0f", names[i], cnt ? acc[i] / cnt : 0.0); tot += cnt ? acc[i] / cnt : 0.0; }
+        std::fprintf(stderr, " | total %.0f\n", tot);
+    }
 }
 
 struct ChainRun {
     bool on = false;
+    ChainOptions opt;                              // the options of the batch (setup)
     ChainResPlan cp;
     blc::ChainParams CQ{};
-    int *d_order = nullptr;
+    int *d_order = nullptr, *d_tapid = nullptr, *d_tapid1 = nullptr;      // launch order; the chains' axis-0 / axis-1 tap sets
     unsigned char *d_ckF = nullptr, *d_ckB = nullptr;      // per (step, chain): what the chain kernels consume (ChainResPlan::ckF / ckB)
     size_t gran_bytes = 0;
     unsigned *d_abort = nullptr;
@@ -366,53 +407,54 @@ struct ChainRun {
     double fold_ref = -INFINITY;                    // the reference the batch's weights are relative to (the carried slots' one where they are continued)
     double fold_max = -INFINITY;                    // the batch's largest log weight
 
+    // The route (blhip_chain_plan.hpp decides, stage by stage) and what it needs on the device.  A batch that declines -- here or at one
+    // of the memory admissions -- keeps the launch-per-step kernels; it has by then allocated and uploaded what the steps before asked for.
     void setup(const BatchEnv &E, bool fast, bool use_rec, size_t &psz) {
-        blhip_ctx *ctx = E.ctx;
         const ChainProgram &prog = *E.prog;
-        const int64_t T = E.T, B = E.B;
-        const long long G = E.G;
-        // the likelihood: the Gaussian recurrence, or a table (every other model on a 2-D grid -- built on the device for the closed-form
-        // ones, evaluated by the caller otherwise: blc::chain_kernel TAB, geometries of <= 512 rows -- padded grids too --, radius <= 40, one chain per block)
-        const bool gauss = E.p->obs_model == BLHIP_OM_GAUSSIAN && use_rec && E.d <= blc::DMAX;
-        tab = E.p->obs_model == BLHIP_OM_TABLE && E.DT->lik != nullptr && ctx->option("chain_table", 1.0) != 0.0;
-        // walks on the second parameter too: the transposing kernels (blc::chainax_kernel; Gaussian recurrence, exact square geometries)
-        const bool may_ax1 = (gauss || tab) && prog.LW1 > 0 && ctx->option("chain_ax1", 1.0) != 0.0;
-        // RegimeSwitch batches (blhip_chainclamp.hpp): the envelope and the routing rule are blcp::chain_clamp_envelope / _route
-        const int clamp_opt = (int)ctx->option("chain_clamp", 1.0);
-        blcp::ClampFacts cf;
-        const bool clamp_try = prog.has_clamp && E.gp->fast_but_clamp && clamp_opt != 0 && clamp_facts(E, gauss, cf) && blcp::chain_clamp_envelope(cf);
-        if ((fast || clamp_try) && (gauss || tab) && !E.ff.resume && !E.ff.carry && !E.p->backward_init &&
-            (!prog.has_clamp || clamp_try) && (prog.LW1 == 0 || may_ax1) && (double)G * 8.0 < 4.0e9 && ctx->option("chain_resident", 1.0) != 0.0 && ctx->resident_ok &&
-            E.allow_chainres) {
-            cp.r0_max = (!tab && !clamp_try && ctx->option("chain_wide", 1.0) != 0.0) ? CHAIN_R0_MAX : FAST_R0_MAX;
-            cp.allow_ax1 = may_ax1;
-            on = plan_chainres(E.g, prog, *E.taps, B, T, E.ff.full, std::min(ctx->num_cus, 256), cp);
-            E.mark("  plan_chainres");
-            if (clamp_try) {
-                // (plan_chainres has checked: the prior first, ONE tap set per chain at every step, restarts noted)
-                cf.same_taps = on; cf.restarts = on && cp.has_reset;
-                on = on && blcp::chain_clamp_envelope(cf) && !cp.ax1 && cp.ntw <= 4 &&
-                     blcp::chain_clamp_route(clamp_opt, true, B, cp.strips, T, E.ff.full ? 2 : 1, std::min(ctx->num_cus, 256));
-                if (on) {
-                    clamp = true;
-                    if (cp.ntw == 3) { cp.ntw = 4; cp.n0p = 512; cp.pad = true; }          // (a 384-row grid runs padded inside 512 rows)
-                    for (int &nk : cp.round_nk) nk = nk <= 4 ? 4 : (nk + 3) / 4 * 4;       // (ring lengths 4, 8, 12 .. 24)
-                }
-            }
-            if (on && tab && cp.ntw > 4) on = false;
-            if (on && tab && cp.pad && cp.ntw >= 3 && !cp.ax1) on = false;      // (padded 384 / 512-row geometries with a likelihood table: no kernel -- never selected by a test or workload, pruned in round 5)
-            if (on && prog.LW1 > 0 && !cp.ax1) on = false;
-        }
+        const ChainFacts F = chain_facts(E, fast, use_rec);
+        opt = chain_options(E.ctx);
+        ChainAdmit A = chain_admit(F, opt, prog);
+        tab = A.tab;
+        if (!A.plan) return;
+        cp.r0_max = A.r0_max; cp.allow_ax1 = A.allow_ax1;
+        const bool planned = plan_chainres(E.g, prog, *E.taps, F.B, F.T, F.full, F.cus(), cp);
+        E.mark("  plan_chainres");
+        on = chain_settle(F, opt, A, planned, cp, clamp);
         if (!on) return;
         ax1 = cp.ax1;
         Gk = (long long)cp.n0p * cp.n1p;
+        upload_metadata(E);
+        if (ax1 && !both_axes_buffers(E)) return decline();
+        fill_params(E, psz);
+        // (no-stencil batches: only their folding backward pass reads the anchors)
+        if (!tab && !ax1 && (prog.LW0 > 0 || F.full) && !anchor_table(E)) return decline();
+        ChainFold f = chain_fold_plan(F, opt, prog, *E.taps, cp, tab, ax1, clamp);
+        bool keep = true;
+        if (chain_needs_depad(F, cp, ax1, f.post_private))
+            keep = depad = chain_padding_rule(F, opt, cp, chain_mem_admits(chain_depad_bytes(F, Gk), 0.8, (double)E.ctx->postpad.cap), f);
+        keep = keep && chain_fold_settle(F, cp, tab, ax1, f);
+        post_private = f.post_private; fused = f.fused; fold2 = f.fold2; slots_used = f.slots_used;
+        round_start_b = std::move(f.round_start_b); round_nk_b = std::move(f.round_nk_b);
+        if (!keep) return decline();
+        E.mark("  fold plan");
+        upload_prefix(E, chain_prefix_plan(F, opt, prog, cp, ax1, fused));
+        E.mark("  prefix plan");
+        if (fused) fold_buffers(E);
+    }
+
+    void decline() { on = false; ax1 = false; Gk = 0; }
+
+    // the per-chain and per-(step, chain) metadata of the kernels, carved out of blhip_ctx::resx
+    void upload_metadata(const BatchEnv &E) {
+        blhip_ctx *ctx = E.ctx;
+        const int64_t T = E.T, B = E.B;
         // (granule slots for 2 x cpr chains: the two-chain fold kernel runs rounds of that size)
         gran_bytes = carve_size((size_t)blc::NSLOT * 2 * cp.cpr * cp.strips * 2 * 8);
         ctx->resx.ensure(carve_size((size_t)B * 4) * 4 + gran_bytes + carve_size(64) + 2 * carve_size((size_t)T * B));
         char *rc = ctx->resx.as<char>();
         d_order = carve<int>(rc, (size_t)B);
-        int *d_tapid = carve<int>(rc, (size_t)B);
-        int *d_tapid1 = carve<int>(rc, (size_t)B);
+        d_tapid = carve<int>(rc, (size_t)B);
+        d_tapid1 = carve<int>(rc, (size_t)B);
         d_tshare = carve<int>(rc, (size_t)B);
         CQ.gran = carve<unsigned long long>(rc, (size_t)blc::NSLOT * 2 * cp.cpr * cp.strips * 2);
         d_abort = carve<unsigned>(rc, 16);
@@ -428,160 +470,116 @@ struct ChainRun {
         HIPCHECK(hipMemcpyAsync(d_tapid1, cp.tap_id1.data(), (size_t)B * 4, hipMemcpyHostToDevice, E.st));
         sync_stream(ctx, E.st);
         E.mark("  chain metadata H2D");
-        if (ax1) {               // the exchange buffers of a launch's chain slots: [slot][2 step parities][Gk] tagged elements
-            xch_bytes = (size_t)cp.cpr * 2 * (size_t)Gk * 8;
-            {   // the exchange buffers and the likelihood table of the even steps are not part of chains_per_batch's budget: a long series
-                // on a large geometry declines the path here instead of failing in the allocator
-                const bool want_tab = tab || B <= 2;
-                const double need = (double)xch_bytes + (want_tab ? (double)((T + 1) / 2) * (double)Gk * 8.0 : 0.0);
-                size_t free_b = 0, total_b = 0;
-                (void)hipMemGetInfo(&free_b, &total_b);
-                if (need > 0.8 * ((double)free_b + (double)ctx->xch.cap + (double)ctx->axlik.cap)) { on = false; ax1 = false; Gk = 0; return; }
-            }
-            ctx->xch.ensure(xch_bytes);
-            CQ.xch = ctx->xch.as<double>(); CQ.xch_chain = 2 * Gk; CQ.tap_id1 = d_tapid1;
-            ax_mode = -1;             // (development: 0 write-through stores on any XCD, 1 one XCD per chain, 2 plain stores, 3 both = the default)
-            // the likelihood of the even time steps (epilogue in the transposed layout) as a table: an exp per cell there otherwise.  Measured
-            // (profiles/r05_notes.md): single fits are latency-bound and gain (200 x 200, radius 20: 7.9 -> 7.5 us per step); launches of
-            // eight chains sit on eight XCDs, every one of which fetches the table through the fabric the exchange already saturates
-            // (c4_both_axes 553 -> 578 ms): one or two chains only
-            const double tab_bytes = (double)((T + 1) / 2) * (double)Gk * 8.0;
-            constexpr double tab_opt = 1.0;
-            if (tab) {          // a tabulated model: every step reads its likelihood -- the even ones out of a transposed copy
-                if (tab_bytes >= 8.0e9) { on = false; ax1 = false; Gk = 0; return; }
-                ctx->axlik.ensure((size_t)tab_bytes);
-                blcl::chainax_lik_transpose(E.st, E.DT->lik, ctx->axlik.as<double>(), cp.n0p, E.g.n0, E.g.n1, (int)T);
-                HIPCHECK(hipGetLastError());
-                CQ.lik = ctx->axlik.as<double>(); CQ.lik_nat = E.DT->lik;
-            } else if (tab_opt != 0.0 && (B <= 2 || tab_opt == 2.0) && tab_bytes < 8.0e9) {
-                ctx->axlik.ensure((size_t)tab_bytes);
-                blcl::chainax_lik_table(E.st, cp.n0p, E.g.n0, E.g.n1, (int)T, E.d, E.rec_len, E.DT->m0, E.DT->colA, E.DT->colB, E.DT->rec, ctx->axlik.as<double>());
-                HIPCHECK(hipGetLastError());
-                CQ.lik = ctx->axlik.as<double>();
-            }
+    }
+
+    // both-axes kernels: the exchange buffers of a launch's chain slots, [slot][2 step parities][Gk] tagged elements, and the likelihood of
+    // the even time steps as a table.  -> false: they do not fit
+    bool both_axes_buffers(const BatchEnv &E) {
+        blhip_ctx *ctx = E.ctx;
+        const int64_t T = E.T, B = E.B;
+        xch_bytes = (size_t)cp.cpr * 2 * (size_t)Gk * 8;
+        // the likelihood of the even time steps (epilogue in the transposed layout) as a table: an exp per cell there otherwise.  Measured
+        // (profiles/r05_notes.md): single fits are latency-bound and gain (200 x 200, radius 20: 7.9 -> 7.5 us per step); launches of
+        // eight chains sit on eight XCDs, every one of which fetches the table through the fabric the exchange already saturates
+        // (c4_both_axes 553 -> 578 ms): one or two chains only
+        const double tab_bytes = (double)((T + 1) / 2) * (double)Gk * 8.0;
+        // the exchange buffers and the table are not part of chains_per_batch's budget: a long series on a large geometry declines the
+        // path here instead of failing in the allocator
+        const bool want_tab = tab || B <= 2;
+        if (!chain_mem_admits((double)xch_bytes + (want_tab ? tab_bytes : 0.0), 0.8, (double)ctx->xch.cap + (double)ctx->axlik.cap)) return false;
+        ctx->xch.ensure(xch_bytes);
+        CQ.xch = ctx->xch.as<double>(); CQ.xch_chain = 2 * Gk; CQ.tap_id1 = d_tapid1;
+        ax_mode = -1;             // (development: 0 write-through stores on any XCD, 1 one XCD per chain, 2 plain stores, 3 both = the default)
+        if (tab) {          // a tabulated model: every step reads its likelihood -- the even ones out of a transposed copy
+            if (tab_bytes >= CHAIN_AXLIK_MAX_BYTES) return false;
+            ctx->axlik.ensure((size_t)tab_bytes);
+            blcl::chainax_lik_transpose(E.st, E.DT->lik, ctx->axlik.as<double>(), cp.n0p, E.g.n0, E.g.n1, (int)T);
+            HIPCHECK(hipGetLastError());
+            CQ.lik = ctx->axlik.as<double>(); CQ.lik_nat = E.DT->lik;
+        } else if (B <= 2 && tab_bytes < CHAIN_AXLIK_MAX_BYTES) {
+            ctx->axlik.ensure((size_t)tab_bytes);
+            blcl::chainax_lik_table(E.st, cp.n0p, E.g.n0, E.g.n1, (int)T, E.d, E.rec_len, E.DT->m0, E.DT->colA, E.DT->colB, E.DT->rec, ctx->axlik.as<double>());
+            HIPCHECK(hipGetLastError());
+            CQ.lik = ctx->axlik.as<double>();
         }
+        return true;
+    }
+
+    // what every launch of the batch is told (pass: round_params adds the round's)
+    void fill_params(const BatchEnv &E, size_t &psz) {
+        const int64_t T = E.T, B = E.B;
         CQ.n0 = cp.n0p; CQ.n1 = cp.n1p; CQ.n0t = E.g.n0; CQ.n1t = E.g.n1; CQ.strips = cp.strips; CQ.T = (int)T; CQ.d = tab ? 0 : E.d; CQ.rec_len = E.rec_len;
-        CQ.lag = std::max(2, std::min(blc::MAXLAG, (int)ctx->option("chain_resident_lag", 4.0)));      // (lag 1 would need the sum of the step in flight)
+        CQ.lag = opt.chain_resident_lag;
         CQ.B = (int)B; CQ.nblk = cp.strips; CQ.tap_id = d_tapid; CQ.taps = E.M->taps; CQ.tap_off = E.M->off; CQ.tap_lw = E.M->lw;
         CQ.post_stride = (long long)T * Gk;
-        CQ.m0 = E.DT->m0; CQ.m1 = E.DT->m1; CQ.colA = E.DT->colA; CQ.colB = E.DT->colB; CQ.rec = E.DT->rec; if (tab && !ax1) CQ.lik = E.DT->lik; CQ.step0 = E.step0;      // (both-axes kernels: CQ.lik is their table of the even steps, set above)
-        CQ.timeout_ticks = (unsigned long long)(resident_timeout_s(ctx, T) * 1e8);
+        CQ.m0 = E.DT->m0; CQ.m1 = E.DT->m1; CQ.colA = E.DT->colA; CQ.colB = E.DT->colB; CQ.rec = E.DT->rec; if (tab && !ax1) CQ.lik = E.DT->lik; CQ.step0 = E.step0;      // (both-axes kernels: CQ.lik is their table of the even steps, set by both_axes_buffers)
+        CQ.timeout_ticks = (unsigned long long)(resident_timeout_s(E.ctx, T) * 1e8);
         psz = std::max(psz, (size_t)T * B * NRED * cp.strips);
-        if (!tab && !ax1 && (prog.LW0 > 0 || E.ff.full)) {          // (no-stencil batches: only their folding backward pass reads it)
-            // the anchors of the likelihood recurrence: the same for every chain of the batch (same data, same grid) -- tabulated once, 32 bytes
-            // per lane and step (C4: 134 MB), read by the kernels a step ahead (ChainParams::anch)
-            const size_t ab = (size_t)T * blc::NW * cp.strips * 64 * 4 * sizeof(double);
-            size_t free_b = 0, total_b = 0;
-            (void)hipMemGetInfo(&free_b, &total_b);
-            if ((double)ab > 0.5 * ((double)free_b + (double)ctx->anchbuf.cap)) { on = false; return; }
-            ctx->anchbuf.ensure(ab);
-            blc::AnchorParams AP{};
-            AP.T = (int)T; AP.d = E.d; AP.rec_len = E.rec_len; AP.strips = cp.strips; AP.rows_per_wave = cp.ntw * blc::TM; AP.n0t = E.g.n0; AP.n1t = E.g.n1;
-            AP.m0 = E.DT->m0; AP.colA = E.DT->colA; AP.colB = E.DT->colB; AP.rec = E.DT->rec; AP.out = ctx->anchbuf.as<double>();
-            BL_LAUNCH(blc::anchor_table_kernel, dim3((unsigned)cp.strips, (unsigned)T), dim3(blc::NT), 0, E.st, AP);
-            HIPCHECK(hipGetLastError());
-            CQ.anch = ctx->anchbuf.as<double>();
-            E.mark("  anchor table queued");
+    }
+
+    // the anchors of the likelihood recurrence: the same for every chain of the batch (same data, same grid) -- tabulated once, 32 bytes
+    // per lane and step (C4: 134 MB), read by the kernels a step ahead (ChainParams::anch).  -> false: the table does not fit
+    bool anchor_table(const BatchEnv &E) {
+        blhip_ctx *ctx = E.ctx;
+        const int64_t T = E.T;
+        const size_t ab = (size_t)T * blc::NW * cp.strips * 64 * 4 * sizeof(double);
+        if (!chain_mem_admits((double)ab, 0.5, (double)ctx->anchbuf.cap)) return false;
+        ctx->anchbuf.ensure(ab);
+        blc::AnchorParams AP{};
+        AP.T = (int)T; AP.d = E.d; AP.rec_len = E.rec_len; AP.strips = cp.strips; AP.rows_per_wave = cp.ntw * blc::TM; AP.n0t = E.g.n0; AP.n1t = E.g.n1;
+        AP.m0 = E.DT->m0; AP.colA = E.DT->colA; AP.colB = E.DT->colB; AP.rec = E.DT->rec; AP.out = ctx->anchbuf.as<double>();
+        BL_LAUNCH(blc::anchor_table_kernel, dim3((unsigned)cp.strips, (unsigned)T), dim3(blc::NT), 0, E.st, AP);
+        HIPCHECK(hipGetLastError());
+        CQ.anch = ctx->anchbuf.as<double>();
+        E.mark("  anchor table queued");
+        return true;
+    }
+
+    // the shared prefix of change-point chains (chain_prefix_plan): the steps every chain leaves to the providing one -> device
+    void upload_prefix(const BatchEnv &E, ChainPrefix P) {
+        share_prefix = P.share; skip_prefix = P.skip; prov = P.prov;
+        if (P.saved <= 0) return;
+        HIPCHECK(hipMemcpyAsync(d_tshare, P.tsh.data(), (size_t)E.B * 4, hipMemcpyHostToDevice, E.st));
+        sync_stream(E.ctx, E.st);
+        shared_steps = P.saved; h_tshare = std::move(P.tsh);
+        CQ.tshare = d_tshare; CQ.bprov = prov; CQ.skip_prefix = skip_prefix ? 1 : 0;
+    }
+
+    // fused fold: the partial accumulators, one per block column of a launch, and the per-chain scales and weights of prepare_fold
+    void fold_buffers(const BatchEnv &E) {
+        blhip_ctx *ctx = E.ctx;
+        const int64_t T = E.T, B = E.B;
+        // (carried slots of earlier batches: a larger buffer or another layout takes them into the accumulator first)
+        if (ctx->part.live && ((size_t)slots_used * T * Gk * 8 > ctx->accpart.cap || ctx->part.T != (int)T || ctx->part.Gk != Gk || ctx->part.n0 != E.g.n0 ||
+                               ctx->part.n1 != E.g.n1 || ctx->part.n0p != cp.n0p || ctx->part.ax1 != (ax1 ? 1 : 0)))
+            flush_partials(ctx, E.st, E.fold_ev);
+        ctx->accpart.ensure((size_t)slots_used * T * Gk * 8);
+        ctx->accw.ensure(carve_size((size_t)T * B * 8) + 2 * carve_size((size_t)B * 8) + carve_size(8192));
+        char *wc = ctx->accw.as<char>();
+        d_fold_sfwd = carve<double>(wc, (size_t)T * B);
+        d_fold_w = carve<double>(wc, (size_t)B);
+        d_fold_inf = carve<double>(wc, (size_t)B);
+        d_zeros = carve<double>(wc, 1024);      // (8 KB: a tile's four cells are read at base + 0 / 512 / 1024 / 1536 bytes, base < 4 KB)
+    }
+
+    // what the launch of chains order[s0 .. s1) is told
+    blc::ChainParams round_params(const BatchEnv &E, bool bwd, double *psum, int s0, int s1, bool fold_now, bool first) const {
+        blc::ChainParams Q = CQ;
+        Q.chain_ids = d_order + s0;
+        Q.nslots = s1 - s0;
+        Q.psum = psum;
+        Q.src0 = bwd ? E.DT->uniform : E.DT->prior;
+        Q.kinds = cp.has_reset ? (bwd ? d_ckB : d_ckF) : nullptr;
+        Q.reset = E.DT->reset;
+        Q.post = E.d_post;
+        Q.means = bwd ? (E.chain_means ? 1 : 0) : (E.ff.forward_only ? 1 : 0);
+        Q.strip_major = (post_private || cp.pad || ax1) ? 1 : 0;            // (the stored sequence is private to the fit then)
+        if (fold_now) {
+            Q.sfwd = d_fold_sfwd; Q.wchain = d_fold_w; Q.infirst = d_fold_inf;
+            Q.part = E.ctx->accpart.as<double>(); Q.part_stride = (long long)E.T * Gk;
+            Q.zeros = d_zeros; Q.part_fresh = (first && part_fresh0) ? 1 : 0;          // (every slot is first used by the first launch: no memset)
         }
-        // (the separate fold reads pairs of cells: an even number of columns; the fused fold's partials take any grid -- fold_parts_kernel)
-        post_private = E.ff.accumulate && E.ff.full && !E.ff.keep && !E.ff.carry && ((G & 1) == 0 || cp.pad || ax1) && ((uintptr_t)ctx->acc & 15) == 0;
-        // (a restart inside a FILTERING chain would need sum(alpha T(reset)) for the predicted sums: such batches store and fold separately)
-        // (clamped batches store and fold afterwards: the predicted sums of the fused fold do not survive a clamp)
-        fused = post_private && !cp.mixed && !clamp && ctx->option("fuse_accumulate", 1.0) != 0.0;
-        if (fused && cp.has_reset) {
-            // change-point batches: the predicted sums survive a restart only through the two-chain fold kernel's restart rule, and
-            // only if the two passes restart at the same places (backward step t restarts <=> forward step t + 1 does: unit-spaced
-            // time stamps, transitionModels.py:316-317)
-            // (the both-axes kernels' fold has no restart rule: such batches store and fold separately -- ADVICE r05)
-            bool aligned = !tab && !ax1 && !E.chain_means && fold2_shape(cp.ntw) && ctx->option("fold2", 1.0) != 0.0 && ctx->option("fold2_cp", 1.0) != 0.0;
-            for (int64_t b = 0; b < B && aligned; ++b)
-                for (int64_t t = 0; t + 1 < T && aligned; ++t)
-                    aligned = (prog.kindB[(size_t)t * B + b] != SRC_PREV) == (prog.kindF[(size_t)(t + 1) * B + b] != SRC_PREV);
-            fused = aligned;
-        }
-        slots_used = (int)std::min<int64_t>(cp.cpr, B);
-        if (fused && !tab && !ax1 && !E.chain_means && fold2_shape(cp.ntw) && ctx->option("fold2", 1.0) != 0.0) {      // (the two-chain kernel has no table / both-axes flavour)
-            fold2 = true;
-            const int per = 2 * cp.cpr;
-            for (int64_t s0 = 0; s0 < B; s0 += per) {
-                const int64_t s1 = std::min<int64_t>(B, s0 + per);
-                const int tp = cp.tap_id[cp.order[s1 - 1]];                   // (sorted by radius: the last chain of the round is its widest)
-                const int r0 = std::max(4, ((tp >= 0 ? E.taps->lw[tp] : 0) + 3) / 4 * 4);
-                round_start_b.push_back((int)s0);
-                round_nk_b.push_back(prog.LW0 == 0 ? 4 : (blc::TM + 2 * r0) / 4);          // (4: the no-stencil variant)
-            }
-            round_start_b.push_back((int)B);
-            slots_used = (int)std::min<int64_t>(cp.cpr, (B + 1) / 2);
-        }
-        // a grid smaller than the geometry: only fits whose sequences are private to the fit (strip-major, padded) -- evidence-only fits
-        // and full fits of hyper- / change-point studies (folded in the backward kernel, or stored and folded by accumulate_pad_kernel);
-        // everything else keeps the launch-per-step kernels
-        // (the both-axes kernels keep their sequences in two alternating strip-major layouts: never the API's, also on an exact geometry)
-        if ((cp.pad || ax1) && !(E.ff.evidence_only || post_private)) {
-            // ... or, at the price of a second sequence in memory, any fit: the posteriors are copied out of the padded layout afterwards
-            // (<= 512 rows: every flavour has a padded storing kernel; 1024 rows: forward passes only)
-            size_t free_b = 0, total_b = 0;
-            (void)hipMemGetInfo(&free_b, &total_b);
-            const double need = (double)B * (double)T * (double)Gk * 8.0;
-            depad = ctx->option("chain_depad", 1.0) != 0.0 && (cp.ntw <= 4 || !E.ff.full) &&
-                    need < 0.8 * ((double)free_b + (double)ctx->postpad.cap);
-            if (!depad) { on = false; fused = false; fold2 = false; return; }
-            fused = false; fold2 = false;
-        }
-        // (<= 512 rows: what the two-chain kernel does not fold -- per-chain means asked for through the C-ABI, option fold2 = 0 -- is stored and
-        //  folded separately: the Gaussian one-chain kernel has no folding flavour there (round 6).  The tabulated one has, on exact
-        //  geometries; 1024 rows: the one-chain kernel is the only folding one, exact and padded; the both-axes kernels fold on padded grids too)
-        if (fused && !fold2 && cp.ntw <= 4 && !ax1 && (cp.pad || !tab)) fused = false;
-        if (cp.pad && cp.ntw > 4 && E.ff.full && !fused) { on = false; fold2 = false; return; }
-        // Change-point batches without a stencil whose backward pass folds: the chains are identical up to their first restart.  The chain
-        // with the LATEST first restart stores all its states; every other chain stores only from its own first restart on, and the
-        // folding backward pass reads the earlier ones from that chain (same values bit for bit: same kernel, same strips, same lagged
-        // scales).  Halves the forward pass's stores, and the backward pass's reads of those states hit the cache (the chains of a launch
-        // read the same rows at about the same time).  (Only when nothing overwrites the stored states: the fused fold.)
-        // The same chains need not COMPUTE that prefix either (a restart consumes the reset distribution, not the chain's past): with
-        // skip_prefix a chain's forward pass begins at its first restart, the sums of its earlier steps are copied from the providing chain
-        // (forward_ok).  Also for evidence-only fits, which store nothing.  C5: 250 chains x 1000 steps -> 125 k chain-steps of 250 k.
-        E.mark("  fold plan");
-        share_prefix = false; skip_prefix = false;
-        const bool may_share = fused && ctx->option("share_prefix", 1.0) != 0.0;
-        const bool may_skip = (fused || E.ff.evidence_only) && ctx->option("skip_prefix", 1.0) != 0.0;
-        if ((may_share || may_skip) && cp.has_reset && prog.LW0 == 0 && !cp.mixed && !ax1 && B >= 2) {      // (blc::chainax_kernel reads neither tshare nor skip_prefix)
-            std::vector<int> tfirst((size_t)B, (int)T);
-            bool plain = true;
-            for (int64_t b = 0; b < B && plain; ++b) {
-                plain = prog.kindF[b] == SRC_PRIOR && cp.tap_id[b] < 0 && cp.tap_id1[b] < 0;
-                for (int64_t t = 1; t < T; ++t)
-                    if (prog.kindF[(size_t)t * B + b] != SRC_PREV) { tfirst[b] = (int)t; break; }
-            }
-            if (plain) {
-                prov = 0;
-                for (int64_t b = 1; b < B; ++b) if (tfirst[b] > tfirst[prov]) prov = (int)b;
-                std::vector<int> tsh((size_t)B, 0);
-                long long saved = 0;
-                for (int64_t b = 0; b < B; ++b)
-                    if (b != prov) { tsh[b] = std::min(tfirst[b], tfirst[prov]); saved += tsh[b]; }
-                if (saved > 0) {
-                    HIPCHECK(hipMemcpyAsync(d_tshare, tsh.data(), (size_t)B * 4, hipMemcpyHostToDevice, E.st));
-                    sync_stream(ctx, E.st);
-                    share_prefix = may_share || may_skip; skip_prefix = may_skip; shared_steps = saved; h_tshare = tsh;
-                    CQ.tshare = d_tshare; CQ.bprov = prov; CQ.skip_prefix = skip_prefix ? 1 : 0;
-                }
-            }
-        }
-        E.mark("  prefix plan");
-        if (fused) {
-            // (carried slots of earlier batches: a larger buffer or another layout takes them into the accumulator first)
-            if (ctx->part.live && ((size_t)slots_used * T * Gk * 8 > ctx->accpart.cap || ctx->part.T != (int)T || ctx->part.Gk != Gk || ctx->part.n0 != E.g.n0 ||
-                                   ctx->part.n1 != E.g.n1 || ctx->part.n0p != cp.n0p || ctx->part.ax1 != (ax1 ? 1 : 0)))
-                flush_partials(ctx, E.st, E.fold_ev);
-            ctx->accpart.ensure((size_t)slots_used * T * Gk * 8);
-            ctx->accw.ensure(carve_size((size_t)T * B * 8) + 2 * carve_size((size_t)B * 8) + carve_size(8192));
-            char *wc = ctx->accw.as<char>();
-            d_fold_sfwd = carve<double>(wc, (size_t)T * B);
-            d_fold_w = carve<double>(wc, (size_t)B);
-            d_fold_inf = carve<double>(wc, (size_t)B);
-            d_zeros = carve<double>(wc, 1024);      // (8 KB: a tile's four cells are read at base + 0 / 512 / 1024 / 1536 bytes, base < 4 KB)
-        }
+        return Q;
     }
 
     // one pass: the launches of the rounds follow each other on the stream
@@ -591,31 +589,15 @@ struct ChainRun {
         const int64_t T = E.T, B = E.B;
         HIPCHECK(hipMemsetAsync(psum, 0, (size_t)T * B * NRED * cp.strips * 8, st));
         HIPCHECK(hipMemsetAsync(d_abort, 0, 64, st));
-        const bool two = bwd && fused && fold2;
+        const bool fold_now = bwd && fused, two = fold_now && fold2;
         const std::vector<int> &rstart = two ? round_start_b : cp.round_start, &rnk = two ? round_nk_b : cp.round_nk;
+        const bool store = fold_now ? false : (bwd || !E.ff.evidence_only);
         for (size_t r = 0; r + 1 < rstart.size(); ++r) {
-            blc::ChainParams Q = CQ;
             HIPCHECK(hipMemsetAsync(CQ.gran, 0, gran_bytes, st));       // tags restart with every launch
-            Q.chain_ids = d_order + rstart[r];
-            Q.nslots = rstart[r + 1] - rstart[r];
-            Q.psum = psum;
-            Q.src0 = bwd ? E.DT->uniform : E.DT->prior;
-            Q.kinds = cp.has_reset ? (bwd ? d_ckB : d_ckF) : nullptr;
-            Q.reset = E.DT->reset;
-            Q.post = E.d_post;
-            Q.means = bwd ? (E.chain_means ? 1 : 0) : (E.ff.forward_only ? 1 : 0);
-            Q.strip_major = (post_private || cp.pad || ax1) ? 1 : 0;            // (the stored sequence is private to the fit then)
-            const bool fold_now = bwd && fused;
-            if (fold_now) {
-                Q.sfwd = d_fold_sfwd; Q.wchain = d_fold_w; Q.infirst = d_fold_inf;
-                Q.part = ctx->accpart.as<double>(); Q.part_stride = (long long)T * Gk;
-                Q.zeros = d_zeros; Q.part_fresh = (r == 0 && part_fresh0) ? 1 : 0;          // (every slot is first used by the first launch: no memset)
-                touched_parts = true;
-            }
+            blc::ChainParams Q = round_params(E, bwd, psum, rstart[r], rstart[r + 1], fold_now, r == 0);
+            if (fold_now) touched_parts = true;
 #ifdef BLC_PROF
-            ctx->small.ensure(2 * 16 * 16 * 8);
-            HIPCHECK(hipMemsetAsync(ctx->small.p, 0, 2 * 16 * 16 * 8, st));
-            Q.prof = ctx->small.as<unsigned long long>();
+            chain_prof_arm(ctx, st, Q);
 #endif
             if (ax1) {
                 HIPCHECK(hipMemsetAsync(CQ.xch, 0, xch_bytes, st));           // (tags restart with every launch)
@@ -626,69 +608,26 @@ struct ChainRun {
                 //  mask -- the plain stores' lines would never reach a consumer on another XCD: write-through stores in dispatch order then)
                 Q.xch_mode = ax_mode >= 0 ? ax_mode : (ctx->xcd_order_ok ? 3 : 0);
                 const bool prof = ctx->option("chain_prof", 0.0) != 0.0;
-                if (prof) {
-                    ctx->small.ensure(2 * 16 * 16 * 8);
-                    HIPCHECK(hipMemsetAsync(ctx->small.p, 0, 2 * 16 * 16 * 8, st));
-                    Q.prof = ctx->small.as<unsigned long long>();
-                }
-                launch_chainax(st, Q, rnk[r], cp.ntw, bwd, fold_now ? false : (bwd || !E.ff.evidence_only), cp.pad);
-                if (prof) {          // where a step of strip 0 spends its time (shader-clock cycles between stamps; waves 0 and 2)
-                    unsigned long long hh[2 * 16 * 16];
-                    HIPCHECK(hipMemcpyAsync(hh, ctx->small.p, sizeof hh, hipMemcpyDeviceToHost, st));
-                    sync_stream(ctx, st);
-                    static const char *names[6] = {"start", "filter 1 + publish", "gather", "barrier", "filter 2 + epilogue", "sums + barrier"};
-                    for (int wvi = 0; wvi < 2; ++wvi) {
-                        const unsigned long long *h = hh + wvi * 256;
-                        double acc[6] = {0}; int n = 0;
-                        for (int q = 0; q < 16; ++q) { if (!h[q * 16 + 5] || !h[q * 16]) continue; ++n; for (int i = 1; i < 6; ++i) acc[i] += (double)(h[q * 16 + i] - h[q * 16 + i - 1]); }
-                        std::fprintf(stderr, "[blc ax prof %s NK %d wave %d] %d steps:", bwd ? "bwd" : "fwd", rnk[r], wvi ? 2 : 0, n);
-                        double tot = 0; for (int i = 1; i < 6; ++i) { std::fprintf(stderr, " %s %.0f", names[i], n ? acc[i] / n : 0.0); tot += n ? acc[i] / n : 0.0; }
-                        std::fprintf(stderr, " | total %.0f\n", tot);
-                    }
-                }
+                if (prof) chain_prof_arm(ctx, st, Q);
+                launch_chainax(st, Q, rnk[r], cp.ntw, bwd, store, cp.pad);
+                static const char *ax_names[6] = {"start", "filter 1 + publish", "gather", "barrier", "filter 2 + epilogue", "sums + barrier"};
+                if (prof) chain_prof_dump(ctx, st, "blc ax prof", bwd, rnk[r], ax_names, 6);
             }
             else if (clamp) {
                 blc::ClampParams CP{Q, bwd ? E.M->cmodeB : E.M->cmodeF, bwd ? E.M->limitB : E.M->limitF};
                 launch_chain_clamp(st, CP, rnk[r], cp.ntw, bwd, bwd || !E.ff.evidence_only);
             }
             else if (two) launch_fold2(st, Q, rnk[r], cp.ntw, cp.pad);
-            else launch_chain(st, Q, rnk[r], cp.ntw, bwd, fold_now ? false : (bwd || !E.ff.evidence_only), cp.pad);
-            {   // HBM: only what the fit keeps -- forward the stored state (8 B; nothing for evidence-only fits), backward the stored
-                // state in + the posterior out (16 B) or + the read-modify-write of the partial accumulator (24 B; shared by the two
-                // chains of a block of the two-chain fold kernel: 8 + 16 / 2 = 16 B)
-                double cells = (double)Q.nslots * Gk * T;
-                if (!bwd && skip_prefix)               // (chain-steps the forward pass does not run)
-                    for (int q = rstart[r]; q < rstart[r + 1]; ++q) cells -= (double)h_tshare[cp.order[q]] * Gk;
-                double bytes = bwd ? (fold_now ? (two ? 8.0 + 16.0 * ((Q.nslots + 1) / 2) / (double)Q.nslots : 24.0) : 16.0) : (E.ff.evidence_only ? 0.0 : 8.0);
-                // (both-axes kernels: the transposing exchange of a step leaves the XCD's L2 as well -- 8 written + 8 read;
-                //  with the blocks of a chain on one XCD the reads mostly hit that L2: the PMC counters say what really moves)
-                if (ax1) bytes += 16.0;
-                const int r0 = (4 * rnk[r] - blc::TM) / 2;
-                double shared = 0.0;                                  // stored states not written (forward) / read once per launch instead of once per chain (backward)
-                if (share_prefix && (bwd ? fold_now : !E.ff.evidence_only)) {
-                    long long sum = 0, mx = 0;
-                    for (int q = rstart[r]; q < rstart[r + 1]; ++q) { const long long v = h_tshare[cp.order[q]]; sum += v; mx = std::max(mx, v); }
-                    shared = (double)(bwd ? sum - mx : sum) * Gk * 8.0;
-                }
-                // (tabulated likelihood: the table of the pass is read once per launch -- its chains read the same rows at about the same time)
-                const double table = tab ? (double)T * Gk * 8.0 : 0.0;
-                account(ctx, bwd, cells * bytes - shared + table, cells * ((rnk[r] > 4 ? band_stencil_flop(r0) * (ax1 ? 2.0 : 1.0) : 0.0) + (bwd ? EPI_BWD_FLOP : EPI_FWD_FLOP)));
-            }
+            else launch_chain(st, Q, rnk[r], cp.ntw, bwd, store, cp.pad);
+            ChainLaunch L;
+            L.nslots = Q.nslots; L.Gk = Gk; L.T = T; L.bwd = bwd; L.fold_now = fold_now; L.two = two; L.ax1 = ax1; L.tab = tab;
+            L.evidence_only = E.ff.evidence_only; L.nk = rnk[r]; L.share_prefix = share_prefix; L.skip_prefix = skip_prefix;
+            L.tshare = h_tshare.data(); L.chains = cp.order.data() + rstart[r];
+            const ChainLaunchCost cost = chain_launch_cost(L, bwd ? EPI_BWD_FLOP : EPI_FWD_FLOP, band_stencil_flop(chain_band_radius(rnk[r])));
+            account(ctx, bwd, cost.bytes, cost.flops);
 #ifdef BLC_PROF
-            {   // development build: where a step of strip 0 spends its time (shader-clock cycles between stamps; waves 0 and 2)
-                unsigned long long hh[2 * 16 * 16];
-                HIPCHECK(hipMemcpyAsync(hh, ctx->small.p, sizeof hh, hipMemcpyDeviceToHost, st));
-                sync_stream(ctx, st);
-                static const char *names[8] = {"start", "ring", "chain0", "scale+anchor", "epi0", "tiles1..", "sums", "barrier"};
-                for (int wvi = 0; wvi < 2; ++wvi) {
-                    const unsigned long long *h = hh + wvi * 256;
-                    double acc[8] = {0}; int n = 0;
-                    for (int q = 0; q < 16; ++q) { if (!h[q * 16 + 7] || !h[q * 16]) continue; ++n; for (int i = 1; i < 8; ++i) acc[i] += (double)(h[q * 16 + i] - h[q * 16 + i - 1]); }
-                    std::fprintf(stderr, "[blc prof %s NK %d wave %d] %d steps:", bwd ? "bwd" : "fwd", rnk[r], wvi ? 2 : 0, n);
-                    double tot = 0; for (int i = 1; i < 8; ++i) { std::fprintf(stderr, " %s %.0f", names[i], n ? acc[i] / n : 0.0); tot += n ? acc[i] / n : 0.0; }
-                    std::fprintf(stderr, " | total %.0f\n", tot);
-                }
-            }
+            static const char *names[8] = {"start", "ring", "chain0", "scale+anchor", "epi0", "tiles1..", "sums", "barrier"};
+            chain_prof_dump(ctx, st, "blc prof", bwd, rnk[r], names, 8);
 #endif
         }
     }
@@ -723,7 +662,7 @@ struct ChainRun {
         // e-folds above it would overflow them: the carried slots go into the accumulator first and the batch starts afresh)
         fold_max = fold_ref;
         part_fresh0 = true;
-        if (ctx->part.live && ctx->option("carry_partials", 1.0) != 0.0) {
+        if (ctx->part.live && opt.carry_partials) {
             if (!(fold_ref - ctx->part.ref <= 500.0)) flush_partials(ctx, E.st, E.fold_ev);
             else { fold_ref = ctx->part.ref; part_fresh0 = false; }
         } else if (ctx->part.live) flush_partials(ctx, E.st, E.fold_ev);

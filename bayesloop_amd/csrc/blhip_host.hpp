@@ -125,7 +125,7 @@ struct blhip_ctx {
     long long resident_giveups = 0;
     int resident_last_reason = 0;                  // BLHIP_FALLBACK_* of the last resident batch that fell back
     int num_cus = 0;
-    DevBuf accw;                 // device copies of the fused fold's per-chain scales and weights (ChainRun::setup)
+    DevBuf accw;                 // device copies of the fused fold's per-chain scales and weights (ChainRun::fold_buffers)
     DevBuf postpad;              // padded strip-major sequence of a chain-resident batch whose posteriors are handed out (de-padded into post)
     DevBuf hsrc;                 // the axis-1 pre-pass's output of one step (blhip_hwide.hpp)
     DevBuf stagebuf, stagemeta;  // composed transitions: two stage outputs (+ their partials) of a step, the stages' per-chain programs (blhip_batch.hpp)

@@ -1,6 +1,6 @@
 """
 RegimeSwitch inside the chain-resident kernel on two-parameter grids (bayesloop_amd/csrc/blhip_chainclamp.hpp: blc::chain_clamp_kernel;
-selectors: ChainRun::setup in blhip_fit_paths.hpp, blcp::chain_clamp_envelope / chain_clamp_route in blhip_chainclamp_plan.hpp).
+selectors: chain_admit / chain_settle in blhip_chain_plan.hpp, run by ChainRun::setup in blhip_fit_paths.hpp; blcp::chain_clamp_envelope / chain_clamp_route in blhip_chainclamp_plan.hpp).
 
 Every instantiation -- ring length 4, 8 .. 24 x 128 / 256 / 512 rows x {forward without storing, forward storing, backward storing} -- is
 launched on the smallest grids with more than one strip and held to the CPU oracle at the parity bar (compare.GPU_TOL); every case asserts

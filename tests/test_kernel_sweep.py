@@ -86,7 +86,7 @@ def run(c, expect, forbid_fallback=True, tol=None):
     return S
 
 
-# ---- the chain-resident kernels (blhip_chainres.hpp; selectors: plan_chainres, ChainRun::setup, blhip_chain_tu.hip: launch_k / launch_k_tab /
+# ---- the chain-resident kernels (blhip_chainres.hpp; selectors: plan_chainres and the stages of blhip_chain_plan.hpp that ChainRun::setup runs, blhip_chain_tu.hip: launch_k / launch_k_tab /
 #      launch_fold2_k): ring length NK = (16 + 2 r0) / 4 for the band radius r0 = 4, 8, .. 80 of the widest chain of a launch (NK = 4: no stencil),
 #      tiles per wave NTW = rows of the geometry / 128, forward / backward, storing or not (folding), padded or exact, tabulated likelihood --------
 
@@ -145,7 +145,7 @@ def test_chain_resident_kernel_instantiations(tab, ntw, pad, nk):
         run(dict(study='Study', data=('series', seed + 1, T), om=om, tm=tm), [k % ('false', 'true'), k % ('true', 'true')])
 
 
-# ---- walks on both parameters (blhip_chainax.hpp; selector: plan_chainres ax1, launch_chainax): ring lengths 8 .. 24 in steps of 4 (radius <= 8 .. 40
+# ---- walks on both parameters (blhip_chainax.hpp; selector: plan_chainres ax1 in blhip_chain_plan.hpp, launch_chainax): ring lengths 8 .. 24 in steps of 4 (radius <= 8 .. 40
 #      on either axis), square geometries of 128 / 256 / 512 (NTW 1 / 2 / 4; the 128 and 256 kernels are the padded ones for every grid) ----------
 
 AX_SWEEP = [(ntw, pad, nk) for ntw, pad in ((1, True), (2, True), (4, False), (4, True)) for nk in (8, 12, 16, 20, 24)]
