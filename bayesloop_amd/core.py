@@ -432,39 +432,58 @@ class Study(object):
             raise ConfigurationError('Observation models with more than two parameters cannot be combined with the RegimeSwitch '
                                      'transition model.')
 
-    def _compile(self, silent=True):
-        """-> (FitProblem, program) ; program = [(kind, axis, model, hyper index)] in list order."""
-        om = self.observationModel
-        program = self.transitionModel._program(om.parameterNames)
+    def _checkGridDims(self):
         if not 1 <= len(self.gridSize) <= _abi.MAX_DIM:
             raise ConfigurationError('The MI355X engine supports observation models with 1 to {} parameters '
                                      '(got {}).'.format(_abi.MAX_DIM, len(self.gridSize)))
-        self._checkManyParameterProgram(program)
-        prior = self._computePrior(silent=silent)
+
+    def _restartPriors(self, program):
+        """-> (what a ChangePoint of the program restarts from, what an Independent model does), None where it has no such op."""
         reset = self._changepointPrior() if any(op[0] == _abi.OP_CHANGEPOINT for op in program) else None
         indep = None
         if any(op[0] == _abi.OP_INDEPENDENT for op in program):
             indep = self._changepointPrior() / np.prod(self.latticeConstant)      # sum 1 (reference transitionModels.py:351-360)
-        data = np.asarray(self.formattedData, dtype=float)
-        lik = lik_program = None
+        return reset, indep
+
+    def _likelihoodSource(self, segments, programs):
+        """-> (obs_model code, lik, lik_program) of a problem over the data ``segments``, the one place that decides where the likelihood
+        comes from: the model's code in the kernels; or, with ``programs``, its density as a program -- the (T, G) table is then built on
+        the device (bllp::lik_program_kernel), and nothing is evaluated here but the data-only subtrees (per step and data dimension) and
+        the tables of one-parameter functions (per axis); or the model's own pdf, evaluated once per time step on the host (the plug-in
+        interface of the reference).  ``Study._compile`` and the blocks of ``OnlineStudy.stepMany`` take programs.  ``OnlineStudy.step``
+        and the one-step problems of ``_fitHostTransition`` take none: one step at a time there is nothing to win over the host's one
+        (1, G) table (DESIGN.md §9 says so; ``_likelihoodProgram`` itself gives no reason), and a recorded series goes through
+        ``stepMany``."""
+        om = self.observationModel
         code = device_code(om)
-        prog = self._likelihoodProgram(om) if code == _abi.OM_TABLE else None
+        if code != _abi.OM_TABLE:
+            return code, None, None
+        prog = self._likelihoodProgram(om) if programs else None
         if prog is not None:
-            # the density as a program: the (T, G) table is built on the device (bllp::lik_program_kernel), nothing is evaluated here
-            # but the data-only subtrees (per step and data dimension) and the tables of one-parameter functions (per axis)
-            code = _abi.OM_PROGRAM
+            data = np.asarray(segments, dtype=float)
             lp_ops, lp_consts = prog.bind(self.marginalGrid)
-            lik_program = (lp_ops, lp_consts, prog.step_values(data.reshape(len(data), -1)))
-        elif code == _abi.OM_TABLE:
-            # the model's own pdf, evaluated once per time step on the host (plug-in interface of the reference)
-            lik = np.array([np.asarray(om.processedPdf(self.grid, seg), dtype=float) * np.ones(self.gridSize)
-                            for seg in self.formattedData])
+            return _abi.OM_PROGRAM, None, (lp_ops, lp_consts, prog.step_values(data.reshape(len(data), -1)))
+        return code, np.array([np.asarray(om.processedPdf(self.grid, seg), dtype=float) * np.ones(self.gridSize) for seg in segments]), None
+
+    def _problem(self, code, data, timestamps, prior, ops, **kw):
+        """The FitProblem of this study's grid and observation model; ``kw``: what only some problems carry (restart priors, the
+        likelihood table or program, the carried state's slot and resume time, a backward message)."""
+        return FitProblem(obs_model=code, marginal=self.marginalGrid, lattice=self.latticeConstant, data=data, timestamps=timestamps,
+                          prior=prior, ops=ops, seg_len=self.observationModel.segmentLength, **kw)
+
+    def _compile(self, silent=True):
+        """-> (FitProblem, program) ; program = [(kind, axis, model, hyper index)] in list order."""
+        program = self.transitionModel._program(self.observationModel.parameterNames)
+        self._checkGridDims()
+        self._checkManyParameterProgram(program)
+        prior = self._computePrior(silent=silent)
+        reset, indep = self._restartPriors(program)
+        data = np.asarray(self.formattedData, dtype=float)
+        code, lik, lik_program = self._likelihoodSource(self.formattedData, programs=True)
         program = self._expandProgram(program, len(data))
-        problem = FitProblem(obs_model=code, marginal=self.marginalGrid, lattice=self.latticeConstant, data=data,
-                             timestamps=np.asarray(self.formattedTimestamps, dtype=float), prior=prior,
-                             ops=[(op[0], op[1], op[4], op[5]) for op in program], reset_prior=reset, indep_prior=indep,
-                             lik=lik, lik_program=lik_program,
-                             seg_len=om.segmentLength)
+        problem = self._problem(code, data, np.asarray(self.formattedTimestamps, dtype=float), prior,
+                                [(op[0], op[1], op[4], op[5]) for op in program], reset_prior=reset, indep_prior=indep,
+                                lik=lik, lik_program=lik_program)
         return problem, program
 
     @staticmethod
@@ -567,6 +586,26 @@ class Study(object):
             print('    ! WARNING: Will omit further warnings about parameter boundaries.')
         self.fitWarningCounter += 1
 
+    def _beforeFit(self, keep):
+        """The device buffer behind the previous fit's posterior is about to be reused.  A fit that stores a new sequence (``keep``)
+        replaces it anyway; an evidence-only fit leaves the previous posteriorSequence in place in the reference (core.py:355-356
+        allocates only `if not evidenceOnly`), so it is brought to the host first."""
+        if keep:
+            self._posterior_pending = None
+        else:
+            self._materialize_posterior()
+
+    def _zeroNormaliser(self, phase, keep, release):
+        """A zero normaliser: the reference warns, sets logEvidence = -inf and returns early (core.py:390-400, 442-452).  ``release``: the
+        engine that kept this fit's posterior for the study (Study.fit), None where the fit kept it on the host (_fitHostTransition)."""
+        self._warnZero(phase)
+        self.logEvidence = -np.inf
+        if keep:
+            if release is not None:
+                release.release_posterior(self)
+            self._posterior_pending = None           # (the reference leaves np.empty garbage here; nothing is exposed)
+            self._posteriorSequence = None
+
     # ---- fit -----------------------------------------------------------------------------------------------------
     def fit(self, forwardOnly=False, evidenceOnly=False, silent=False):
         """
@@ -585,28 +624,14 @@ class Study(object):
         eng = _engine_mod.get_engine()
         T = len(self.formattedData)
         keep = not evidenceOnly
-        if self._posterior_pending is not None:
-            # the device buffer behind the previous fit's posterior is about to be reused.  A fit that stores a new sequence
-            # replaces it anyway; an evidence-only fit leaves the previous posteriorSequence in place in the reference
-            # (core.py:355-356 allocates only `if not evidenceOnly`), so it is brought to the host first.
-            if keep:
-                self._posterior_pending = None
-            else:
-                self._materialize_posterior()
+        self._beforeFit(keep)
         res = eng.fit(problem, self._opValueMatrix(program), forward_only=forwardOnly, evidence_only=evidenceOnly,
                       keep_posterior=keep, owner=self)
         self.lastTiming = res.timing
         self.logEvidence = float(res.log_evidence[0])
         self.localEvidence = res.local_evidence[0].copy()
         if res.abort_step[0] >= 0:
-            # zero normaliser: the reference warns, sets logEvidence = -inf and returns early (core.py:390-400, 442-452)
-            self._warnZero(int(res.abort_phase[0]))
-            self.logEvidence = -np.inf
-            if keep:
-                eng.release_posterior(self)
-                self._posterior_pending = None       # (the reference leaves np.empty garbage here; nothing is exposed)
-                self._posteriorSequence = None
-            return
+            return self._zeroNormaliser(int(res.abort_phase[0]), keep, release=eng)
         if not silent:
             print('    + Finished forward pass.')
             print('    + Log10-evidence: {:.5f}'.format(self.logEvidence / np.log(10)))
@@ -636,7 +661,7 @@ class Study(object):
         normalisation, sum(p / L) and the means (:436-464, :480-483) with the backward message handed over as
         ``blhip_problem.backward_init``, and beta * L (:467) as a one-step product.  Announced once per model class on stderr."""
         import sys
-        tm, om = self.transitionModel, self.observationModel
+        tm = self.transitionModel
         tm.study, tm.latticeConstant = self, self.latticeConstant
         key = type(tm).__name__
         if key not in Study._host_transition_announced:
@@ -652,32 +677,19 @@ class Study(object):
         T = len(self.formattedData)
         ts = np.asarray(self.formattedTimestamps, dtype=float)
         dV = float(np.prod(self.latticeConstant))
-        code = device_code(om)
         keep = not evidenceOnly
         full = keep and not forwardOnly
-        if self._posterior_pending is not None:
-            if keep:
-                self._posterior_pending = None
-            else:
-                self._materialize_posterior()
+        self._beforeFit(keep)
         no_value = np.full((1, 1), np.nan)
 
         def step_problem(i, prior, backward_init=None):
             seg = self.formattedData[i]
-            lik = None
-            if code == _abi.OM_TABLE:
-                lik = np.array([np.asarray(om.processedPdf(self.grid, seg), dtype=float) * np.ones(gs)])
-            return FitProblem(obs_model=code, marginal=self.marginalGrid, lattice=self.latticeConstant,
-                              data=np.asarray([seg], dtype=float), timestamps=ts[i:i + 1], prior=prior,
-                              ops=[(_abi.OP_STATIC, 0, -1, 0)], lik=lik, seg_len=om.segmentLength,
-                              carry_slot=Study._HOST_SLOT, backward_init=backward_init)
+            code, lik, _ = self._likelihoodSource([seg], programs=False)      # (looks the model's code up per step: nothing next to the round trip)
+            return self._problem(code, np.asarray([seg], dtype=float), ts[i:i + 1], prior, [(_abi.OP_STATIC, 0, -1, 0)], lik=lik,
+                                 carry_slot=Study._HOST_SLOT, backward_init=backward_init)
 
         def aborted(phase):
-            self._warnZero(phase)
-            self.logEvidence = -np.inf
-            self._posterior_pending = None
-            if keep:
-                self._posteriorSequence = None
+            return self._zeroNormaliser(phase, keep, release=None)      # (the sequence is a host array here: nothing to release)
 
         prior = np.array(self._computePrior(silent=silent), dtype=float).reshape(gs)
         # full fits keep the distribution ENTERING each step (the backward pass multiplies it with the likelihood again on the
@@ -1121,24 +1133,28 @@ class HyperStudy(Study):
             if not silent:
                 print('    + Computed average posterior sequence')
 
-        # hyper-parameter distribution and evidence of the average model (reference core.py:1391-1410)
+        self._averageModel(out['log_evidence'], localList, prior_values, silent)
+        if not evidenceOnly:
+            self.posteriorMeanValues = out['posterior_mean']
+        self._setAllHyperParameters(self.flatHyperParameters)
+        if not silent:
+            print('+ Finished fit.')
+
+    def _averageModel(self, log_evidence, local_list, prior_values, silent):
+        """Hyper-parameter distribution, evidence of the average model and its prior-weighted local evidence from the chains' evidences
+        (reference core.py:1391-1410)."""
         with np.errstate(divide='ignore'):
-            logHPD = np.asarray(out['log_evidence'], dtype=float) + np.log(prior_values) + np.sum(np.log(self.hyperGridConstant))
+            logHPD = np.asarray(log_evidence, dtype=float) + np.log(prior_values) + np.sum(np.log(self.hyperGridConstant))
         scaled = logHPD - np.amax(logHPD)
         self.hyperParameterDistribution = np.exp(scaled)
         self.hyperParameterDistribution /= np.sum(self.hyperParameterDistribution)
         self.hyperParameterDistribution /= np.prod(self.hyperGridConstant)
         self.logEvidence = float(_logsumexp(logHPD))                            # :1405 scipy.special.logsumexp
+        self.localEvidence = np.sum((np.asarray(local_list).T * prior_values).T, axis=0)
+        self.localEvidenceList = []
         if not silent:
             print('    + Computed hyper-parameter distribution')
             print('    + Log10-evidence of average model: {:.5f}'.format(self.logEvidence / np.log(10)))
-        self.localEvidence = np.sum((np.asarray(localList).T * prior_values).T, axis=0)
-        if not evidenceOnly:
-            self.posteriorMeanValues = out['posterior_mean']
-        self.localEvidenceList = []
-        self._setAllHyperParameters(self.flatHyperParameters)
-        if not silent:
-            print('+ Finished fit.')
 
     def _fitHostTransitionHyper(self, forwardOnly, evidenceOnly, silent):
         """A hyper-study over a transition model that is applied on the host (Study._fitHostTransition): one fit per hyper-grid point
@@ -1181,28 +1197,19 @@ class HyperStudy(Study):
             self._posteriorSequence = np.full([T] + list(self.gridSize), np.nan)
             self.posteriorMeanValues = np.full((len(self.gridSize), T), np.nan)
             if n_fold > 0:
-                # (marginal grids and lattice are all accum_finalize reads of the problem: per-step normalisation and the means of the average)
+                # (marginal grids and lattice are all accum_finalize reads of the problem: per-step normalisation and the means of the average;
+                #  the model's code comes from _likelihoodSource over NO segments -- the one reader of device_code -- and its empty table is dropped)
                 self._posteriorSequence = None
-                shell = FitProblem(obs_model=device_code(self.observationModel), marginal=self.marginalGrid, lattice=self.latticeConstant,
-                                   data=np.zeros((T, 1)), timestamps=np.zeros(T), prior=np.ones(int(np.prod(self.gridSize))), ops=[])
+                shell = self._problem(self._likelihoodSource((), programs=False)[0], np.zeros((T, 1)), np.zeros(T),
+                                      np.ones(int(np.prod(self.gridSize))), [])
                 self.posteriorMeanValues = eng.accum_finalize(shell)
                 self._posterior_pending = DevicePosterior(eng, 1, T, list(self.gridSize))
                 if hasattr(eng, 'accum_set_owner'):          # (the per-point fits released the engine's results: the average is this study's)
                     eng.accum_set_owner(self)
                 if not silent:
                     print('    + Computed average posterior sequence')
-        with np.errstate(divide='ignore'):
-            logHPD = np.array(self.logEvidenceList) + np.log(prior_values) + np.sum(np.log(self.hyperGridConstant))
-        scaled = logHPD - np.amax(logHPD)
-        self.hyperParameterDistribution = np.exp(scaled)
-        self.hyperParameterDistribution /= np.sum(self.hyperParameterDistribution)
-        self.hyperParameterDistribution /= np.prod(self.hyperGridConstant)
-        self.logEvidence = float(_logsumexp(logHPD))
-        self.localEvidence = np.sum((np.array(localList).T * prior_values).T, axis=0)
-        self.localEvidenceList = []
+        self._averageModel(self.logEvidenceList, localList, prior_values, silent)
         if not silent:
-            print('    + Computed hyper-parameter distribution')
-            print('    + Log10-evidence of average model: {:.5f}'.format(self.logEvidence / np.log(10)))
             print('+ Finished fit.')
 
     @property
@@ -1469,9 +1476,19 @@ class OnlineStudy(HyperStudy):
         raise NotImplementedError('OnlineStudy object has no "fit" method. Use "step" instead.')
 
     # ---- one data point (reference core.py:2062-2226) -------------------------------------------------------------------
+    def _compileModel(self, tm, hpv, T):
+        """-> (program, ops, op values of all of its chains) of one transition model over T steps.  Every transition of an online study
+        is evaluated at time stamp -1 (the reference evaluates them at len(formattedData) - 1 = -1, core.py:2164-2165; step:
+        ``resume_time=-1.0``), so every time stamp is -1: a ChangePoint whose value lies inside a block's index range restarts nothing, a
+        Deterministic model shifts by the same amount at every step, and the op values never change from call to call."""
+        program = self._expandProgram(tm._program(self.observationModel.parameterNames), T)
+        op_values = self._opValueMatrix(program, np.asarray(hpv, dtype=float) if len(hpv) > 0 else np.zeros((1, 0)),
+                                        timestamps=np.full(T, -1.0), resume_time=-1.0)
+        return program, [(op[0], op[1], op[4], op[5]) for op in program], op_values
+
     def _compileModels(self):
-        """Per transition model: its flat program and the op-aligned hyper-parameter values of all of its chains."""
-        om = self.observationModel
+        """Per transition model: its one-step program with the op-aligned hyper-parameter values of all of its chains, its restart
+        priors, and a carry slot."""
         self._device = []
         for tm, hpv in zip(self.transitionModels, self.hyperParameterValues):
             self.setTransitionModel(tm, silent=True)
@@ -1481,16 +1498,9 @@ class OnlineStudy(HyperStudy):
                 raise ConfigurationError('OnlineStudy: transition model {} defines computeForwardPrior / computeBackwardPrior itself (or '
                                          'contains such a model); user-defined transition models are supported by Study.fit and '
                                          'HyperStudy.fit only.'.format(type(tm).__name__))
-            program = self._expandProgram(tm._program(om.parameterNames), 1)
+            program, ops, op_values = self._compileModel(tm, hpv, 1)
             self._checkManyParameterProgram(program)
-            # every step is a one-step problem resumed at t = -1 (core.py:2164-2165): the op values never change
-            op_values = self._opValueMatrix(program, np.asarray(hpv, dtype=float) if len(hpv) > 0 else np.zeros((1, 0)),
-                                            timestamps=[0.0], resume_time=-1.0)
-            reset = self._changepointPrior() if any(op[0] == _abi.OP_CHANGEPOINT for op in program) else None
-            indep = None
-            if any(op[0] == _abi.OP_INDEPENDENT for op in program):
-                indep = self._changepointPrior() / np.prod(self.latticeConstant)
-            self._device.append(([(op[0], op[1], op[4], op[5]) for op in program], op_values, reset, indep))
+            self._device.append((ops, op_values) + self._restartPriors(program))
             OnlineStudy._slot_counter[0] += 1
             self._slots.append(OnlineStudy._slot_counter[0])
 
@@ -1504,6 +1514,8 @@ class OnlineStudy(HyperStudy):
             self.addTransitionModel('transition model', self.transitionModel)
         point = np.array(dataPoint if isinstance(dataPoint, list) else [dataPoint])
         if len(self.rawData) > 0:
+            # (not through _appendRaw: a call takes ONE time stamp however many entries a list-fed point adds to the raw series,
+            #  reference core.py:2095-2096; a block takes one per point)
             self.rawData = np.append(self.rawData, point, axis=0)
             self.rawTimestamps = np.append(self.rawTimestamps, self.rawTimestamps[-1] + 1)
             return
@@ -1515,6 +1527,83 @@ class OnlineStudy(HyperStudy):
         Study._checkConsistency(self)
         self.rawTimestamps, self.formattedTimestamps = np.array([0]), []
 
+    def _startStream(self):
+        """Before the first data point is filtered: the prior, the prior over the models, an empty evidence book, the models' programs."""
+        nTM = len(self.transitionModels)
+        self._checkGridDims()
+        self._prior = self._computePrior(silent=False)
+        if self.transitionModelPrior is None:
+            self.transitionModelPrior = np.ones(nTM) / nTM
+            if nTM > 1:
+                print('    + Set flat transition model prior.')
+        dV = np.prod(self.latticeConstant)
+        self.logEvidenceList = [np.zeros(tmc) + np.log(dV) for tmc in self.tmCounts]
+        self.hyperLogEvidenceList = np.array([0. for tmc in self.tmCounts])
+        self.hyperParameterDistribution = [np.zeros(tmc) for tmc in self.tmCounts]
+        self.transitionModelDistribution = np.zeros(nTM)
+        self.localTransitionModelDistribution = np.zeros(nTM)
+        self._compileModels()
+
+    # The evidence book (reference core.py:2167-2214) over the T steps of a block, in the order of operations of step's scalar form.
+    def _bookModel(self, i, local):
+        """(chains, T) local evidences of model i -> its (logEvidenceList, hyperLogEvidenceList, hyper-parameter distribution) at every
+        step: (T, C), (T,), (T, C)"""
+        with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+            lni = np.log(np.ascontiguousarray(local.T) / np.prod(self.latticeConstant))                              # core.py:2167
+            LE = np.add.accumulate(np.concatenate((self.logEvidenceList[i][None, :], lni), axis=0), axis=0)[1:]   # :2170, in step order
+            x = LE + np.log(self.hyperPriorValues[i])[None, :]                                                   # :2171
+            m = np.amax(x, axis=1)
+            hle = np.where(np.isfinite(m), m, 0.0)
+            hle = hle + np.log(np.sum(np.exp(x - hle[:, None]), axis=1))                                          # :2178 logsumexp
+            hpd = np.exp(x - m[:, None])                                                                         # :2184-2186
+            hpd /= np.sum(hpd, axis=1)[:, None]
+            if len(self.hyperGridConstants[i]) > 0:
+                hpd /= np.prod(self.hyperGridConstants[i])                                                       # :2187-2188
+        return LE, hle, hpd
+
+    def _bookAcross(self, books):
+        """The bookkeeping across models (:2179-2181, :2199-2214) -> (T, nTM) hyperLogEvidenceList, distribution over the models and
+        local distribution, and the (T,) evidences."""
+        with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+            hle = np.ascontiguousarray(np.array([b[1] for b in books]).T)                                        # (T, nTM)
+            old = np.concatenate((np.asarray(self.hyperLogEvidenceList, dtype=float)[None, :], hle[:-1]), axis=0)
+            ltd = hle - old + np.log(self.transitionModelPrior)[None, :]
+            tmd = np.exp(hle - np.amax(hle, axis=1)[:, None])
+            tmd /= np.sum(tmd, axis=1)[:, None]
+            ltd = np.exp(ltd - np.amax(ltd, axis=1)[:, None])
+            ltd /= np.sum(ltd, axis=1)[:, None]
+            x = hle + np.log(self.transitionModelPrior)[None, :]
+            m = np.amax(x, axis=1)
+            logE = m + np.log(np.sum(np.exp(x - m[:, None]), axis=1))
+        return hle, tmd, ltd, logE
+
+    def _commitBooks(self, books, hle, tmd, ltd, logE):
+        """The last row of the books becomes the study's state."""
+        for i, b in enumerate(books):
+            self.logEvidenceList[i] = b[0][-1].copy()
+            self.hyperParameterDistribution[i] = b[2][-1].copy()
+        self.hyperLogEvidenceList = hle[-1].copy()
+        self.transitionModelDistribution = tmd[-1].copy()
+        self.localTransitionModelDistribution = ltd[-1].copy()
+        self.logEvidence = float(logE[-1])
+
+    def _mixCarried(self, eng):
+        """marginalised posterior = sum_i tmd_i sum_j hpd_ij prod(dh_i) posterior_ij of the carried states, reduced on the device
+        (:2194-2211)"""
+        for i, s in enumerate(self._slots):
+            w = self.hyperParameterDistribution[i] * np.prod(self.hyperGridConstants[i]) * self.transitionModelDistribution[i]
+            eng.carry_mix(s, w, accumulate=i > 0)
+        self.marginalizedPosterior = eng.carry_read(0, -1, self.gridSize)
+
+    def _appendHistory(self, means, posterior, hpds, tmd, ltd):
+        """One step behind the histories (storeHistory): the means and the mixture of that step, the hyper-parameter distribution of
+        every model, the distribution over the models and the local one; copies of all but the means."""
+        self.posteriorMeanValues.append(means)
+        self.posteriorSequence.append(posterior.copy())
+        self.hyperParameterSequence.append([h.copy() for h in hpds])
+        self.transitionModelSequence.append(tmd.copy())
+        self.localTransitionModelSequence.append(ltd.copy())
+
     def step(self, dataPoint):
         """Update every chain with a new data point (float, int, or 1-D array for multi-dimensional data)."""
         self._takeDataPoint(dataPoint)
@@ -1525,59 +1614,38 @@ class OnlineStudy(HyperStudy):
             return
         self.formattedTimestamps.append(self.rawTimestamps[-1])
         eng = _engine_mod.get_engine()
-        nTM = len(self.transitionModels)
-
         if self.firstStep:
-            if not 1 <= len(self.gridSize) <= _abi.MAX_DIM:
-                raise ConfigurationError('The MI355X engine supports observation models with 1 to {} parameters '
-                                         '(got {}).'.format(_abi.MAX_DIM, len(self.gridSize)))
-            self._prior = self._computePrior(silent=False)
-            if self.transitionModelPrior is None:
-                self.transitionModelPrior = np.ones(nTM) / nTM
-                if nTM > 1:
-                    print('    + Set flat transition model prior.')
-            dV = np.prod(self.latticeConstant)
-            self.logEvidenceList = [np.zeros(tmc) + np.log(dV) for tmc in self.tmCounts]
-            self.hyperLogEvidenceList = np.array([0. for tmc in self.tmCounts])
-            self.hyperParameterDistribution = [np.zeros(tmc) for tmc in self.tmCounts]
-            self.transitionModelDistribution = np.zeros(nTM)
-            self.localTransitionModelDistribution = np.zeros(nTM)
-            self._compileModels()
+            self._startStream()
 
-        # the current data segment as a one-step problem; the likelihood is evaluated ONCE for all chains (core.py:2146):
-        # in-kernel for the closed-form device models, on the host through the model's own pdf otherwise
+        # the current data segment as a one-step problem; the likelihood is evaluated ONCE for all chains (core.py:2146)
         segment = self.rawData[-om.segmentLength:]
         data = np.asarray([segment], dtype=float)
-        code = device_code(om)
-        lik = None
-        if code == _abi.OM_TABLE:
-            lik = np.array([np.asarray(om.processedPdf(self.grid, segment), dtype=float) * np.ones(self.gridSize)])
+        code, lik, _ = self._likelihoodSource([segment], programs=False)
         dV = np.prod(self.latticeConstant)
 
+        # The evidence book of ONE step in scalar form: step is called once per data point, and the array form of a block
+        # (_bookModel / _bookAcross) with T = 1 measured 18 us per call slower on 423 (profiles/core_dedup_notes.md).  The two agree bit
+        # for bit (tests/test_online_block_host.py: test_vectorised_bookkeeping_is_bit_identical_for_identical_local_evidences).
         for i, (ops, op_values, reset, indep) in enumerate(self._device):
-            problem = FitProblem(obs_model=code, marginal=self.marginalGrid, lattice=self.latticeConstant, data=data,
-                                 timestamps=np.asarray([self.rawTimestamps[-1]], dtype=float), prior=self._prior, ops=ops,
-                                 reset_prior=reset, indep_prior=indep, lik=lik, seg_len=om.segmentLength,
-                                 resume_time=-1.0,      # the reference evaluates transitions at len(formattedData) - 1 = -1
-                                 carry_slot=self._slots[i])
+            problem = self._problem(code, data, np.asarray([self.rawTimestamps[-1]], dtype=float), self._prior, ops,
+                                    reset_prior=reset, indep_prior=indep, lik=lik, resume_time=-1.0, carry_slot=self._slots[i])
             res = eng.fit(problem, op_values, evidence_only=True, resume=not self.firstStep, carry=True)
-            with np.errstate(divide='ignore', invalid='ignore'):
+            with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
                 ni = res.local_evidence[:, 0] / dV                                               # core.py:2167
                 self.logEvidenceList[i] = self.logEvidenceList[i] + np.log(ni)                   # :2170
-                hpd = self.logEvidenceList[i] + np.log(self.hyperPriorValues[i])                 # :2171
+                x = self.logEvidenceList[i] + np.log(self.hyperPriorValues[i])                   # :2171
                 old = self.hyperLogEvidenceList[i]
-                x = self.logEvidenceList[i] + np.log(self.hyperPriorValues[i])
                 self.hyperLogEvidenceList[i] = _logsumexp(x)                                     # :2178 logsumexp
                 self.transitionModelDistribution[i] = self.hyperLogEvidenceList[i]               # :2179
                 self.localTransitionModelDistribution[i] = self.hyperLogEvidenceList[i] - old + \
                     np.log(self.transitionModelPrior[i])                                         # :2180-2181
-                hpd = np.exp(hpd - np.amax(hpd))                                                 # :2184-2186
+                hpd = np.exp(x - np.amax(x))                                                     # :2184-2186
                 hpd /= np.sum(hpd)
                 if len(self.hyperGridConstants[i]) > 0:
                     hpd /= np.prod(self.hyperGridConstants[i])                                   # :2187-2188
             self.hyperParameterDistribution[i] = hpd
 
-        with np.errstate(divide='ignore', invalid='ignore'):
+        with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
             tmd = self.transitionModelDistribution
             tmd = np.exp(tmd - np.amax(tmd)); tmd /= np.sum(tmd)                                 # :2199-2201
             self.transitionModelDistribution = tmd
@@ -1588,18 +1656,10 @@ class OnlineStudy(HyperStudy):
             m = np.amax(x)
             self.logEvidence = float(m + np.log(np.sum(np.exp(x - m))))                          # :2214
 
-        # marginalised posterior = sum_i tmd_i sum_j hpd_ij prod(dh_i) posterior_ij, reduced on the device (:2194-2211)
-        for i in range(nTM):
-            w = self.hyperParameterDistribution[i] * np.prod(self.hyperGridConstants[i]) * self.transitionModelDistribution[i]
-            eng.carry_mix(self._slots[i], w, accumulate=i > 0)
-        self.marginalizedPosterior = eng.carry_read(0, -1, self.gridSize)
-
+        self._mixCarried(eng)
         if self.storeHistory:
-            self.posteriorMeanValues.append(np.array([np.sum(self.marginalizedPosterior * g) for g in self.grid]))
-            self.posteriorSequence.append(self.marginalizedPosterior.copy())
-            self.hyperParameterSequence.append([h.copy() for h in self.hyperParameterDistribution])
-            self.transitionModelSequence.append(self.transitionModelDistribution.copy())
-            self.localTransitionModelSequence.append(self.localTransitionModelDistribution.copy())
+            self._appendHistory(np.array([np.sum(self.marginalizedPosterior * g) for g in self.grid]), self.marginalizedPosterior,
+                                self.hyperParameterDistribution, tmd, ltd)
         if self.firstStep:
             self.firstStep = False
 
@@ -1660,21 +1720,7 @@ class OnlineStudy(HyperStudy):
         nTM = len(self.transitionModels)
 
         if self.firstStep:
-            if not 1 <= len(self.gridSize) <= _abi.MAX_DIM:
-                raise ConfigurationError('The MI355X engine supports observation models with 1 to {} parameters '
-                                         '(got {}).'.format(_abi.MAX_DIM, len(self.gridSize)))
-            self._prior = self._computePrior(silent=False)
-            if self.transitionModelPrior is None:
-                self.transitionModelPrior = np.ones(nTM) / nTM
-                if nTM > 1:
-                    print('    + Set flat transition model prior.')
-            dV = np.prod(self.latticeConstant)
-            self.logEvidenceList = [np.zeros(tmc) + np.log(dV) for tmc in self.tmCounts]
-            self.hyperLogEvidenceList = np.array([0. for tmc in self.tmCounts])
-            self.hyperParameterDistribution = [np.zeros(tmc) for tmc in self.tmCounts]
-            self.transitionModelDistribution = np.zeros(nTM)
-            self.localTransitionModelDistribution = np.zeros(nTM)
-            self._compileModels()
+            self._startStream()
 
         # time chunks: the kept sequence of the widest model + the history planes within the memory budget
         planes = 0 if not self.storeHistory else (1 if nTM == 1 else 1 + nTM)
@@ -1717,121 +1763,53 @@ class OnlineStudy(HyperStudy):
             self.rawTimestamps = np.append(self.rawTimestamps, self.rawTimestamps[-1] + 1 + np.arange(len(pts)))
 
     def _compileBlock(self, T):
-        """Per transition model: (ops, op values) of a T-step block.  Every transition of an online study is evaluated at time stamp -1
-        (step: ``resume_time=-1.0``), so every time stamp of the block is -1 too: a ChangePoint whose value lies inside the block's index
-        range restarts nothing, a Deterministic model shifts by the same amount at every step."""
-        om = self.observationModel
+        """Per transition model: (ops, op values) of a T-step block (see :meth:`_compileModel`)."""
         out = []
         for tm, hpv in zip(self.transitionModels, self.hyperParameterValues):
             self.setTransitionModel(tm, silent=True)
-            program = self._expandProgram(tm._program(om.parameterNames), T)
-            op_values = self._opValueMatrix(program, np.asarray(hpv, dtype=float) if len(hpv) > 0 else np.zeros((1, 0)),
-                                            timestamps=np.full(T, -1.0), resume_time=-1.0)
-            out.append(([(op[0], op[1], op[4], op[5]) for op in program], op_values))
+            out.append(self._compileModel(tm, hpv, T)[1:])
         return out
 
     def _stepChunk(self, eng, programs, segments, planes, last):
-        """One time chunk of a block: the fits, the evidence bookkeeping of step (reference core.py:2167-2214) vectorised over the chunk's
-        steps in the loop's order of operations, the mixtures.  -> False (and nothing of the study touched but the carried states) when a
-        chain met a zero normaliser."""
-        om = self.observationModel
+        """One time chunk of a block: the fits, the evidence book over the chunk's steps, the mixtures.  -> False (and nothing of the
+        study touched but the carried states) when a chain met a zero normaliser."""
         T = len(segments)
         nTM = len(self.transitionModels)
         data = np.asarray(segments, dtype=float)
-        # the likelihood as Study.fit builds it: in-kernel models, device-built tables, likelihood programs; a host table otherwise
-        code = device_code(om)
-        lik = lik_program = None
-        prog = self._likelihoodProgram(om) if code == _abi.OM_TABLE else None
-        if prog is not None:
-            code = _abi.OM_PROGRAM
-            lp_ops, lp_consts = prog.bind(self.marginalGrid)
-            lik_program = (lp_ops, lp_consts, prog.step_values(data.reshape(len(data), -1)))
-        elif code == _abi.OM_TABLE:
-            lik = np.array([np.asarray(om.processedPdf(self.grid, seg), dtype=float) * np.ones(self.gridSize) for seg in segments])
-        dV = np.prod(self.latticeConstant)
+        code, lik, lik_program = self._likelihoodSource(segments, programs=True)        # (the likelihood as Study.fit builds it)
         history = self.storeHistory
         stamps = np.full(T, -1.0)
-
-        def fit(i):
-            ops, op_values = programs[i]
-            _, _, reset, indep = self._device[i]
-            problem = FitProblem(obs_model=code, marginal=self.marginalGrid, lattice=self.latticeConstant, data=data, timestamps=stamps,
-                                 prior=self._prior, ops=ops, reset_prior=reset, indep_prior=indep, lik=lik, lik_program=lik_program,
-                                 seg_len=om.segmentLength, resume_time=-1.0, carry_slot=self._slots[i])
-            res = eng.fit(problem, op_values, evidence_only=not history, forward_only=history, keep_posterior=history,
-                          resume=not self.firstStep, carry=True)
-            return None if np.any(res.abort_step >= 0) else res
-
-        def book(i, local):
-            """-> (logEvidenceList, hyperLogEvidenceList, hyper-parameter distributions) of model i at every step: (T, C), (T,), (T, C)"""
-            with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
-                lni = np.log(np.ascontiguousarray(local.T) / dV)                                                      # core.py:2167
-                LE = np.add.accumulate(np.concatenate((self.logEvidenceList[i][None, :], lni), axis=0), axis=0)[1:]   # :2170, in step order
-                x = LE + np.log(self.hyperPriorValues[i])[None, :]                                                   # :2171
-                m = np.amax(x, axis=1)
-                hle = np.where(np.isfinite(m), m, 0.0)
-                hle = hle + np.log(np.sum(np.exp(x - hle[:, None]), axis=1))                                          # :2178 logsumexp
-                hpd = np.exp(x - m[:, None])                                                                         # :2184-2186
-                hpd /= np.sum(hpd, axis=1)[:, None]
-                if len(self.hyperGridConstants[i]) > 0:
-                    hpd /= np.prod(self.hyperGridConstants[i])                                                       # :2187-2188
-            return LE, hle, hpd
-
-        def finish(books):
-            """The bookkeeping across models (:2179-2181, :2199-2214) -> (T, nTM) distributions and the (T,) evidences."""
-            with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
-                hle = np.ascontiguousarray(np.array([b[1] for b in books]).T)                                        # (T, nTM)
-                old = np.concatenate((np.asarray(self.hyperLogEvidenceList, dtype=float)[None, :], hle[:-1]), axis=0)
-                ltd = hle - old + np.log(self.transitionModelPrior)[None, :]
-                tmd = np.exp(hle - np.amax(hle, axis=1)[:, None])
-                tmd /= np.sum(tmd, axis=1)[:, None]
-                ltd = np.exp(ltd - np.amax(ltd, axis=1)[:, None])
-                ltd /= np.sum(ltd, axis=1)[:, None]
-                x = hle + np.log(self.transitionModelPrior)[None, :]
-                m = np.amax(x, axis=1)
-                logE = m + np.log(np.sum(np.exp(x - m[:, None]), axis=1))
-            return hle, tmd, ltd, logE
-
         scale = [np.prod(self.hyperGridConstants[i]) for i in range(nTM)]
         books = []
         for i in range(nTM):
-            res = fit(i)
-            if res is None:
+            ops, op_values = programs[i]
+            _, _, reset, indep = self._device[i]
+            problem = self._problem(code, data, stamps, self._prior, ops, reset_prior=reset, indep_prior=indep, lik=lik,
+                                    lik_program=lik_program, resume_time=-1.0, carry_slot=self._slots[i])
+            res = eng.fit(problem, op_values, evidence_only=not history, forward_only=history, keep_posterior=history,
+                          resume=not self.firstStep, carry=True)
+            if np.any(res.abort_step >= 0):
                 return False
-            books.append(book(i, res.local_evidence))
+            books.append(self._bookModel(i, res.local_evidence))
             if history and nTM > 1:
                 # the next model's fit overwrites the kept sequence, and the distribution over models needs every model's evidence: one
                 # history plane per model, weighted with the model's own hyper-parameter distribution (known now) ...
                 eng.mix_sequence(books[i][2] * scale[i], plane=1 + i, n_planes=1 + nTM)
-        hle, tmd, ltd, logE = finish(books)
+        hle, tmd, ltd, logE = self._bookAcross(books)
         if history and nTM > 1:
             eng.mix_sequence(tmd, plane=0, n_planes=1 + nTM, source=1)          # ... and the planes mixed with the distribution over models
         elif history:
             eng.mix_sequence(books[0][2] * scale[0] * tmd[:, [0]])              # (one model: its probability is 1, or NaN where the loop's is)
-
-        for i in range(nTM):
-            self.logEvidenceList[i] = books[i][0][-1].copy()
-            self.hyperParameterDistribution[i] = books[i][2][-1].copy()
-        self.hyperLogEvidenceList = hle[-1].copy()
-        self.transitionModelDistribution = tmd[-1].copy()
-        self.localTransitionModelDistribution = ltd[-1].copy()
-        self.logEvidence = float(logE[-1])
+        self._commitBooks(books, hle, tmd, ltd, logE)
 
         if history:
             seq = eng.mix_read(T, self.gridSize)
             means = eng.mix_means(self.marginalGrid, T)
             self.marginalizedPosterior = seq[-1].copy()
             for k in range(T):
-                self.posteriorMeanValues.append(means[k].copy())
-                self.posteriorSequence.append(seq[k].copy())
-                self.hyperParameterSequence.append([b[2][k].copy() for b in books])
-                self.transitionModelSequence.append(tmd[k].copy())
-                self.localTransitionModelSequence.append(ltd[k].copy())
+                self._appendHistory(means[k].copy(), seq[k], [b[2][k] for b in books], tmd[k], ltd[k])
         elif last:
-            for i in range(nTM):
-                w = self.hyperParameterDistribution[i] * scale[i] * self.transitionModelDistribution[i]
-                eng.carry_mix(self._slots[i], w, accumulate=i > 0)
-            self.marginalizedPosterior = eng.carry_read(0, -1, self.gridSize)
+            self._mixCarried(eng)
         return True
 
     # ---- device-resident per-chain results, fetched on demand -----------------------------------------------------------
