@@ -243,9 +243,10 @@ void finish_batch(BatchRun &R, int64_t usedK, bool folded_before, int64_t nbatch
     const ChainRun &CR = R.CR;
     const int64_t T = E.T, B = E.B;
     const long long G = E.G;
-    const bool chain_ran = CR.on && !R.resident_failed;
+    // (what ran, not what was planned: a declined or repeated batch left row-major posteriors -- chain_fold_source, blhip_chain_plan.hpp)
+    const ChainFoldSource src = chain_fold_source(CR.on, R.resident_failed, CR.post_private, CR.cp.pad, CR.ax1, CR.depad, g.n0);
     double *d_post = E.d_post;
-    if (chain_ran && CR.depad) {                 // (E.d_post was the kernels' scratch sequence on the padded geometry)
+    if (src.through_depad) {                     // (E.d_post was the kernels' scratch sequence on the padded geometry)
         d_post = ctx->post.as<double>();
         for_grid_y(ctx, (long long)B * T, [&](long long y0, unsigned ny) {
             BL_LAUNCH(depad_kernel, dim3((unsigned)((G + NTHREADS - 1) / NTHREADS), ny), dim3(NTHREADS), 0, E.st, d_post,
@@ -263,10 +264,10 @@ void finish_batch(BatchRun &R, int64_t usedK, bool folded_before, int64_t nbatch
         // (the backward kernel folded this batch, or it was folded before)
     } else if (E.ff.accumulate) {
         FoldJob lay;
-        const bool padded = chain_ran && (CR.cp.pad || CR.ax1) && !CR.depad;
+        const bool padded = src.layout == FOLD_PADDED;
         if (padded) { lay.pad_n0p = CR.cp.n0p; lay.pad_n0 = g.n0; lay.pad_n1 = g.n1; lay.pad_step = CR.Gk; lay.pad_ax = CR.ax1 ? 1 : 0; }
         // (many small batches: nobody waits for a batch's fold; the last one is waited for with the stream below)
-        fold_accumulate(ctx, T, G, B, R.O, E.log_w + E.c0, d_post, E.M->w, E.M->invN, (CR.post_private && !R.resident_failed && !padded) ? g.n0 : 0, padded ? &lay : nullptr,
+        fold_accumulate(ctx, T, G, B, R.O, E.log_w + E.c0, d_post, E.M->w, E.M->invN, src.sm_n0, padded ? &lay : nullptr,
                         (nbatch >= 4 && !E.ff.keep && !E.ff.carry) ? E.fold_ev : nullptr);
     }
     if (E.ff.keep) {

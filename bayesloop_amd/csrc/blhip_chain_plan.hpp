@@ -1,6 +1,7 @@
 // The route of a batch through the chain-resident kernels of two-parameter grids (blhip_chainres.hpp, blhip_chainax.hpp, blhip_chainclamp.hpp):
 // everything ChainRun (blhip_fit_paths.hpp) decides that needs no HIP call -- which kernels run, on which geometry, in which rounds, whether
-// the backward pass folds, what a padded batch does, which steps change-point chains share, and what a launch moves and computes.  Pure
+// the backward pass folds, what a padded batch does, which steps change-point chains share, which layout the separate fold reads afterwards,
+// and what a launch moves and computes.  Pure
 // functions of plain facts (ChainFacts), the options (ChainOptions) and the batch's transition program, one per stage, because
 // plan_chainres and the memory admissions of the device side sit between them; tests/host/chain_plan_main.cpp builds a stand-alone program
 // around this header (tests/test_chain_plan_host.py).
@@ -326,6 +327,31 @@ inline ChainPrefix chain_prefix_plan(const ChainFacts &F, const ChainOptions &O,
         if (b != P.prov) { P.tsh[b] = std::min(P.tfirst[b], P.tfirst[P.prov]); P.saved += P.tsh[b]; }
     if (P.saved > 0) { P.share = may_share || may_skip; P.skip = may_skip; }
     return P;
+}
+
+// ---- behind the passes: where the batch's posteriors are and in which layout the separate fold reads them (finish_batch, blhip.hip) ----------
+// Only the chain kernels store anything but [t][row][column]: a batch that was planned and then declined (`on` is false; post_private,
+// pad and depad describe the plan, not what ran) and a batch the launch-per-step kernels repeated after a failed check
+// (`resident_failed`) left their posteriors row-major in blhip_ctx::post.
+enum ChainFoldLayout {
+    FOLD_ROW_MAJOR = 0,                            // [t][row][column]: accumulate_kernel / accumulate2_kernel / accumulate_small_kernel
+    FOLD_STRIP_MAJOR = 1,                          // [t][column / 16][row][16] on the exact geometry: accumulate2_kernel with sm_n0 = the grid's rows
+    FOLD_PADDED = 2,                               // ... on the padded geometry, or the both-axes kernels' alternating layouts: accumulate_pad_kernel
+};
+struct ChainFoldSource {
+    int layout = FOLD_ROW_MAJOR;
+    int sm_n0 = 0;                                 // FOLD_STRIP_MAJOR: rows per strip (FoldJob::sm_n0); 0 otherwise
+    bool through_depad = false;                    // the posteriors reach blhip_ctx::post through depad_kernel (row-major there); false: the passes wrote the buffer themselves
+};
+
+inline ChainFoldSource chain_fold_source(bool on, bool resident_failed, bool post_private, bool pad, bool ax1, bool depad, int n0) {
+    ChainFoldSource s;
+    if (!on || resident_failed) return s;
+    s.through_depad = depad;
+    if (depad) return s;
+    if (pad || ax1) s.layout = FOLD_PADDED;
+    else if (post_private) { s.layout = FOLD_STRIP_MAJOR; s.sm_n0 = n0; }
+    return s;
 }
 
 // ---- what a launch moves and computes BY CONSTRUCTION (blhip_timing: fwd / bwd _hbm_bytes, _flops) -----------------------------------------

@@ -14,7 +14,10 @@
 //   admits=need,fraction,free,own              -> "admits 0 / 1" (chain_admits alone)
 //   launch=nslots,Gk,T,bwd,fold,two,ax1,tab,evidence_only,nk,share,skip[,tshare of every chain of the launch]   -> "cost bytes flops cells"
 //                          (chain_launch_cost alone, with epilogue and band flop of 1 and 0)
-// Prints "constants", "admit", then "plan refused" or the plan, "route", and where the path is on "fold" and "prefix" (see the code).
+//   source=on,resident_failed,post_private,pad,ax1,depad,n0   -> "source layout sm_n0 through_depad" (chain_fold_source alone; layout 0 row-major,
+//                          1 strip-major, 2 padded)
+// Prints "constants", "admit", then "plan refused" or the plan, "route", and where the path is on "fold", "fold_source" (the layout the
+// separate fold reads after each of the three outcomes of the planned batch) and "prefix" (see the code).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -137,6 +140,15 @@ int run_launch(const std::string &v) {
     std::printf("cost %.17g %.17g\n", c.bytes, c.flops);
     return 0;
 }
+
+int run_source(const std::string &v) {
+    const std::vector<std::string> a = split(v, ',');
+    if (a.size() != 7) return 2;
+    auto I = [&](size_t k) { return std::atoi(a[k].c_str()); };
+    const ChainFoldSource s = chain_fold_source(I(0) != 0, I(1) != 0, I(2) != 0, I(3) != 0, I(4) != 0, I(5) != 0, I(6));
+    std::printf("source %d %d %d\n", s.layout, s.sm_n0, s.through_depad ? 1 : 0);
+    return 0;
+}
 }   // namespace
 
 int main(int argc, char **argv) {
@@ -158,6 +170,7 @@ int main(int argc, char **argv) {
         else if (key == "om") om = val;
         else if (key == "admits") { if (int e = run_admits(val)) return e; }
         else if (key == "launch") { if (int e = run_launch(val)) return e; }
+        else if (key == "source") { if (int e = run_source(val)) return e; }
         else if (kv.count(key)) kv[key] = std::strtod(val.c_str(), nullptr);
         else { std::fprintf(stderr, "unknown key %s\n", key.c_str()); return 2; }
     }
@@ -210,6 +223,15 @@ int main(int argc, char **argv) {
     if (needs) keep = depad = chain_padding_rule(F, O, cp, on("admitted"), f);
     keep = keep && chain_fold_settle(F, cp, tab, ax1, f);
     std::printf("fold keep %d needs_depad %d depad %d post_private %d fused %d fold2 %d slots_used %d\n", keep, needs, depad, f.post_private, f.fused, f.fold2, f.slots_used);
+    // what finish_batch folds from, with the members as ChainRun holds them behind setup (on = keep; a decline clears none of the others):
+    // the chain kernels ran | the batch was declined | they failed a check and the launch-per-step kernels repeated the batch
+    std::printf("fold_source");
+    const char *outcome[3] = {"ran", "declined", "failed"};
+    for (int k = 0; k < 3; ++k) {
+        const ChainFoldSource s = chain_fold_source(k == 1 ? false : keep, k == 2, f.post_private, cp.pad, ax1, depad, g.n0);
+        std::printf(" %s_layout %d %s_n0 %d %s_depad %d", outcome[k], s.layout, outcome[k], s.sm_n0, outcome[k], s.through_depad ? 1 : 0);
+    }
+    std::printf("\n");
     row("round_start_b", f.round_start_b); row("round_nk_b", f.round_nk_b);
     if (!keep) return 0;
     const ChainPrefix P = chain_prefix_plan(F, O, prog, cp, ax1, f.fused);

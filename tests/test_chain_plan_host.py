@@ -16,16 +16,21 @@ and prints every stage; the expectations below are written out by hand from the 
   step t restarts exactly when forward step t + 1 does); without that kernel the Gaussian model folds in the kernel on 1024 rows only, the
   table on exact grids only;
 * a padded batch whose sequence is not private copies it out afterwards (depad) if memory admits and, for a full fit, on <= 512 rows;
-* prefix: without a stencil, the chain with the latest first restart provides the steps before the others' first restarts.
+* prefix: without a stencil, the chain with the latest first restart provides the steps before the others' first restarts;
+* the layout the separate fold reads (chain_fold_source): strip-major or padded only when the chain kernels ran; a batch that was planned and
+  then declined, or repeated on the launch-per-step kernels, reads row-major (tests/DECLINED_BATCHES.md; the studies: test_declined_batches.py).
 
 Built plain and with -fsanitize=address,undefined (host code only; the program has its own main).
 """
+import itertools
 import os
 import re
 import shutil
 import subprocess
 
 import pytest
+
+import declined_cases as dc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, 'tests', 'host', 'chain_plan_main.cpp')
@@ -40,7 +45,8 @@ def _hipcc():
 
 
 def _args(chains=(), **kw):
-    return ['chain=%s' % c for c in chains] + ['%s=%s' % (k, v) for k, v in kw.items()]
+    """(a list as value: the key once per element)"""
+    return ['chain=%s' % c for c in chains] + ['%s=%s' % (k, x) for k, v in kw.items() for x in (v if isinstance(v, list) else [v])]
 
 
 def _parse(out):
@@ -50,8 +56,10 @@ def _parse(out):
         w = line.split()
         if w[0] == 'plan' and w[1] == 'refused':
             r['plan'] = None
-        elif w[0] in ('admit', 'plan', 'route', 'fold_plan', 'fold', 'prefix'):
+        elif w[0] in ('admit', 'plan', 'route', 'fold_plan', 'fold', 'fold_source', 'prefix'):
             r[w[0]] = dict(zip(w[1::2], map(int, w[2::2])))
+        elif w[0] == 'source':
+            r.setdefault('source', []).append(tuple(int(x) for x in w[1:]))
         elif w[0] == 'cost':
             r.setdefault('cost', []).append((float(w[1]), float(w[2])))
         elif w[0] == 'admits':
@@ -305,6 +313,96 @@ def test_traffic_model(plan):
     assert _launch(plan, 3, bwd=1, share=1, skip=1, tsh=tsh, nk=4) == (cells * 16.0, cells)      # a storing backward pass shares nothing
 
 
+ROW_MAJOR, STRIP_MAJOR, PADDED = dc.ROW_MAJOR, dc.STRIP_MAJOR, dc.PADDED
+ROW_FROM_POST = (ROW_MAJOR, 0, 0)                  # (layout, sm_n0, through depad_kernel): row-major, written into blhip_ctx::post by the passes themselves
+
+
+def test_fold_source_over_the_whole_product(plan):
+    """chain_fold_source, the layout finish_batch hands the separate fold: strip-major or padded ONLY when the chain kernels ran -- a
+    declined batch (on = 0, whatever the plan left in the other members: the late declines of chain_fold_settle and chain_padding_rule, and
+    the memory admissions of both_axes_buffers, anchor_table and the de-padding copy, which no test can force on the card) and a batch the
+    launch-per-step kernels repeated read row-major from blhip_ctx::post."""
+    combos = list(itertools.product((0, 1), (0, 1), (0, 1), (0, 1), (0, 1), (0, 1), (100, 128, 520, 601, 1024)))
+    got = plan(source=[','.join(map(str, c)) for c in combos])['source']
+    assert len(got) == len(combos) == 320
+    seen = set()
+    for (on, failed, post_private, pad, ax1, depad, n0), s in zip(combos, got):
+        what = dict(on=on, failed=failed, post_private=post_private, pad=pad, ax1=ax1, depad=depad, n0=n0)
+        if not on or failed:
+            assert s == ROW_FROM_POST, what
+            continue
+        # the chain kernels ran: a de-padded sequence is row-major; else the padded geometry or the both-axes layouts; else the exact
+        # geometry, strip-major where the sequence is private to the fit (rows per strip: the grid's), row-major where it is handed out
+        want = (ROW_MAJOR, 0, 1) if depad else (PADDED, 0, 0) if (pad or ax1) else (STRIP_MAJOR, n0, 0) if post_private else ROW_FROM_POST
+        assert s == want, what
+        seen.add(s[0])
+    assert seen == {ROW_MAJOR, STRIP_MAJOR, PADDED}
+    assert all(s[1] == 0 for s in got if s[0] != STRIP_MAJOR) and all(s[1] > 0 for s in got if s[0] == STRIP_MAJOR)
+
+
+def _outcome(r, which):
+    s = r['fold_source']
+    return (s[which + '_layout'], s[which + '_n0'], s[which + '_depad'])
+
+
+def test_fold_source_of_the_three_outcomes_of_a_planned_batch(plan):
+    W = ['3', '2', '1']
+    # stored strip-major on an exact geometry and folded separately; repeated or declined: row-major
+    r = plan(W, fuse_accumulate=0, **HYPER)
+    assert (_outcome(r, 'ran'), _outcome(r, 'declined'), _outcome(r, 'failed')) == ((STRIP_MAJOR, 128, 0), ROW_FROM_POST, ROW_FROM_POST)
+    r = plan(W, n0=1024, n1=32, fuse_accumulate=0, **HYPER)
+    assert (_outcome(r, 'ran'), _outcome(r, 'declined'), _outcome(r, 'failed')) == ((STRIP_MAJOR, 1024, 0), ROW_FROM_POST, ROW_FROM_POST)
+    # a table on a padded grid: stored on the padded geometry
+    r = plan(W, om='table', n0=100, n1=20, **HYPER)
+    assert (_outcome(r, 'ran'), _outcome(r, 'declined'), _outcome(r, 'failed')) == ((PADDED, 0, 0), ROW_FROM_POST, ROW_FROM_POST)
+    # a kept fit of a padded grid: through depad_kernel; of an exact one: row-major as stored
+    r = plan(W, n0=100, n1=20, accumulate=1, keep=1)
+    assert (_outcome(r, 'ran'), _outcome(r, 'declined'), _outcome(r, 'failed')) == ((ROW_MAJOR, 0, 1), ROW_FROM_POST, ROW_FROM_POST)
+    assert _outcome(plan(W, accumulate=1, keep=1), 'ran') == ROW_FROM_POST
+    # both axes, private: the alternating layouts
+    assert _outcome(plan(['3:2', '2:2'], n0=128, n1=128, fuse_accumulate=0, **HYPER), 'ran') == (PADDED, 0, 0)
+
+
+# a full change-point study, a walk with a change point inside, walks without the fused fold: ordinary studies on 513 .. 1023 rows (or 1024
+# rows and ragged columns) that the route plans (on = 1) and chain_fold_settle declines with post_private left set
+LATE_DECLINES = [(['0:0:3', '0:0:5'], dict(n0=600, n1=32)),
+                 (['0:0:3', '0:0:5'], dict(n0=1024, n1=20)),
+                 (['3:0:3', '3:0:5'], dict(n0=600, n1=32)),
+                 (['3'], dict(n0=600, n1=32, fuse_accumulate=0))]
+
+
+@pytest.mark.parametrize('chains,kw', LATE_DECLINES)
+def test_a_late_decline_folds_row_major(plan, chains, kw):
+    r = plan(chains, **HYPER, **kw)
+    assert r['plan']['n0p'] == 1024 and r['plan']['pad'] == 1 and r['plan']['ntw'] == 8 and r['route']['on'] == 1
+    assert _fold(r) == dict(keep=0, post_private=1, fused=0, fold2=0)
+    for which in ('ran', 'declined', 'failed'):               # (on = keep = 0 in every one)
+        assert _outcome(r, which) == ROW_FROM_POST, which
+    assert 'prefix' not in r
+
+
+@pytest.mark.parametrize('name', list(dc.DECLINED))
+def test_the_planner_declines_the_cases_of_test_declined_batches(plan, name):
+    """the same facts as the GPU case (tests/declined_cases.py): planned, on the route, then keep 0"""
+    d = dc.DECLINED[name]
+    r = plan(d['chains'], **d['facts'])
+    assert r['admit']['plan'] == 1 and r['plan'] is not None and r['plan']['pad'] == 1 and r['route'] == dict(
+        on=1, clamp=0, n0p=r['plan']['n0p'], ntw=r['plan']['ntw'], pad=1), r
+    assert r['fold']['keep'] == 0 and r['fold']['post_private'] == d['post_private'] and r['fold']['depad'] == 0, r['fold']
+    assert r['fold']['needs_depad'] == (0 if d['post_private'] else 1)
+    assert _outcome(r, 'declined') == ROW_FROM_POST
+    # with nothing declined the same plan would be a strip-major layout on the padded geometry: what the launch-per-step kernels never write
+    assert plan(source='1,0,%d,1,0,0,%d' % (d['post_private'], d['grid'][0]))['source'] == [(PADDED, 0, 0)]
+
+
+def test_the_planner_keeps_the_strip_major_case_of_test_declined_batches(plan):
+    for name, d in dc.C_CASES.items():
+        r = plan(d['chains'], **d['facts'])
+        assert r['plan']['pad'] == 0 and r['plan']['strips'] == 2 and r['route']['on'] == 1, name
+        assert _fold(r) == dict(keep=1, post_private=1, fused=0, fold2=0), name
+        assert _outcome(r, 'ran') == (STRIP_MAJOR, d['grid'][0], 0) and _outcome(r, 'failed') == ROW_FROM_POST, name
+
+
 def test_host_functions_under_the_sanitizers(tmp_path):
     """the same program with AddressSanitizer and UBSan on the host side, as a stand-alone executable"""
     exe = str(tmp_path / 'chain_plan_san')
@@ -319,9 +417,12 @@ def test_host_functions_under_the_sanitizers(tmp_path):
             _args(['0:0:3', '0:0:5:5'], T=8, full=0, evidence_only=1),
             _args(['3:0:4', '3'], n0=600, **HYPER),
             _args(['3'], n0=20),
-            _args(admits='1,0.5,1,1', launch='3,2048,8,1,1,1,0,0,0,4,1,1,3,0,2')]
+            _args(admits='1,0.5,1,1', launch='3,2048,8,1,1,1,0,0,0,4,1,1,3,0,2'),
+            _args(['0:0:3', '0:0:5'], n0=600, n1=32, **HYPER),
+            _args(['3', '2'], n0=1024, n1=32, fuse_accumulate=0, **HYPER),
+            _args(source=['1,0,1,0,0,0,128', '0,0,1,1,0,0,600', '1,1,0,1,1,1,100'])]
     for a in runs:
         r = subprocess.run([exe] + a, capture_output=True, text=True, timeout=300, env=env)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-        assert r.stdout.splitlines()[-1].startswith(('tsh', 'route ', 'cost ', 'round_nk_b'))
+        assert r.stdout.splitlines()[-1].startswith(('tsh', 'route ', 'cost ', 'round_nk_b', 'source '))
         assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr

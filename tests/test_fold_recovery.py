@@ -71,6 +71,9 @@ FLAVOURS = {
     # the single-chain fold (1024 rows: the two-chain kernel stops at 512; the wide walk: radius 115 > 80)
     'single_chain': dict(wide=_hyper(1024, 16, 94, 6, _values(0.01, 0.15, wide=0.45)), plain=_hyper(1024, 16, 94, 6, _values(0.01, 0.15)),
                          off=dict(fuse_accumulate=0), opts=dict(fold2=0)),
+    # ... on two strips (one strip of 16 columns stores strip-major exactly as row-major: a repeated batch's layout cannot go wrong there)
+    'single_chain_2strips': dict(wide=_hyper(1024, 32, 98, 6, _values(0.01, 0.15, wide=0.45)), plain=_hyper(1024, 32, 98, 6, _values(0.01, 0.15)),
+                                 off=dict(fuse_accumulate=0), opts=dict(fold2=0)),
     # change points: the two-chain fold with its restart rule
     'changepoint': dict(wide=None, plain=dict(study='ChangepointStudy', data=('series_jump', 96, 52, 26, 0.0), om=_g2(256, 32),
                                               tm=('ChangePoint', 'tChange', [int(x) for x in np.arange(2, 50)], None)),
@@ -182,7 +185,7 @@ def test_every_fused_fold_flavour_carries_its_slots_through_the_call(flavour):
 
 
 @pytest.mark.parametrize('poison_kind', ['fold', 'stage2', 'stage3'])
-@pytest.mark.parametrize('flavour', ['two_chain', 'single_chain', 'both_axes'])
+@pytest.mark.parametrize('flavour', ['two_chain', 'single_chain', 'single_chain_2strips', 'both_axes'])
 def test_wide_batch_between_fused_batches_is_folded_once(flavour, poison_kind):
     """fused, direct (a wide walk), fused -- the last batch poisons the slots that carry the first: the repeat re-runs batches 0 .. 2,
     the direct batch 1 must not reach the accumulator a second time."""
