@@ -67,6 +67,7 @@ namespace {
 #include "blhip_fit_paths.hpp"    // BatchEnv, ResidentRun, ChainRun: the resident paths of a batch
 #include "blhip_fit_row1d.hpp"    // Row1dRun: the 1-D paths of a batch
 #include "blhip_fit_step.hpp"     // StepRun: the launch-per-step path of a batch
+#include "blhip_batch_sched.hpp"  // BatchPath, PassPlan, the tail's decisions, BatchSchedule, ResidentRetry: do_fit's batch loop (no HIP call; blhip_host.hpp has read it already)
 
 // one batch of a fit: the paths it may run on, and what its passes and its tail share
 struct BatchRun {
@@ -80,6 +81,7 @@ struct BatchRun {
     double dV = 1.0;
     bool resident_failed = false;                // a resident pass gave up or failed a check: the launch-per-step kernels take over
     double *redF = nullptr, *redB = nullptr;     // reduced sums on the host (page-locked staging of the context)
+    BatchPath path() const { return batch_path(RR.on, CR.on, R1.on, resident_failed); }      // of the next attempt / of the one that went through
 };
 
 // The end of a pass: the partial sums of its `nblk` slots are added up, and the sums travel to the page-locked buffer -- on the main
@@ -111,42 +113,121 @@ void reset_pass_timing(blhip_ctx *ctx) {
     ctx->timing.forward_launches = ctx->timing.backward_launches = 0;
 }
 
+// the launches of one pass of an attempt on its path
+void launch_pass(BatchRun &R, BatchPath path, bool bwd, int64_t K, double *d_ps) {
+    const BatchEnv &E = R.E;
+    switch (path) {
+    case PATH_RESIDENT: R.RR.launch(E, bwd, d_ps); break;
+    case PATH_CHAIN:
+        if (bwd && R.CR.fused) { R.CR.prepare_fold(E, R.O); E.mark("  prepare_fold"); }
+        R.CR.pass(E, bwd, d_ps);
+        break;
+    case PATH_ROW1D: if (bwd) R.R1.backward(E, K, d_ps); else R.R1.forward(E, K, d_ps); break;
+    case PATH_STEP: if (bwd) R.SR.backward(E, d_ps); else R.SR.forward(E, d_ps); break;
+    }
+}
+
+// The path's own check of a pass from its reduced sums, and the kernel variant the pass reports (the chain-resident backward pass: also
+// the fused fold, which is queued behind its prediction check).  -> false: a resident pass gave up or failed its check
+bool check_pass(BatchRun &R, BatchPath path, bool bwd, double *red) {
+    const BatchEnv &E = R.E;
+    int32_t &variant = bwd ? E.ctx->timing.bwd_kernel_variant : E.ctx->timing.fwd_kernel_variant;
+    switch (path) {
+    case PATH_RESIDENT:
+        variant = 5;
+        return bwd ? R.RR.backward_ok(E, red) : R.RR.forward_ok(E, red);
+    case PATH_CHAIN:
+        variant = R.CR.clamp ? blcp::VARIANT : 6;
+        if (!(bwd ? R.CR.backward_ok(E, red) : R.CR.forward_ok(E, red))) return false;
+        E.mark(bwd ? "  backward_ok" : "  forward_ok");
+        if (!bwd) return true;
+        if (R.CR.fused && !R.CR.fold(E, red, *E.fold_ev)) return false;
+        E.mark("  prediction check + fold queued");
+        return true;
+    case PATH_ROW1D:
+        variant = R.R1.variant();
+        return !R.R1.gave_up(E);
+    case PATH_STEP:
+        variant = R.SR.variant(E, bwd);
+        return true;
+    }
+    return true;
+}
+
+// forward-only fits: 1 / (the sum of each stored row), from where the path of the pass left the sums
+void forward_only_invN(BatchRun &R, BatchPath path, const double *redF) {
+    const int64_t T = R.E.T, B = R.E.B;
+    for (int64_t b = 0; b < B; ++b)
+        for (int64_t t = 0; t < T; ++t) {
+            double &inv = R.O.invN[(size_t)b * T + t];
+            switch (path) {
+            case PATH_RESIDENT:
+                inv = forward_invN(R.RR.rowsumF[t]);
+                if (t <= T - 1 - R.RR.RQ.lag) inv = 1.0;            // (already normalised by the resident kernel)
+                break;
+            case PATH_CHAIN: inv = forward_invN(R.CR.rowsumC[b][t]); break;
+            default: inv = forward_invN(redF[((size_t)t * B + b) * NRED]); break;
+            }
+        }
+}
+
+// The backward pass of a full fit (core.py:424-470) behind its forward pass, with the host's checks and bookkeeping.  raw_ok: the forward
+// bookkeeping's answer, which this pass still owes where it runs behind the launches (P.late_fb).  -> 1 / 0: that answer and the
+// backward bookkeeping's; -1: a resident pass gave up or failed its check
+int backward_pass(BatchRun &R, const int64_t K, BatchPath path, const PassPlan &P, bool raw_ok) {
+    const BatchEnv &E = R.E;
+    blhip_ctx *ctx = E.ctx;
+    hipStream_t st = E.st;
+    hipEvent_t *ev = ctx->ev;
+    const int64_t T = E.T, B = E.B;
+    float ms = 0;
+    HIPCHECK(hipEventRecord(ev[2], st));
+    double *d_psB = ctx->psumB.as<double>();
+    launch_pass(R, path, true, K, d_psB);
+    double *redB = R.redB = end_pass(ctx, st, ev[3], T * B * NRED, P.nblk, d_psB, ctx->redB, ctx->pinB, false);
+    E.mark("backward pass queued");
+    if (P.late_fb) {
+        if (P.late_copy) HIPCHECK(hipEventSynchronize(ctx->cev[1]));
+        raw_ok = forward_bookkeeping(E.p, *E.prog, R.redF, B, R.dV, R.R1.on, K, E.ff.evidence_only, E.ff.forward_only, R.O);
+        E.mark("forward bookkeeping (behind the backward pass)");
+    }
+    sync_stream(ctx, st);
+    E.mark("backward pass done + sums D2H");
+    if (P.late_copy) {
+        HIPCHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        ctx->timing.forward_ms += ms;
+    }
+    HIPCHECK(hipEventElapsedTime(&ms, ev[2], ev[3]));
+    ctx->timing.backward_ms += ms;
+    ctx->timing.backward_launches += T;
+    if (!check_pass(R, path, true, redB)) return -1;
+    // (a batch the backward kernel folded: nobody reads its row normalisers; per-chain means only where the caller asked for them --
+    //  hyper- / change-point studies take theirs from the average posterior)
+    raw_ok = backward_bookkeeping(E.p, *E.prog, R.redF, redB, B, R.dV, R.R1.on, path == PATH_RESIDENT ? 0 : -1, R.O,
+                                  !(path == PATH_CHAIN && R.CR.fold_done), E.chain_means) && raw_ok;
+    E.mark("backward checks + fused fold + bookkeeping");
+    return raw_ok ? 1 : 0;
+}
+
 // The two passes of a batch and the host's checks and bookkeeping behind each.  K: steps per launch of the K-steps-per-launch 1-D kernel.
 // -> false: the batch has to be repeated -- R.resident_failed: on the launch-per-step kernels, else with K = 1.
 bool run_passes(BatchRun &R, const int64_t K) {
     const BatchEnv &E = R.E;
     blhip_ctx *ctx = E.ctx;
-    const blhip_problem *p = E.p;
     hipStream_t st = E.st;
     hipEvent_t *ev = ctx->ev;
-    const ChainProgram &prog = *E.prog;
     const int64_t T = E.T, B = E.B;
-    const bool full = E.ff.full, evidence_only = E.ff.evidence_only, forward_only = E.ff.forward_only;
-    ResidentRun &RR = R.RR;
-    ChainRun &CR = R.CR;
-    Row1dRun &R1 = R.R1;
-    StepRun &SR = R.SR;
-    BatchOutcome &O = R.O;
     float ms = 0;
     E.mark("path setup");
     // --- forward pass (core.py:372-411) ---
     HIPCHECK(hipEventRecord(ev[0], st));
-    const bool res_now = RR.on && !R.resident_failed;
-    const bool cres_now = CR.on && !R.resident_failed;
-    const int nblk_now = res_now ? RR.nblk : (cres_now ? CR.cp.strips : E.tile.nblk);      // partial-sum slots per (step, sum) of this pass
+    const BatchPath path = R.path();
+    const PassPlan P = pass_plan(path, R.RR.nblk, R.CR.cp.strips, E.tile.nblk, E.ff.full, R.R1.chain, B, ctx->cstream != nullptr,
+                                 ctx->option("late_sums", 1.0) != 0.0);
     double *d_psF = ctx->psumF.as<double>();
-    if (res_now) RR.launch(E, false, d_psF);
-    else if (cres_now) CR.pass(E, false, d_psF);
-    else if (R1.on) R1.forward(E, K, d_psF);
-    else SR.forward(E, d_psF);
-    // (the launch-per-step backward pass of a batch of chains needs nothing of the forward pass's host bookkeeping: it is done
-    //  while the GPU runs that pass -- 11 ms of the published break-point study's fit, 23 batches of 1017 chains)
-    const bool late_fb = full && !res_now && !cres_now && (!R1.on || R1.chain) && B >= 64;
-    // ... and nobody waits for its sums either: they travel to the host on the copy stream BESIDE the backward pass (10 MB per batch
-    // of the break-point study, 2.4 of its 42 ms over PCIe with the chip idle)
-    const bool late_copy = late_fb && ctx->cstream && ctx->option("late_sums", 1.0) != 0.0;
-    double *redF = R.redF = end_pass(ctx, st, ev[1], T * B * NRED, nblk_now, d_psF, ctx->redF, ctx->pinF, late_copy);
-    if (late_copy) {
+    launch_pass(R, path, false, K, d_psF);
+    double *redF = R.redF = end_pass(ctx, st, ev[1], T * B * NRED, P.nblk, d_psF, ctx->redF, ctx->pinF, P.late_copy);
+    if (P.late_copy) {
         E.mark("forward pass queued (its sums follow beside the backward pass)");
     } else {
         E.mark("forward pass queued");
@@ -156,86 +237,28 @@ bool run_passes(BatchRun &R, const int64_t K) {
         ctx->timing.forward_ms += ms;
     }
     ctx->timing.forward_launches += T;
-    if (res_now) {
-        ctx->timing.fwd_kernel_variant = 5;
-        if (!RR.forward_ok(E, redF)) { R.resident_failed = true; return false; }
-    } else if (cres_now) {
-        ctx->timing.fwd_kernel_variant = CR.clamp ? blcp::VARIANT : 6;
-        if (!CR.forward_ok(E, redF)) { R.resident_failed = true; return false; }
-        E.mark("  forward_ok");
-    } else if (R1.on) {
-        ctx->timing.fwd_kernel_variant = R1.variant();
-        if (R1.gave_up(E)) { R.resident_failed = true; return false; }
-    } else {
-        ctx->timing.fwd_kernel_variant = SR.variant(E, false);
-    }
+    if (!check_pass(R, path, false, redF)) { R.resident_failed = true; return false; }
 
-    bool raw_ok = late_fb ? true : forward_bookkeeping(p, prog, redF, B, R.dV, R1.on, K, evidence_only, forward_only, O);
+    bool raw_ok = P.late_fb ? true : forward_bookkeeping(E.p, *E.prog, redF, B, R.dV, R.R1.on, K, E.ff.evidence_only, E.ff.forward_only, R.O);
     E.mark("forward checks + bookkeeping");
 
-    // --- backward pass (core.py:424-470) ---
-    O.invN.assign((size_t)B * T, 0.0);
-    if (full) {
+    R.O.invN.assign((size_t)B * T, 0.0);
+    if (E.ff.full) {
         ctx->psumB.ensure(R.psz * 8);
         ctx->redB.ensure((size_t)T * B * NRED * 8);
-        double *d_psB = ctx->psumB.as<double>();
-        if (R1.on && !raw_ok && K > 1) return false;
-        HIPCHECK(hipEventRecord(ev[2], st));
-        if (res_now) RR.launch(E, true, d_psB);
-        else if (cres_now) {
-            if (CR.fused) { CR.prepare_fold(E, O); E.mark("  prepare_fold"); }
-            CR.pass(E, true, d_psB);
-        }
-        else if (R1.on) R1.backward(E, K, d_psB);
-        else SR.backward(E, d_psB);
-        const double *redB = R.redB = end_pass(ctx, st, ev[3], T * B * NRED, nblk_now, d_psB, ctx->redB, ctx->pinB, false);
-        E.mark("backward pass queued");
-        if (late_fb) {
-            if (late_copy) HIPCHECK(hipEventSynchronize(ctx->cev[1]));
-            raw_ok = forward_bookkeeping(p, prog, redF, B, R.dV, R1.on, K, evidence_only, forward_only, O);
-            E.mark("forward bookkeeping (behind the backward pass)");
-        }
-        sync_stream(ctx, st);
-        E.mark("backward pass done + sums D2H");
-        if (late_copy) {
-            HIPCHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-            ctx->timing.forward_ms += ms;
-        }
-        HIPCHECK(hipEventElapsedTime(&ms, ev[2], ev[3]));
-        ctx->timing.backward_ms += ms;
-        ctx->timing.backward_launches += T;
-        if (res_now) {
-            ctx->timing.bwd_kernel_variant = 5;
-            if (!RR.backward_ok(E, redB)) { R.resident_failed = true; return false; }
-        } else if (cres_now) {
-            ctx->timing.bwd_kernel_variant = CR.clamp ? blcp::VARIANT : 6;
-            if (!CR.backward_ok(E, redB)) { R.resident_failed = true; return false; }
-            E.mark("  backward_ok");
-            if (CR.fused && !CR.fold(E, redB, *E.fold_ev)) { R.resident_failed = true; return false; }
-            E.mark("  prediction check + fold queued");
-        } else if (R1.on) {
-            ctx->timing.bwd_kernel_variant = R1.variant();
-            if (R1.gave_up(E)) { R.resident_failed = true; return false; }
-        } else {
-            ctx->timing.bwd_kernel_variant = SR.variant(E, true);
-        }
-        // (a batch the backward kernel folded: nobody reads its row normalisers; per-chain means only where the caller asked for them --
-        //  hyper- / change-point studies take theirs from the average posterior)
-        raw_ok = backward_bookkeeping(p, prog, redF, redB, B, R.dV, R1.on, res_now ? 0 : -1, O, !(cres_now && CR.fold_done), E.chain_means) && raw_ok;
-        E.mark("backward checks + fused fold + bookkeeping");
-    } else if (forward_only) {
-        for (int64_t b = 0; b < B; ++b)
-            for (int64_t t = 0; t < T; ++t) {
-                O.invN[(size_t)b * T + t] = forward_invN(res_now ? RR.rowsumF[t] : (cres_now ? CR.rowsumC[b][t] : redF[((size_t)t * B + b) * NRED]));
-                if (res_now && t <= T - 1 - RR.RQ.lag) O.invN[(size_t)b * T + t] = 1.0;                // (already normalised by the resident kernel)
-            }
+        if (R.R1.on && !raw_ok && K > 1) return false;
+        const int back = backward_pass(R, K, path, P, raw_ok);
+        if (back < 0) { R.resident_failed = true; return false; }
+        raw_ok = back != 0;
+    } else if (E.ff.forward_only) {
+        forward_only_invN(R, path, redF);
     }
     return raw_ok || K == 1;
 }
 
-// The tail of a batch: carried states / average posterior / kept posterior / results.  usedK: the K its passes went through with;
-// folded_before: a repeat after poisoned carried slots of a batch that is in the accumulator already.
-void finish_batch(BatchRun &R, int64_t usedK, bool folded_before, int64_t nbatch, blhip_result *res) {
+// The tail of a batch: carried states / average posterior / kept posterior / results.  path: the one its passes went through on, usedK:
+// with that K; folded_before: a repeat after poisoned carried slots of a batch that is in the accumulator already.
+void finish_batch(BatchRun &R, BatchPath path, int64_t usedK, bool folded_before, int64_t nbatch, blhip_result *res) {
     const BatchEnv &E = R.E;
     blhip_ctx *ctx = E.ctx;
     const blhip_problem *p = E.p;
@@ -255,31 +278,178 @@ void finish_batch(BatchRun &R, int64_t usedK, bool folded_before, int64_t nbatch
         HIPCHECK(hipGetLastError());
     }
     if (E.ff.carry) {
-        const double *fin; long long fstr;
-        if (!E.ff.evidence_only) { fin = d_post + (size_t)(T - 1) * G; fstr = (long long)T * G; }
-        else { fin = R.R1.on ? E.d_pp[((T - 1) / usedK) & 1] : E.d_pp[(T - 1) & 1]; fstr = G; }
-        store_carry(ctx, p, B, G, R.redF, fin, fstr, E.M->w, E.prog->has_clamp);
+        const CarriedStateSource cs = carried_state_source(E.ff.evidence_only, R.R1.on, T, usedK, G);
+        store_carry(ctx, p, B, G, R.redF, (cs.state < 0 ? d_post : E.d_pp[cs.state]) + cs.offset, cs.stride, E.M->w, E.prog->has_clamp);
     }
-    if (E.ff.accumulate && (CR.fold_done || folded_before)) {
-        // (the backward kernel folded this batch, or it was folded before)
-    } else if (E.ff.accumulate) {
+    const FoldAction fold = fold_action(E.ff.accumulate, CR.fold_done, folded_before, nbatch, E.ff.keep, E.ff.carry);
+    if (fold == FOLD_AND_WAIT || fold == FOLD_UNWAITED) {
         FoldJob lay;
         const bool padded = src.layout == FOLD_PADDED;
         if (padded) { lay.pad_n0p = CR.cp.n0p; lay.pad_n0 = g.n0; lay.pad_n1 = g.n1; lay.pad_step = CR.Gk; lay.pad_ax = CR.ax1 ? 1 : 0; }
-        // (many small batches: nobody waits for a batch's fold; the last one is waited for with the stream below)
         fold_accumulate(ctx, T, G, B, R.O, E.log_w + E.c0, d_post, E.M->w, E.M->invN, src.sm_n0, padded ? &lay : nullptr,
-                        (nbatch >= 4 && !E.ff.keep && !E.ff.carry) ? E.fold_ev : nullptr);
+                        fold == FOLD_UNWAITED ? E.fold_ev : nullptr);
     }
     if (E.ff.keep) {
-        int64_t row0 = 0, row1 = T;              // rows the resident kernel normalised in place (invN = 1 there) need no pass
-        if (R.RR.on && !R.resident_failed) {
-            if (E.ff.full) row1 = 0;             // (every posterior row was stored normalised)
-            else row0 = std::max<int64_t>(0, T - R.RR.RQ.lag);
-        }
-        keep_posterior(ctx, g, T, B, R.O, row0, row1);
+        const RowRange rows = keep_rows(path, E.ff.full, T, R.RR.RQ.lag);
+        keep_posterior(ctx, g, T, B, R.O, rows.row0, rows.row1);
     }
     E.mark("fold / keep / carry");
     write_results(res, p, E.c0, B, R.O, !E.ff.evidence_only);
+}
+
+// what a call of do_fit holds for every one of its batches
+struct FitCall {
+    blhip_ctx *ctx; const blhip_problem *p; hipStream_t st;
+    FitFlags ff; Geometry g; double dV;
+    int64_t n_chains, nbatch; const double *log_w; blhip_result *res;
+    const DeviceTables *DT; Trace *tr;
+    std::vector<hipEvent_t> *fold_ev;          // folds nobody waits for: start / end events of every one (timing)
+};
+
+// The per-(step, chain) programs of batch bi + 1 are built by a second host thread while batch bi runs -- its passes on the GPU, its
+// bookkeeping on this thread (the reference's published break-point study: 23 batches of 1017 chains x 41 steps, 23 - 30 ms of
+// build_program of a 90 - 130-ms fit; the builder touches only its own BatchProgram and the caller's read-only inputs, no HIP call).
+struct BatchProgram { TapTable taps; ChainProgram prog; bool ready = false; std::exception_ptr err; };
+
+class BatchPrograms {
+public:
+    BatchPrograms(const blhip_problem *p, const Geometry &g, const std::vector<int64_t> &batch_start, const double *op_values, bool resume)
+        : p_(p), g_(g), batch_start_(batch_start), op_values_(op_values), resume_(resume) {}
+    BatchPrograms(const BatchPrograms &) = delete;
+    BatchPrograms &operator=(const BatchPrograms &) = delete;
+    ~BatchPrograms() { join(); }                 // (also when a batch throws)
+
+    // The program of batch bi: waits for the builder, builds the program here if nobody has, and starts batch bi + 1.  A failure of an
+    // early build is raised where the build used to be: at the top of that batch.
+    BatchProgram &take(int64_t bi) {
+        join();
+        if (!slot_[bi & 1] || !slot_[bi & 1]->ready) build(bi);
+        BatchProgram &BP = *slot_[bi & 1];
+        BP.ready = false;                        // (consumed: the slot is rebuilt for batch bi + 2)
+        if (BP.err) std::rethrow_exception(BP.err);
+        if (bi + 2 < (int64_t)batch_start_.size()) {
+            try { builder_ = std::thread([this, bi] { build(bi + 1); }); }
+            catch (const std::system_error &) {}        // (no thread to be had: the batch is built at its own top, as before)
+        }
+        return BP;
+    }
+    // the call goes back to an earlier batch: nothing that was built ahead is of use
+    void drop() { join(); slot_[0].reset(); slot_[1].reset(); }
+
+private:
+    void join() { if (builder_.joinable()) builder_.join(); }
+    void build(int64_t bj) {
+        std::unique_ptr<BatchProgram> &N = slot_[bj & 1];
+        N.reset(new BatchProgram());
+        try { build_program(p_, g_, batch_start_[bj], batch_start_[bj + 1] - batch_start_[bj], op_values_, N->taps, N->prog, resume_); }
+        catch (...) { N->err = std::current_exception(); }
+        N->ready = true;
+    }
+    const blhip_problem *p_; const Geometry &g_; const std::vector<int64_t> &batch_start_; const double *op_values_; bool resume_;
+    std::unique_ptr<BatchProgram> slot_[2];
+    std::thread builder_;
+};
+
+// What the fit starts from: nothing kept or carried inside a call from the one before; the resident paths re-armed where their wait
+// is over (probe_residency asks the chip first then)
+void begin_fit(blhip_ctx *ctx) {
+    ctx->post_valid = false;
+    ctx->part = blhip_ctx::PartState{};            // (carried partial accumulators live inside one call)
+    ctx->timing = blhip_timing{};
+    ctx->resident_last_reason = 0;
+    if (ctx->resident.fit_begins()) ctx->probe_last = -1.0;
+    probe_residency(ctx);
+    ctx->timing.xcd_order = ctx->xcd_order_ok ? 1 : 0;
+}
+
+// The state of batch bi -- chains [c0, c0 + B) -- of the call: its buffers, and the paths it may run on set up: the 1-D kernels, or the
+// resident ones (single chain: blhip_resident.hpp; batches of chains: blhip_chainres.hpp) with the launch-per-step kernels as their fall-back
+BatchRun setup_batch(const FitCall &F, int64_t bi, int64_t c0, int64_t B, BatchProgram &BP, const GeometryPlan &gp, const DeviceMeta &M, bool allow_chainres) {
+    blhip_ctx *ctx = F.ctx;
+    const int64_t T = F.p->T;
+    const long long G = F.g.G;
+    BatchRun R;
+    R.dV = F.dV;
+    R.psz = (size_t)T * B * NRED * gp.tile.nblk;
+    ctx->psumF.ensure(R.psz * 8);
+    ctx->redF.ensure((size_t)T * B * NRED * 8);
+    BatchEnv &E = R.E;
+    E.ctx = ctx; E.p = F.p; E.st = F.st; E.g = F.g; E.G = G; E.T = T; E.B = B; E.c0 = c0; E.d = F.DT->d; E.rec_len = F.DT->rec_len; E.ff = F.ff;
+    E.DT = F.DT; E.M = &M; E.prog = &BP.prog; E.taps = &BP.taps; E.gp = &gp; E.tile = gp.tile; E.log_w = F.log_w;
+    E.chain_means = F.res && F.res->posterior_mean;
+    E.tr = F.tr;
+    E.fold_ev = F.fold_ev; E.bi = bi; E.allow_chainres = allow_chainres;
+    ctx->state.ensure((size_t)2 * B * G * 8);
+    E.d_pp[0] = ctx->state.as<double>();
+    E.d_pp[1] = E.d_pp[0] + (size_t)B * G;
+    if (!F.ff.evidence_only) {
+        ctx->post.ensure((size_t)B * T * G * 8);
+        E.d_post = ctx->post.as<double>();
+    }
+    // BLHIP_RESUME: step 0 reads each chain's carried (normalised) state; its "previous partial sums" add up to 1
+    if (F.ff.resume) {
+        E.d_carry_src = carry_source(ctx, F.p, F.n_chains, G);
+        E.d_unit = upload_unit_sums(ctx, F.p, F.st, B, gp.tile.nblk, true);
+    }
+    // (fast_but_clamp: only step0 / use_rec are read, by the chain-resident clamp kernels' setup)
+    const RowRecurrence rr = (gp.fast || gp.fast_but_clamp) ? plan_recurrence(ctx, F.p, F.g.n0, F.g.n1) : RowRecurrence{};
+    E.step0 = rr.step0;
+    R.R1.setup(E);
+    if (!R.R1.on) R.SR.setup(E, rr);
+    ChainRun &CR = R.CR;
+    R.RR.setup(E, F.n_chains, gp.fast, rr.use_rec, R.psz);
+    if (!R.RR.on) CR.setup(E, gp.fast, rr.use_rec, R.psz);
+    if (R.RR.on || CR.on) ctx->psumF.ensure(R.psz * 8);
+    if (CR.on && CR.depad) {                 // a padded batch that hands its posteriors out: scratch sequence for the kernels, ctx->post stays the result
+        ctx->postpad.ensure((size_t)B * T * CR.Gk * 8);
+        E.d_post = ctx->postpad.as<double>();
+    } else if (CR.on && (CR.cp.pad || CR.ax1) && E.d_post) {      // the private sequence of a padded chain-resident batch lives on the padded geometry
+        ctx->post.ensure((size_t)B * T * CR.Gk * 8);
+        E.d_post = ctx->post.as<double>();
+    }
+    return R;
+}
+
+// The attempts of a batch, as the schedule hands them out, until its passes went through (BATCH_FINISH) or the call has to go back to an
+// earlier batch (BATCH_REWIND).  usedK: in, the K of the first attempt; out, of the one that went through
+BatchStep run_attempts(BatchSchedule &sched, BatchRun &R, int base_variant, int64_t &usedK) {
+    blhip_ctx *ctx = R.E.ctx;
+    const ChainRun &CR = R.CR;
+    for (bool first = true;; first = false) {
+        PassFacts f;
+        f.ok = run_passes(R, usedK);
+        f.resident_failed = R.resident_failed; f.cr_on = CR.on; f.touched_parts = CR.touched_parts; f.part_fresh0 = CR.part_fresh0;
+        f.part_live = ctx->part.live; f.part_first_batch = ctx->part.first_batch;
+        const BatchStep s = sched.after_passes(R.E.bi, f);
+        if (s.action == BATCH_FINISH) {
+            if (first && (R.RR.on || CR.on || ctx->timing.fwd_kernel_variant == 8)) ctx->resident.passed();
+            return s;
+        }
+        if (s.action == BATCH_INTERNAL_ERROR) fail("internal: the launch-per-step pass failed after the resident pass gave up");
+        if (s.action == BATCH_REPEAT_K1) { usedK = 1; continue; }
+        // a resident pass gave up or failed: the launch-per-step kernels take over (timing of the failed attempt is dropped)
+        ctx->timing.resident_fallbacks += 1;
+        ctx->timing.resident_fallback_reason = ctx->resident_last_reason ? ctx->resident_last_reason : BLHIP_FALLBACK_RANGE;
+        reset_pass_timing(ctx);
+        if (s.action == BATCH_REWIND) {              // (the slots its backward pass has added to carry earlier batches: they are dropped)
+            ctx->part = blhip_ctx::PartState{};
+            return s;
+        }
+        ctx->timing.fwd_kernel_variant = ctx->timing.bwd_kernel_variant = base_variant;
+        if (CR.on && CR.depad) R.E.d_post = ctx->post.as<double>();      // (no scratch sequence: the launch-per-step kernels write the result)
+    }
+}
+
+// the folds nobody waited for: the last one(s) before anybody reads the accumulator; their time from their events
+void collect_fold_times(blhip_ctx *ctx, hipStream_t st, std::vector<hipEvent_t> &fold_ev) {
+    if (fold_ev.empty()) return;
+    sync_stream(ctx, st);
+    for (size_t k = 0; k + 1 < fold_ev.size(); k += 2) {
+        float fms = 0;
+        HIPCHECK(hipEventElapsedTime(&fms, fold_ev[k], fold_ev[k + 1]));
+        ctx->timing.accumulate_ms += fms;
+    }
+    for (hipEvent_t e : fold_ev) (void)hipEventDestroy(e);
 }
 
 void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const double *op_values,
@@ -297,181 +467,55 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
     HIPCHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const FitFlags ff = decode_flags(ctx, p, flags, log_w);
-    const int64_t T = p->T;
 
     Geometry g{};
     if (p->ndim == 1) { g.n0 = 1; g.n1 = (int)p->n[0]; g.axis_map[0] = 1; g.axis_map[1] = 1; }
     else { g.n0 = (int)p->n[0]; g.n1 = (int)p->n[1]; g.axis_map[0] = 0; g.axis_map[1] = 1; }
     g.G = (long long)g.n0 * g.n1;
-    const long long G = g.G;
-    if (ff.accumulate && (ctx->acc_T != T || ctx->acc_G != G)) fail("accumulator shape mismatch");
+    if (ff.accumulate && (ctx->acc_T != p->T || ctx->acc_G != g.G)) fail("accumulator shape mismatch");
     double dV = 1.0;
     for (int k = 0; k < p->ndim; ++k) dV *= p->lattice[k];
+    begin_fit(ctx);
 
-    ctx->post_valid = false;
-    ctx->part = blhip_ctx::PartState{};            // (carried partial accumulators live inside one call)
-    ctx->timing = blhip_timing{};
-    ctx->resident_last_reason = 0;
-    // a context whose resident launch once gave up tries the resident paths again after a while (one hiccup -- another process
-    // holding CUs -- must not cost 1.4 - 2 x for the life of the process); the wait doubles with every give-up in a row
-    if (!ctx->resident_ok && ++ctx->resident_fits_since >= ctx->resident_retry_after) {
-        ctx->resident_ok = true;
-        ctx->resident_fits_since = 0;
-        ctx->probe_last = -1.0;                      // (re-armed: ask the chip first)
-    }
-    probe_residency(ctx);
-    ctx->timing.xcd_order = ctx->xcd_order_ok ? 1 : 0;
-
-    // ---- shared tables -> HBM ---------------------------------------------------------------------------------------------------
     const DeviceTables DT = upload_tables(ctx, p, g, ff, table_model);
     tr.mark("tables + H2D");
-
-    // ---- memory plan: the batches of the call -------------------------------------------------------------------------------------
+    // the memory plan: the batches of the call
     const std::vector<int64_t> batch_start = plan_fit_batches(ctx, p, g, ff, n_chains, op_values);
     const int64_t nbatch = (int64_t)batch_start.size() - 1;
     ctx->timing.batches = nbatch;
-
     tr.mark("memory budget");
     HIPCHECK(hipEventRecord(ctx->ev[6], st));
 
-    std::vector<hipEvent_t> fold_ev;           // folds nobody waits for: start / end events of every one (timing)
-    // The per-(step, chain) programs of batch bi + 1 are built by a second host thread while batch bi runs -- its passes on the GPU, its
-    // bookkeeping on this thread (the reference's published break-point study: 23 batches of 1017 chains x 41 steps, 23 - 30 ms of
-    // build_program of a 90 - 130-ms fit; the builder touches only its own BatchProgram and the caller's read-only inputs, no HIP call).
-    // A failure of the early build is raised where the build used to be: at the top of that batch.
-    struct BatchProgram { TapTable taps; ChainProgram prog; bool ready = false; std::exception_ptr err; };
-    std::unique_ptr<BatchProgram> bprog[2];
-    auto build_batch = [&](int64_t bj) {
-        std::unique_ptr<BatchProgram> &N = bprog[bj & 1];
-        N.reset(new BatchProgram());
-        try { build_program(p, g, batch_start[bj], batch_start[bj + 1] - batch_start[bj], op_values, N->taps, N->prog, ff.resume); }
-        catch (...) { N->err = std::current_exception(); }
-        N->ready = true;
-    };
-    std::thread builder;
-    struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } builder_guard{builder};      // (also when a batch throws)
-    const bool build_ahead = nbatch > 1;
-    int64_t fallback_until = -1;                   // batches up to this one repeat on the launch-per-step kernels (poisoned carried slots, below)
-    // per batch of the call: its contribution went into the carried partial accumulators (a fused fold with a finite reference), not
-    // into the accumulator itself.  The repeat after poisoned slots folds only such batches again: a batch that was folded directly
-    // (not chain-resident, or repeated in place after its forward check) is in the accumulator already.
-    std::vector<char> in_slots((size_t)nbatch, 0);
-    int64_t refold_before = -1;                    // batches below this one that a repeat re-runs are folded again only if in_slots
-    for (int64_t bi = 0; bi < nbatch; ++bi) {
-        const int64_t c0 = batch_start[bi], B = batch_start[bi + 1] - c0;
+    std::vector<hipEvent_t> fold_ev;
+    const FitCall F{ctx, p, st, ff, g, dV, n_chains, nbatch, log_w, res, &DT, &tr, &fold_ev};
+    BatchPrograms programs(p, g, batch_start, op_values, ff.resume);
+    BatchSchedule sched(nbatch);
+    while (sched.more()) {
+        const int64_t bi = sched.batch(), c0 = batch_start[bi], B = batch_start[bi + 1] - c0;
         tr.mark("batch setup");
-        if (builder.joinable()) builder.join();
-        if (!bprog[bi & 1] || !bprog[bi & 1]->ready) build_batch(bi);
-        BatchProgram &BP = *bprog[bi & 1];
-        BP.ready = false;                        // (consumed: the slot is rebuilt for batch bi + 2)
-        if (BP.err) std::rethrow_exception(BP.err);
-        TapTable &taps = BP.taps;
-        ChainProgram &prog = BP.prog;
-        if (build_ahead && bi + 1 < nbatch) {
-            try { builder = std::thread(build_batch, bi + 1); }
-            catch (const std::system_error &) {}        // (no thread to be had: the batch is built at its own top, as before)
-        }
+        BatchProgram &BP = programs.take(bi);
         tr.mark("build_program");
-        const GeometryPlan gp = plan_geometry(ctx, p, g, prog, B, DT.d, ff.resume, ff.carry, &taps);
-        const Tile &tile = gp.tile;
+        const GeometryPlan gp = plan_geometry(ctx, p, g, BP.prog, B, DT.d, ff.resume, ff.carry, &BP.taps);
         const int base_variant = gp.fast ? 1 : (gp.fused1d ? 4 : 0);
         ctx->timing.fwd_kernel_variant = ctx->timing.bwd_kernel_variant = base_variant;
-        ctx->timing.cells_per_launch = std::max<int64_t>(ctx->timing.cells_per_launch, B * G);
-
-        // --- device metadata ---
+        ctx->timing.cells_per_launch = std::max<int64_t>(ctx->timing.cells_per_launch, B * g.G);
         DeviceMeta M;
-        upload_metadata(ctx, p, prog, taps, B, ff.full, gp.fast, tile.nblk, M, gp.wideH, gp.wideV, gp.hSplit, gp.hFusedMax);
+        upload_metadata(ctx, p, BP.prog, BP.taps, B, ff.full, gp.fast, gp.tile.nblk, M, gp.wideH, gp.wideV, gp.hSplit, gp.hFusedMax);
         tr.mark("buckets + metadata H2D");
 
-        // --- state ---
-        BatchRun R;
-        R.dV = dV;
-        R.psz = (size_t)T * B * NRED * tile.nblk;
-        ctx->psumF.ensure(R.psz * 8);
-        ctx->redF.ensure((size_t)T * B * NRED * 8);
-        BatchEnv &E = R.E;
-        E.ctx = ctx; E.p = p; E.st = st; E.g = g; E.G = G; E.T = T; E.B = B; E.c0 = c0; E.d = DT.d; E.rec_len = DT.rec_len; E.ff = ff;
-        E.DT = &DT; E.M = &M; E.prog = &prog; E.taps = &taps; E.gp = &gp; E.tile = tile; E.log_w = log_w;
-        E.chain_means = res && res->posterior_mean;
-        E.tr = &tr;
-        E.fold_ev = &fold_ev; E.bi = bi; E.allow_chainres = bi > fallback_until;
-        ctx->state.ensure((size_t)2 * B * G * 8);
-        E.d_pp[0] = ctx->state.as<double>();
-        E.d_pp[1] = E.d_pp[0] + (size_t)B * G;
-        if (!ff.evidence_only) {
-            ctx->post.ensure((size_t)B * T * G * 8);
-            E.d_post = ctx->post.as<double>();
-        }
-        // BLHIP_RESUME: step 0 reads each chain's carried (normalised) state; its "previous partial sums" add up to 1
-        if (ff.resume) {
-            E.d_carry_src = carry_source(ctx, p, n_chains, G);
-            E.d_unit = upload_unit_sums(ctx, p, st, B, tile.nblk, true);
-        }
-        // ---- the paths: 1-D kernels, or the resident ones (single chain: blhip_resident.hpp; batches of chains: blhip_chainres.hpp) with
-        //      the launch-per-step kernels as their fall-back -----------------------------------------------------------------------------
-        // (fast_but_clamp: only step0 / use_rec are read, by the chain-resident clamp kernels' setup)
-        const RowRecurrence rr = (gp.fast || gp.fast_but_clamp) ? plan_recurrence(ctx, p, g.n0, g.n1) : RowRecurrence{};
-        E.step0 = rr.step0;
-        R.R1.setup(E);
-        if (!R.R1.on) R.SR.setup(E, rr);
-        ResidentRun &RR = R.RR;
-        ChainRun &CR = R.CR;
-        RR.setup(E, n_chains, gp.fast, rr.use_rec, R.psz);
-        if (!RR.on) CR.setup(E, gp.fast, rr.use_rec, R.psz);
-        if (RR.on || CR.on) ctx->psumF.ensure(R.psz * 8);
-        if (CR.on && CR.depad) {                 // a padded batch that hands its posteriors out: scratch sequence for the kernels, ctx->post stays the result
-            ctx->postpad.ensure((size_t)B * T * CR.Gk * 8);
-            E.d_post = ctx->postpad.as<double>();
-        } else if (CR.on && (CR.cp.pad || CR.ax1) && E.d_post) {      // the private sequence of a padded chain-resident batch lives on the padded geometry
-            ctx->post.ensure((size_t)B * T * CR.Gk * 8);
-            E.d_post = ctx->post.as<double>();
-        }
-
+        BatchRun R = setup_batch(F, bi, c0, B, BP, gp, M, sched.allow_chainres(bi));
         int64_t usedK = gp.fusedK;
-        if (!run_passes(R, gp.fusedK)) {
-            if (R.resident_failed) {                 // the launch-per-step kernels take over (timing of the failed attempt is dropped)
-                ctx->timing.resident_fallbacks += 1;
-                ctx->timing.resident_fallback_reason = ctx->resident_last_reason ? ctx->resident_last_reason : BLHIP_FALLBACK_RANGE;
-                reset_pass_timing(ctx);
-                if (CR.on && CR.touched_parts && !CR.part_fresh0) {
-                    // the failed backward pass has added to partial accumulators that carry earlier batches of this call: the slots are
-                    // dropped, and the batches since the first one they carry and this one are repeated on the launch-per-step kernels.
-                    // Batches of that range that were folded directly into the accumulator (in_slots = 0: not chain-resident, or repeated
-                    // in place) are in the average posterior already: their repeat skips the fold
-                    const int64_t from = ctx->part.live ? ctx->part.first_batch : bi;
-                    refold_before = bi;
-                    ctx->part = blhip_ctx::PartState{};
-                    fallback_until = bi;
-                    if (builder.joinable()) builder.join();
-                    bprog[0].reset(); bprog[1].reset();
-                    sync_stream(ctx, st);
-                    bi = from - 1;
-                    continue;
-                }
-                ctx->timing.fwd_kernel_variant = ctx->timing.bwd_kernel_variant = base_variant;
-                if (CR.on && CR.depad) E.d_post = ctx->post.as<double>();      // (no scratch sequence: the launch-per-step kernels write the result)
-                if (!run_passes(R, gp.fusedK)) fail("internal: the launch-per-step pass failed after the resident pass gave up");
-            } else { usedK = 1; run_passes(R, 1); }
-        } else if (RR.on || CR.on || ctx->timing.fwd_kernel_variant == 8) {
-            ctx->resident_retry_after = 8;           // a resident pass went through: the next give-up starts from the short wait again
-            ctx->resident_giveups = 0;               // (the wait doubles with give-ups IN A ROW only)
+        if (run_attempts(sched, R, base_variant, usedK).action == BATCH_REWIND) {
+            programs.drop();
+            sync_stream(ctx, st);
+            continue;
         }
-
-        // (a repeat after poisoned carried slots: a batch before the failed one that did not fold into the slots is in the accumulator already)
-        const bool refold_skip = bi < refold_before && !in_slots[bi];
-        in_slots[bi] = CR.on && !R.resident_failed && CR.fused && CR.fold_done && std::isfinite(CR.fold_ref);
-        finish_batch(R, usedK, refold_skip, nbatch, res);
+        const BatchPath path = R.path();
+        const bool went_into_slots = path == PATH_CHAIN && R.CR.fused && R.CR.fold_done && std::isfinite(R.CR.fold_ref);
+        finish_batch(R, path, usedK, sched.finished(bi, went_into_slots), nbatch, res);
     }
     flush_partials(ctx, st, &fold_ev);         // the carried partial accumulators of the chain-resident fold -> the average posterior
-    if (!fold_ev.empty()) {                    // the last fold(s) before anybody reads the accumulator; their time from their events
-        sync_stream(ctx, st);
-        for (size_t k = 0; k + 1 < fold_ev.size(); k += 2) {
-            float fms = 0;
-            HIPCHECK(hipEventElapsedTime(&fms, fold_ev[k], fold_ev[k + 1]));
-            ctx->timing.accumulate_ms += fms;
-        }
-        for (hipEvent_t e : fold_ev) (void)hipEventDestroy(e);
-    }
+    collect_fold_times(ctx, st, fold_ev);
     tr.mark("batches done");
     HIPCHECK(hipEventRecord(ctx->ev[7], st));
     HIPCHECK(hipEventSynchronize(ctx->ev[7]));
@@ -799,8 +843,8 @@ int blhip_set_option(blhip_ctx *ctx, const char *key, double value) {
     if (!ctx || !key) return -1;
     // "resident_ok": the context's memory of a resident launch that gave up (its blocks were not all co-resident) -- settable so that
     // a caller (the tests of the fall-back) can re-arm the resident paths
-    if (std::strcmp(key, "resident_ok") == 0) { ctx->resident_ok = value != 0.0; ctx->resident_fits_since = 0; if (value != 0.0) { ctx->resident_retry_after = 8; ctx->resident_giveups = 0; } return 0; }
-    if (std::strcmp(key, "resident_retry_after") == 0) { ctx->resident_retry_after = std::max(1, (int)value); return 0; }
+    if (std::strcmp(key, "resident_ok") == 0) { ctx->resident.set_ok(value != 0.0); return 0; }
+    if (std::strcmp(key, "resident_retry_after") == 0) { ctx->resident.retry_after = std::max(1, (int)value); return 0; }
     // (a key the library never reads is an error, not a silent no-op: an A/B run over a removed option measured nothing -- ADVICE r05)
     static const char *const known[] = {
         "carry_partials", "chain1d", "chain1d_clamp", "chain1d_long", "chain1d_shift", "chain_ax1", "chain_clamp", "chain_depad", "chain_prof", "chain_resident", "chain_resident_lag",
@@ -881,7 +925,7 @@ int blhip_bandwidth_probe(blhip_ctx *ctx, int64_t bytes, int iterations, double 
 int blhip_last_timing(blhip_ctx *ctx, blhip_timing *out) {
     if (!ctx || !out) return -1;
     *out = ctx->timing;
-    out->resident_armed = ctx->resident_ok ? 1 : 0;
+    out->resident_armed = ctx->resident.ok ? 1 : 0;
     return 0;
 }
 

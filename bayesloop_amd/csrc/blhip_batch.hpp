@@ -365,7 +365,7 @@ int64_t chains_per_batch(blhip_ctx *ctx, const blhip_problem *p, const Geometry 
     // -- only where the chain-resident path can be taken at all (else they are never allocated: a narrow grid with a long series
     //    gave up its whole budget to 128 slots it never used and ran one chain per batch), and never more than half of the budget
     if (ff.accumulate && ff.full && p->ndim == 2 && p->obs_model == BLHIP_OM_GAUSSIAN && chain_rows_ok(g.n0) &&
-        g.n1 >= 1 && g.n1 <= 16 * blc::MAX_STRIPS && ctx->option("chain_resident", 1.0) != 0.0 && ctx->resident_ok) {
+        g.n1 >= 1 && g.n1 <= 16 * blc::MAX_STRIPS && ctx->option("chain_resident", 1.0) != 0.0 && ctx->resident.ok) {
         const double slots = std::max(1, std::min(ctx->num_cus, 256) / ((g.n1 + blc::WCOL - 1) / blc::WCOL));
         budget -= std::min(0.5 * budget, std::min<double>(slots, (double)n_chains) * (double)T * Gk * 8.0);
     }
@@ -391,7 +391,7 @@ std::vector<int64_t> plan_fit_batches(blhip_ctx *ctx, const blhip_problem *p, co
     const int64_t Bmax = chains_per_batch(ctx, p, g, ff, n_chains);
     // (cuts on radius-bucket boundaries serve the launch-per-step kernels; grids the chain-resident kernel takes keep whole launches)
     const bool chain_shape = p->ndim == 2 && (p->obs_model == BLHIP_OM_GAUSSIAN || (p->obs_model == BLHIP_OM_TABLE && g.n0 <= 512)) && chain_rows_ok(g.n0) && g.n1 <= 16 * blc::MAX_STRIPS &&
-                             ctx->option("chain_resident", 1.0) != 0.0 && ctx->resident_ok;
+                             ctx->option("chain_resident", 1.0) != 0.0 && ctx->resident.ok;
     std::vector<int64_t> batch_start = plan_batches(p, n_chains, op_values, Bmax, !chain_shape);
     // (the cut: 40; grids the chain-resident kernels take: 80)
     const bool chain_wide = chain_shape && p->obs_model == BLHIP_OM_GAUSSIAN && ctx->option("chain_wide", 1.0) != 0.0;

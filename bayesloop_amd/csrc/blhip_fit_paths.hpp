@@ -52,13 +52,10 @@ bool resident_gave_up(blhip_ctx *ctx, hipStream_t st, const unsigned *d_abort, b
     // (option resident_force_abort: the tests of the fall-back pretend that a block gave up)
     if (*h != 0u || force || ctx->option("resident_force_abort", 0.0) != 0.0) {
         ctx->resident_last_reason = *h != 0u ? BLHIP_FALLBACK_GAVE_UP : BLHIP_FALLBACK_FORCED;
-        if (ctx->resident_ok && ctx->option("quiet", 0.0) == 0.0)
+        if (ctx->resident.ok && ctx->option("quiet", 0.0) == 0.0)
             std::fprintf(stderr, "[blhip] a resident launch gave up waiting for a peer block (its blocks were not all co-resident: a shared or "
                                  "partitioned GPU?); this batch is repeated and the context continues with the launch-per-step kernels\n");
-        ctx->resident_ok = false;
-        ctx->resident_fits_since = 0;
-        ctx->resident_giveups += 1;
-        if (ctx->resident_giveups > 1) ctx->resident_retry_after = std::min(1024, 2 * ctx->resident_retry_after);
+        ctx->resident.gave_up();
         return true;
     }
     return false;
@@ -96,7 +93,7 @@ bool chip_is_ours(blhip_ctx *ctx) {
 // per resident_probe_interval_s (1 s) otherwise.  A busy chip parks the resident paths exactly as a give-up does (retry after 8, 16, ..
 // fits) -- at the price of the probe's bound (2 ms), not of a launch's.
 void probe_residency(blhip_ctx *ctx) {
-    if (!ctx->resident_ok || ctx->option("resident_probe", 1.0) == 0.0) return;
+    if (!ctx->resident.ok || ctx->option("resident_probe", 1.0) == 0.0) return;
     const double now = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
     if (ctx->probe_last >= 0.0 && now - ctx->probe_last < ctx->option("resident_probe_interval_s", 1.0)) return;
     ctx->probe_last = now;
@@ -108,12 +105,9 @@ void probe_residency(blhip_ctx *ctx) {
                              "%.1f ms: another process, or a partitioned device); fits run on the launch-per-step kernels until a later probe finds it free\n",
                      1e3 * std::max(1e-4, ctx->option("resident_probe_timeout_s", 0.002)));
     ctx->probe_announced = true;
-    ctx->resident_ok = false;
-    ctx->resident_fits_since = 0;
-    ctx->resident_giveups += 1;
+    ctx->resident.gave_up();
     ctx->resident_last_reason = BLHIP_FALLBACK_BUSY;
     ctx->timing.resident_fallback_reason = BLHIP_FALLBACK_BUSY;
-    if (ctx->resident_giveups > 1) ctx->resident_retry_after = std::min(1024, 2 * ctx->resident_retry_after);
 }
 
 // ---- the time-resident path of a single-chain batch: one launch per pass instead of one per step (blhip_resident.hpp) -----------------
@@ -141,7 +135,7 @@ struct ResidentRun {
         const bool gauss = E.p->obs_model == BLHIP_OM_GAUSSIAN && use_rec && E.d <= blr::DMAX;
         const bool tab = E.p->obs_model == BLHIP_OM_TABLE && E.DT->lik != nullptr && ctx->option("resident_table", 1.0) != 0.0;
         if (fast && n_chains == 1 && (gauss || tab) && !E.ff.resume && !E.ff.carry && !E.p->backward_init &&
-            prog.LW0 <= blr::R && prog.LW1 <= blr::R && ctx->option("resident", 1.0) != 0.0 && ctx->resident_ok &&
+            prog.LW0 <= blr::R && prog.LW1 <= blr::R && ctx->option("resident", 1.0) != 0.0 && ctx->resident.ok &&
             plan_resident(E.g.n0, E.g.n1, std::min(ctx->num_cus, 256), rp)) {
             on = prog.kindF[0] == SRC_PRIOR && (!full || prog.kindB[T - 1] == SRC_UNIFORM);
             // (the padded 128 x 128 BACKWARD kernel spills 231 registers: 2000 x 1100, backward step 40 - 45 us against 26.8 us with one
@@ -329,7 +323,7 @@ inline ChainFacts chain_facts(const BatchEnv &E, bool fast, bool use_rec) {
     F.resume = E.ff.resume; F.carry = E.ff.carry; F.full = E.ff.full; F.keep = E.ff.keep; F.accumulate = E.ff.accumulate;
     F.evidence_only = E.ff.evidence_only; F.forward_only = E.ff.forward_only; F.backward_init = E.p->backward_init != nullptr;
     F.n0 = E.g.n0; F.n1 = E.g.n1; F.G = E.G; F.T = E.T; F.B = E.B;
-    F.chain_means = E.chain_means; F.allow_chainres = E.allow_chainres; F.resident_ok = E.ctx->resident_ok; F.num_cus = E.ctx->num_cus;
+    F.chain_means = E.chain_means; F.allow_chainres = E.allow_chainres; F.resident_ok = E.ctx->resident.ok; F.num_cus = E.ctx->num_cus;
     F.acc_aligned = ((uintptr_t)E.ctx->acc & 15) == 0;
     return F;
 }

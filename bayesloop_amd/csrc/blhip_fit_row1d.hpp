@@ -46,7 +46,7 @@ struct Row1dRun {
         d_fwd_sums = d_psF;
         // 1-D grids whose blocks all fit on the chip at once: ONE persistent launch per pass (blhip_persist1d.hpp), else a launch per K steps
         // (a pass of a single superstep -- OnlineStudy.step, T <= K -- has no launch boundary to save)
-        persist = !chain && !gave_up_before && ctx->resident_ok && ctx->option("persist1d", 1.0) != 0.0 && T > K &&
+        persist = !chain && !gave_up_before && ctx->resident.ok && ctx->option("persist1d", 1.0) != 0.0 && T > K &&
                   (long long)E.tile.nblk * B <= std::min(ctx->num_cus, 256);
         // (the chains of a batch see the same likelihood: tabulated once per batch by the in-kernel function itself, shared by both passes)
         // (rows beyond bl1c::NMAX: the long-row kernel has no likelihood of its own -- the table for any number of chains)

@@ -2,9 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdint>
 #include <limits>
 #include <map>
 #include <mutex>
@@ -69,6 +71,8 @@ struct PinBuf {
 
 thread_local std::string g_create_error;
 
+#include "blhip_batch_sched.hpp"    // ResidentRetry (no HIP call)
+
 }  // namespace
 
 struct blhip_ctx {
@@ -118,11 +122,9 @@ struct blhip_ctx {
     PinBuf pinC;
     // time-resident path (blhip_resident.hpp): halo strips / flags, and whether every tile was co-resident so far
     DevBuf resx;
-    bool resident_ok = true;
     // a resident launch that gave up (its blocks were not all co-resident: another process held CUs) parks the resident paths; they
-    // are tried again after `resident_retry_after` further fits, and the wait doubles with every give-up in a row (8, 16, ... 1024)
-    int resident_retry_after = 8, resident_fits_since = 0;
-    long long resident_giveups = 0;
+    // are tried again after `resident.retry_after` further fits, and the wait doubles with every give-up in a row (8, 16, ... 1024)
+    ResidentRetry resident;
     int resident_last_reason = 0;                  // BLHIP_FALLBACK_* of the last resident batch that fell back
     int num_cus = 0;
     DevBuf accw;                 // device copies of the fused fold's per-chain scales and weights (ChainRun::fold_buffers)

@@ -507,7 +507,7 @@ def _build():
 
 _build()
 
-NOT_IN_THE_TABLE = {'commbuf': 'multi-GPU exchange only (blhip_comm.hpp)', 'probebuf': 'the co-residency probe only, zeroed before every probe (blhip_fit_paths.hpp:77)'}
+NOT_IN_THE_TABLE = {'commbuf': 'multi-GPU exchange only (blhip_comm.hpp)', 'probebuf': 'the co-residency probe only, zeroed before every probe (blhip_fit_paths.hpp:74)'}
 
 
 def devbuf_members():
