@@ -12,7 +12,7 @@ import os
 from .exceptions import BackendError
 
 LIB_NAME = 'libblhip.so'
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 OM_POISSON, OM_GAUSSIAN, OM_GAUSSIAN_MEAN, OM_TABLE = 1, 2, 3, 100
 OM_BERNOULLI, OM_LAPLACE, OM_WHITE_NOISE, OM_AR1, OM_SCALED_AR1 = 4, 5, 6, 7, 8
@@ -156,6 +156,9 @@ PROTOTYPES = {
     'blhip_posterior_query': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int64), C.c_int64, C.POINTER(Query), c_double_p]),
     'blhip_host_query_check': (C.c_int, [C.POINTER(Query), C.c_int64, C.c_char_p, C.c_int]),
     'blhip_host_query_plan': (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_double, C.POINTER(C.c_int64)]),
+    'blhip_posterior_bins': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int64, c_double_p]),
+    'blhip_host_bins_check': (C.c_int, [C.POINTER(C.c_int32), C.c_int64, C.c_int64, C.c_char_p, C.c_int]),
+    'blhip_host_bins_plan': (C.c_int, [C.POINTER(C.c_int32), C.c_int64, C.c_int64, C.c_int64, C.c_double, C.POINTER(C.c_int64)]),
     'blhip_host_taps': (C.c_int64, [C.c_int, C.c_int64, c_double_p, C.c_int, c_double_p, C.c_int64, C.POINTER(C.c_int)]),
 }
 

@@ -49,6 +49,7 @@
 #include "blhip_predictive.hpp"
 #include "blhip_online.hpp"
 #include "blhip_query.hpp"
+#include "blhip_bins.hpp"
 
 using namespace blk;
 
@@ -847,7 +848,7 @@ int blhip_set_option(blhip_ctx *ctx, const char *key, double value) {
     if (std::strcmp(key, "resident_retry_after") == 0) { ctx->resident.retry_after = std::max(1, (int)value); return 0; }
     // (a key the library never reads is an error, not a silent no-op: an A/B run over a removed option measured nothing -- ADVICE r05)
     static const char *const known[] = {
-        "carry_partials", "chain1d", "chain1d_clamp", "chain1d_long", "chain1d_shift", "chain_ax1", "chain_clamp", "chain_depad", "chain_prof", "chain_resident", "chain_resident_lag",
+        "bins_gw", "bins_sb", "bins_slab", "carry_partials", "chain1d", "chain1d_clamp", "chain1d_long", "chain1d_shift", "chain_ax1", "chain_clamp", "chain_depad", "chain_prof", "chain_resident", "chain_resident_lag",
         "chain_force_fail_batch", "chain_force_fail_stage", "chain_nd", "chain_table", "chain_wide", "comm_reduce_mode", "fast", "fast_S", "fold2", "fold2_cp", "fold_force_fail_batch", "fuse1d", "fuse_accumulate", "late_sums", "lik_program", "max_batch",
         "mem_budget_bytes", "mfma", "mfma_S", "mfma_h", "mfma_h_max_cells", "online_block", "parser_device", "parser_pair_max", "peer_copy_mode", "persist1d", "predictive", "quiet", "recurrence", "resident",
         "resident_force_abort", "resident_lag", "resident_probe", "resident_probe_force_busy", "resident_probe_interval_s", "resident_probe_timeout_s",
@@ -1283,6 +1284,84 @@ int blhip_posterior_query(blhip_ctx *ctx, int source, int64_t chain, const int64
             HIPCHECK(hipGetLastError());
             HIPCHECK(hipMemcpyAsync(host_out + c0, d_out, (size_t)S * 8, hipMemcpyDeviceToHost, st));
             sync_stream(ctx, st);       // (the chunk's uploads are overwritten by the next one)
+        }
+    });
+}
+
+int blhip_host_bins_check(const int32_t *bin, int64_t G, int64_t n_bins, char *err, int errlen) { return blb::check_bins(bin, G, n_bins, err, errlen); }
+
+int blhip_host_bins_plan(const int32_t *bin, int64_t G, int64_t n_bins, int64_t n_steps, double budget, int64_t *plan_out) {
+    if (!plan_out || G < 1 || G > 0x7fffffffLL || n_bins < 1 || n_bins > 0x7fffffffLL) return -1;
+    const blb::Shape sh;
+    blb::Order O;
+    O.slab = sh.slab; O.n_slabs = (G + sh.slab - 1) / sh.slab; O.gw = sh.gw_max;
+    if (bin && (blb::check_bins(bin, G, n_bins, nullptr, 0) != 0 || !blb::order(bin, G, n_bins, sh.slab, sh.gw_max, O))) return -1;
+    blb::BinsPlan P;
+    const bool ok = blb::bins_plan(n_bins, O.n_runs, O.table_bytes(), n_steps, sh.sb, budget, P);
+    if (!ok && P.min_budget_bytes == 0) return -1;
+    const int64_t v[12] = {O.slab, O.n_slabs, sh.sb, O.gw, O.n_runs, O.n_groups, O.table_bytes(), P.steps_per_chunk, P.n_chunks, P.workspace_bytes,
+                           P.min_budget_bytes, O.lds_bytes(sh.sb)};
+    for (int k = 0; k < 12; ++k) plan_out[k] = v[k];
+    return ok ? 0 : 1;
+}
+
+int blhip_posterior_bins(blhip_ctx *ctx, int source, int64_t chain, const int64_t *steps, int64_t n_steps, const int32_t *bin, int64_t G, int64_t n_bins,
+                         double *host_out) {
+    return guarded(ctx, [&] {
+        // ---- everything that can be refused is refused before the first launch
+        if (!host_out) fail("blhip_posterior_bins: host_out is NULL");
+        if (!steps) fail("blhip_posterior_bins: steps is NULL");
+        if (n_steps < 1 || n_steps > (1ll << 31)) fail("blhip_posterior_bins: n_steps = %lld", (long long)n_steps);
+        char msg[256] = "";
+        if (blb::check_bins(bin, G, n_bins, msg, (int)sizeof msg) != 0) fail("blhip_posterior_bins: %s", msg);
+        HIPCHECK(hipSetDevice(ctx->device));
+        const SeqView v = sequence_view(ctx, source, chain);
+        for (int64_t s = 0; s < n_steps; ++s)
+            if (steps[s] < 0 || steps[s] >= v.T) fail("blhip_posterior_bins: steps[%lld] = %lld is outside the %lld rows of the sequence", (long long)s, (long long)steps[s], (long long)v.T);
+        if ((long long)v.n0 * v.n1 != G) fail("blhip_posterior_bins: the map (%lld cells) does not match the sequence (%lld cells)", (long long)G, (long long)v.n0 * v.n1);
+        // ---- the order of the map and the plan
+        const blb::Shape sh = blb::shape(ctx->option("bins_slab", (double)blb::SLAB), ctx->option("bins_sb", blb::SB), ctx->option("bins_gw", blb::GW));
+        blb::Order O;
+        if (!blb::order(bin, G, n_bins, sh.slab, sh.gw_max, O)) fail("blhip_posterior_bins: the tables of this map do not fit 32-bit indices");
+        size_t free_b = 0, total_b = 0;
+        HIPCHECK(hipMemGetInfo(&free_b, &total_b));
+        const double budget = std::min((double)free_b + (double)ctx->queryws.cap, ctx->option("mem_budget_bytes", 0.70 * (double)total_b)) * 0.9;
+        blb::BinsPlan PL;
+        if (!blb::bins_plan(n_bins, O.n_runs, O.table_bytes(), n_steps, sh.sb, budget, PL))
+            fail("blhip_posterior_bins: a workspace budget of %.0f bytes is below the %lld bytes the smallest plan needs", budget, PL.min_budget_bytes);
+        const long long lds = O.lds_bytes(sh.sb);
+        if (O.n_slabs > 0x7fffffffLL || (PL.steps_per_chunk + sh.sb - 1) / sh.sb > ctx->max_grid_y || lds > blb::LDS_BYTES_MAX)
+            fail("blhip_posterior_bins: the plan's grid does not fit one launch");
+        ctx->queryws.ensure((size_t)PL.workspace_bytes);
+        char *ws = ctx->queryws.as<char>(), *cur = ws;
+        hipStream_t st = ctx->stream;
+        long long *d_slabs = carve<long long>(cur, O.slabs.size());
+        int *d_tab = carve<int>(cur, O.tab.size());
+        if ((long long)(cur - ws) != O.table_bytes()) fail("blhip_posterior_bins: internal: the tables take %lld bytes, planned %lld", (long long)(cur - ws), O.table_bytes());
+        HIPCHECK(hipMemcpyAsync(d_slabs, O.slabs.data(), O.slabs.size() * 8, hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(d_tab, O.tab.data(), O.tab.size() * 4, hipMemcpyHostToDevice, st));
+        long long *d_steps = reinterpret_cast<long long *>(ws + PL.off_steps);
+        double *d_part = reinterpret_cast<double *>(ws + PL.off_part), *d_out = reinterpret_cast<double *>(ws + PL.off_out);
+        blb::BinsParams P{};
+        P.post = v.p; P.steps = d_steps; P.slabs = d_slabs;
+        P.perm = d_tab + O.off_perm; P.gdst = d_tab + O.off_gdst; P.multi = d_tab + O.off_multi;
+        P.part = d_part;
+        P.G = G; P.slab = O.slab; P.R = O.n_runs; P.n_slabs = O.n_slabs;
+        P.sb = sh.sb; P.gw = O.gw; P.slots = (int)O.max_slots;
+        P.wide = (G % 2 == 0 && ((uintptr_t)v.p & 15) == 0) ? 1 : 0;
+        if (lds > 64 * 1024) blerr::arm_kernel(reinterpret_cast<const void *>(blb::bins_kernel));
+        static_assert(sizeof(long long) == sizeof(int64_t), "steps are uploaded as they come");
+        for (int64_t c0 = 0; c0 < n_steps; c0 += PL.steps_per_chunk) {
+            const long long S = std::min<int64_t>(PL.steps_per_chunk, n_steps - c0);
+            HIPCHECK(hipMemcpyAsync(d_steps, steps + c0, (size_t)S * 8, hipMemcpyHostToDevice, st));
+            P.S = (int)S;
+            if (O.n_runs > 0)      // (a map that leaves every cell out has nothing to add: the combine kernel writes the zeros)
+                BL_LAUNCH(blb::bins_kernel, dim3((unsigned)O.n_slabs, (unsigned)((S + sh.sb - 1) / sh.sb)), dim3(blb::NT), (size_t)lds, st, P);
+            BL_LAUNCH(blb::bins_combine_kernel, dim3((unsigned)((S * n_bins + blb::NT - 1) / blb::NT)), dim3(blb::NT), 0, st, d_part, d_tab + O.off_binptr,
+                      d_tab + O.off_binruns, d_out, O.n_runs, S, (long long)n_bins);
+            HIPCHECK(hipGetLastError());
+            HIPCHECK(hipMemcpyAsync(host_out + (size_t)c0 * n_bins, d_out, (size_t)S * n_bins * 8, hipMemcpyDeviceToHost, st));
+            sync_stream(ctx, st);       // (the chunk's steps are overwritten by the next one)
         }
     });
 }

@@ -138,7 +138,8 @@ struct blhip_ctx {
     struct LikProgram { std::vector<int32_t> ops; std::vector<double> consts, step; int64_t n_step = 0; bool armed = false; } likprog;
     DevBuf likprog_dev;
     DevBuf predws, predx;        // the posterior predictive (blhip_predictive.hpp): likelihood rows of a chunk of x + split-K partials + result; x, k!, grids
-    DevBuf queryws;              // probability queries at many steps (blhip_query.hpp): program, tables, B's columns, the steps of a chunk + partials + result
+    DevBuf queryws;              // parser queries at many steps, every call uploads all it reads: probabilities (blhip_query.hpp): program, tables, B's columns, the steps of a
+                                 // chunk + partials + result; distributions (blhip_bins.hpp): the order of the map, the steps of a chunk + partials + result
     DevBuf accpart;              // partial accumulators of the fused fold (one per launch slot of the chain-resident kernel)
     // The partial accumulators are CARRIED from batch to batch of one blhip_fit call (round 6): the batches' weights share the reference of
     // the first one, the slots go into the average posterior once, after the call's last batch (fold_parts_kernel read 8 + 2 sequences of

@@ -136,7 +136,13 @@ class DevicePosterior:
             return self._predictive
         if name == 'query' and hasattr(self.__dict__.get('engine'), 'posterior_query'):      # (the same for the parser's vector of time stamps)
             return self._query
+        if name == 'bins' and hasattr(self.__dict__.get('engine'), 'posterior_bins'):        # (and for its distribution queries)
+            return self._bins
         raise AttributeError(name)
+
+    def _bins(self, steps, bin, n_bins):
+        """The rows `steps` of this sequence summed over the cells of every bin on the device (HipEngine.posterior_bins)."""
+        return self.engine.posterior_bins(self.source, self.chain, steps, bin, n_bins)
 
     def _query(self, steps, ops, consts, relation, marginal, **spaces):
         """Probabilities of a parser query at the rows `steps` of this sequence, summed on the device (HipEngine.posterior_query)."""
@@ -662,6 +668,32 @@ class HipEngine:
         if rc < 0:
             raise BackendError('query_plan: bad arguments')
         plan = dict(zip(('slab', 'n_slabs', 'steps_per_chunk', 'n_chunks', 'workspace_bytes', 'min_budget_bytes'), [int(v) for v in out]))
+        return plan if rc == 0 else None
+
+    def posterior_bins(self, source, chain, steps, bin, n_bins):
+        """(len(steps), n_bins): out[s][b] = the sum of row steps[s] of a device-resident sequence over the cells c with bin[c] == b
+        (blhip_posterior_bins, include/blhip.h).  bin: int32 per cell of the grid, -1 leaves the cell out."""
+        steps = np.ascontiguousarray(steps, dtype=np.int64).ravel()
+        bin = np.ascontiguousarray(bin, dtype=np.int32).ravel()
+        out = np.empty((steps.size, max(int(n_bins), 0)))
+        self._check(self.lib.blhip_posterior_bins(self.ctx, int(source), int(chain), steps.ctypes.data_as(C.POINTER(C.c_int64)), steps.size,
+                                                  bin.ctypes.data_as(C.POINTER(C.c_int32)), bin.size, int(n_bins), _abi.dptr(out)))
+        return out
+
+    @staticmethod
+    def bins_plan(G, n_bins, n_steps, bin=None, budget=float(1 << 62)):
+        """blhip_host_bins_plan as a dict (no GPU needed); None for a budget below the plan's minimum.  bin: the map, or None for the shape
+        alone (slab, sb)."""
+        out = (C.c_int64 * 12)()
+        if bin is not None:
+            bin = np.ascontiguousarray(bin, dtype=np.int32).ravel()
+            if bin.size != int(G):
+                raise BackendError('bins_plan: the map has %d cells, G = %d' % (bin.size, int(G)))
+        rc = _abi.load().blhip_host_bins_plan(None if bin is None else bin.ctypes.data_as(C.POINTER(C.c_int32)), int(G), int(n_bins), int(n_steps), float(budget), out)
+        if rc < 0:
+            raise BackendError('bins_plan: bad arguments')
+        plan = dict(zip(('slab', 'n_slabs', 'sb', 'gw', 'n_runs', 'n_groups', 'table_bytes', 'steps_per_chunk', 'n_chunks', 'workspace_bytes',
+                         'min_budget_bytes', 'lds_bytes'), [int(v) for v in out]))
         return plan if rc == 0 else None
 
     def release_posterior(self, owner=None):

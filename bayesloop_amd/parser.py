@@ -28,7 +28,8 @@ Added: ``t='all'`` or a list / tuple / 1-D array of time stamps evaluates a quer
 (``[P('rho < 0.', t=t, silent=True) for t in range(1, 389)]``, ``P('(mu - ' + str(mu0[t]) + ')/sigma > 1', t=t, silent=True)``).
 Entry i of the result is by definition ``P(query, t=t[i], silent=True)``.  A probability query whose plan has one or two index
 spaces is summed on the GPU while the posterior sequence lives there (the plan: further down; the kernels:
-bayesloop_amd/csrc/blhip_query.hpp); every other query is the loop over the scalar call.
+bayesloop_amd/csrc/blhip_query.hpp); a distribution query over the parameters of one study is binned once on the host and summed per bin
+on the GPU (the plan: at the end of this file; the kernels: bayesloop_amd/csrc/blhip_bins.hpp); every other query is the loop over the scalar call.
 """
 from __future__ import annotations
 
@@ -328,17 +329,9 @@ class Parser:
                 print('P({}) = {}'.format(query, p))
             return p
 
-        values = values.copy()
-        values[np.isinf(values)] = np.nan
-        dmin, dmax = np.nanmin(values), np.nanmax(values)
-        gap = np.nanmax(np.diff(np.sort(values)))                               # bin size = largest gap between two derived values
-        n_bins = int((dmax - dmin) / gap)
-        bins = np.linspace(dmin, dmax, n_bins)
+        n_bins, bins, index, ok = _binning(values)
         if not silent:
             print('+ Computing distribution: {}'.format(query))
-        # probabilities of the half-open bins [lower, upper), labelled by their upper edge (:408-418)
-        index = np.searchsorted(bins, values, side='right') - 1
-        ok = ~np.isnan(values) & (index >= 0) & (index < n_bins - 1)
         binned = np.bincount(index[ok], weights=prob[ok], minlength=max(n_bins - 1, 0))[:max(n_bins - 1, 0)]
         return bins[:-1] + (bins[1] - bins[0]), binned
 
@@ -375,6 +368,12 @@ class Parser:
         stamps = self._stamps(t)
         return _plan(self, query, stamps, self._series(series, len(stamps)), pair_max)
 
+    def planDistribution(self, query, t='all', series=None):
+        """The plan of a distribution query (no relation) with a vector of time stamps (:class:`DistributionPlan`); ``plan.reason`` says why
+        a query stays on the host loop (None: the device takes it if the sequence of ``plan.study`` is resident there)."""
+        stamps = self._stamps(t)
+        return _plan_distribution(self, query, stamps, self._series(series, len(stamps)))
+
     def _call_many(self, query, t, silent, series):
         stamps = self._stamps(t)
         series = self._series(series, len(stamps))
@@ -382,6 +381,8 @@ class Parser:
         out = None
         if relational and len(stamps) > 0:
             out = self._device_query(query, stamps, series)
+        elif not relational and len(stamps) >= DIST_MIN_STAMPS:
+            out = self._device_distribution(query, stamps, series)
         if out is None:
             out = self._loop(query, stamps, series)
             if relational:
@@ -413,6 +414,43 @@ class Parser:
         if pending is None or not hasattr(pending, 'query') or list(pending.grid_size) != [len(m) for m in plan.marginal]:
             return None
         return pending.query(plan.steps, plan.ops, plan.consts, plan.relation, plan.marginal, **plan.spaces_kwargs())
+
+    def _device_distribution(self, query, stamps, series):
+        """The (bin labels, probabilities) of every time stamp with the sums from the device, or None: the plan does not fit it, the
+        study's sequence is not resident there, the engine has no such path (option parser_device = 0, the test doubles) -- or anything at
+        all went wrong while planning (the loop raises what the scalar call raises)."""
+        try:
+            candidates = [getattr(s, '_posterior_pending', None) for s in self.studies]
+            candidates = [p for p in candidates if p is not None and hasattr(p, 'bins')]
+            if not candidates:
+                return None
+            if getattr(getattr(candidates[0], 'engine', None), 'options', {}).get('parser_device', 1.0) == 0:
+                return None
+            plan = _plan_distribution(self, query, stamps, series)
+            if plan.reason is not None:
+                return None
+            pending = getattr(plan.study, '_posterior_pending', None)
+            if pending is None or not hasattr(pending, 'bins') or int(np.prod(pending.grid_size)) != plan.bin.size:
+                return None
+        except Exception:           # noqa: BLE001
+            return None
+        prob = pending.bins(plan.steps, plan.bin, plan.n_bins)
+        return [(plan.labels.copy(), prob[i]) for i in range(len(stamps))]
+
+
+def _binning(values):
+    """The equal bins of a derived quantity (:399-418): ``int((max - min) / largest gap)`` edges from min to max; -> (n_bins, edges, the
+    half-open bin [lower, upper) of every value, which values take part).  The scalar call and the device plan both bin with this."""
+    values = values.copy()
+    values[np.isinf(values)] = np.nan
+    dmin, dmax = np.nanmin(values), np.nanmax(values)
+    gap = np.nanmax(np.diff(np.sort(values)))                               # bin size = largest gap between two derived values
+    n_bins = int((dmax - dmin) / gap)
+    bins = np.linspace(dmin, dmax, n_bins)
+    # probabilities of the half-open bins [lower, upper), labelled by their upper edge (:408-418)
+    index = np.searchsorted(bins, values, side='right') - 1
+    ok = ~np.isnan(values) & (index >= 0) & (index < n_bins - 1)
+    return n_bins, bins, index, ok
 
 
 def _is_vector(t):
@@ -574,17 +612,8 @@ def _plan(parser, query, stamps, series, pair_max=None):
         return QueryPlan(e.reason, e.n_spaces)
 
 
-def _plan_relational(parser, query, parts, stamps, series, pair_max, _abi):
-    n_steps = len(stamps)
-    stamps0 = list(parser.studies[0].formattedTimestamps)
-    first = {}
-    for i, ts in enumerate(stamps0):
-        first.setdefault(ts, i)
-    try:
-        steps = np.array([first[ts] for ts in stamps], dtype=np.int64)
-    except (KeyError, TypeError):
-        steps = np.array([stamps0.index(ts) for ts in stamps], dtype=np.int64)      # (ValueError for an unknown stamp, as the scalar call)
-    # ---- symbolic quantities: what _load(t) gives for a scalar t, without values
+def _symbols(parser):
+    """Symbolic quantities: what _load(t) gives for a scalar t, without values -> (leaves, quantities)"""
     leaves, quantities = {}, {}
     for study in parser.studies:
         online = _is_online(study)
@@ -609,6 +638,25 @@ def _plan_relational(parser, query, parts, stamps, series, pair_max, _abi):
                 space = ('hyper', id(study), 0)
                 leaves[name] = dict(space=space, study=study, model=None, values=np.asarray(grid, dtype=float)[:, k])
                 quantities[name] = _Sym(('leaf', name), space, name, 'hyper', study, None)
+    return leaves, quantities
+
+
+def _step_indices(parser, stamps):
+    """The rows of the time stamps: their first places among the stamps of the first study, the rule for t (:291)"""
+    stamps0 = list(parser.studies[0].formattedTimestamps)
+    first = {}
+    for i, ts in enumerate(stamps0):
+        first.setdefault(ts, i)
+    try:
+        return np.array([first[ts] for ts in stamps], dtype=np.int64)
+    except (KeyError, TypeError):
+        return np.array([stamps0.index(ts) for ts in stamps], dtype=np.int64)       # (ValueError for an unknown stamp, as the scalar call)
+
+
+def _plan_relational(parser, query, parts, stamps, series, pair_max, _abi):
+    n_steps = len(stamps)
+    steps = _step_indices(parser, stamps)
+    leaves, quantities = _symbols(parser)
     # ---- the expression, walked once
     planner = _Planner(parser)
     reduced = '-1*(' + parts[1] + ')+' + parts[0]
@@ -741,6 +789,75 @@ def _plan_relational(parser, query, parts, stamps, series, pair_max, _abi):
         else:
             d = np.asarray(B.hyperParameterDistribution, dtype=float)
             plan.b_prob, plan.b_const = (d / d.sum()).reshape(1, n_b), True
+    return plan
+
+
+# ---- the plan of a distribution query at many time stamps ------------------------------------------------------------------------------------
+# A query without a relation over the parameters of ONE study is element-wise arithmetic on that study's grid: its values, the bins of the
+# scalar call and the bin of every cell are functions of the grid alone, only the probabilities change with the time stamp.  The plan bins the
+# grid ONCE -- with the scalar call's own host arithmetic (_load at the first stamp, _expression, _binning): the bin of a cell is decided by
+# comparisons of values, so they never come from the device interpreter -- and the device sums every selected row of the sequence over the
+# cells of each bin (bayesloop_amd/csrc/blhip_bins.hpp).  Two spaces, hyper-parameters, "@" and series (the bins would change with the step) stay
+# on the loop over the scalar call, and so does every query the scalar call raises on: the loop raises it.
+# fewest time stamps the device path takes, measured (profiles/parser_bins_notes.md): the plan is one scalar call's host work (its _load, its
+# values, its sort) plus the order of the map and two launches, so at 1 stamp the loop was 1.2 to 2.3 times faster at every size, at 2 stamps
+# still faster on grids of 50 and 1000 cells (the device 0.88 and 0.94 of the loop's speed) and slower on 100 x 100 and 512 x 512 cells; from 3
+# stamps on the device was faster everywhere (1.3 to 2.7 times, 2.2 to 8.1 times at 8) -- fewer than 3 stamps: the loop
+DIST_MIN_STAMPS = 3
+
+
+class DistributionPlan:
+    """What a vector-t distribution query needs from the device.  reason: None, or why the query stays on the host loop; study: whose
+    parameter grid the query lives on; steps: rows of its sequence; labels: the bin labels of the scalar call (upper edges); bin: int32 per
+    cell of the grid, the bin of the cell or -1 where the scalar call leaves it out; n_bins = len(labels)."""
+
+    def __init__(self, reason=None):
+        self.reason = reason
+        self.study = self.steps = self.labels = self.bin = None
+        self.n_bins = 0
+
+
+def _plan_distribution(parser, query, stamps, series):
+    if len(re.split('>=|<=|==|>|<', query)) != 1:
+        return DistributionPlan('no distribution query')
+    if series:
+        return DistributionPlan('a series: the bins change with the time stamp')
+    if '@' in query:
+        return DistributionPlan('a time stamp pinned with "@"')
+    if len(stamps) == 0:
+        return DistributionPlan('no time stamps')
+    try:
+        steps = _step_indices(parser, stamps)
+        _, quantities = _symbols(parser)
+        planner = _Planner(parser)
+        tokens = _tokenize(query, set(parser.names), parser.functions)
+        derived, pos = planner._expression(tokens, 0, quantities)
+        if pos != len(tokens) or not isinstance(derived, _Sym):
+            raise ConfigurationError('Cannot parse query.')
+    except _NoPlan as e:
+        return DistributionPlan(e.reason)
+    except Exception as e:          # noqa: BLE001 -- whatever it is, the loop over the scalar call raises it
+        return DistributionPlan('the scalar call raises {}: {}'.format(type(e).__name__, e))
+    if derived.space == 'pair':
+        return DistributionPlan('two index spaces: the values are an outer product')
+    if derived.space[0] != 'param':
+        return DistributionPlan('hyper-parameters: no sequence of theirs is resident on the device')
+    A = next(s for s in parser.studies if id(s) == derived.space[1])
+    if steps.min() < 0 or steps.max() >= len(A.formattedTimestamps):
+        return DistributionPlan('a time stamp of the first study beyond the sequence of the study queried')
+    try:
+        # the values of the scalar call at the first stamp, by its own arithmetic
+        value, _ = Parser._expression(parser, tokens, 0, parser._load(stamps[0]))
+        with np.errstate(all='ignore'):
+            n_bins, bins, index, ok = _binning(value.values)
+        labels = bins[:-1] + (bins[1] - bins[0])
+    except Exception as e:          # noqa: BLE001
+        return DistributionPlan('the scalar call raises {}: {}'.format(type(e).__name__, e))
+    if index.size != int(np.prod(A.gridSize)) or n_bins - 1 != labels.size:
+        return DistributionPlan('values that do not live on the grid of the study')
+    plan = DistributionPlan()
+    plan.study, plan.steps, plan.labels, plan.n_bins = A, steps, labels, int(labels.size)
+    plan.bin = np.where(ok, index, -1).astype(np.int32)
     return plan
 
 

@@ -10,7 +10,8 @@
  *                        (+ the per-hyper-point loop of   bayesloop/core.py:1349-1366 / 1473-1489 when n_chains > 1)
  *   blhip_accum_*        the evidence-weighted average    bayesloop/core.py:1295, 1362-1366, 1339, 1375-1382, 1416-1419
  *   blhip_posterior_*    the posteriorSequence attribute  bayesloop/core.py:356, 408, 436-441
- *   blhip_carry_*        OnlineStudy.step                 bayesloop/core.py:2062-2226 (with BLHIP_RESUME / BLHIP_CARRY fits)
+ *   blhip_posterior_query / _bins   Parser.__call__ over a loop of time stamps   bayesloop/parser.py:256-440 (probabilities; :399-418 distributions)
+ *   blhip_carry_*        OnlineStudy.step                bayesloop/core.py:2062-2226 (with BLHIP_RESUME / BLHIP_CARRY fits)
  *   blhip_comm_*         HyperStudy.fit(nJobs > 1):       bayesloop/core.py:1307-1340 (pool.map fan-out and the merge of the
  *                        sub-studies), _parallelFit       bayesloop/core.py:1443-1495 -- one process per GPU, RCCL over xGMI
  *
@@ -42,7 +43,7 @@
 extern "C" {
 #endif
 
-#define BLHIP_ABI_VERSION 12
+#define BLHIP_ABI_VERSION 13
 
 typedef struct blhip_ctx blhip_ctx;
 
@@ -520,6 +521,29 @@ int blhip_host_query_check(const blhip_query *query, int64_t n_steps, char *err,
  * (c + 1) * spc)).  Returns 0; -1 for bad arguments; 1 for a budget below the minimum (plan_out[5] is still written). */
 int blhip_host_query_plan(int64_t G, int64_t n_steps, int64_t n_series, int64_t n_b, int b_const, int64_t fixed_bytes, double budget,
                           int64_t *plan_out);
+
+/* ---- derived distributions at many time steps (ABI v13; bl.Parser / Study.eval WITHOUT a relation and with a vector of time stamps,
+ *      bayesloop/parser.py:399-418: the binned distribution of a derived quantity) ----------------------------------------------------
+ *   host_out[s][b] = sum of sequence[steps[s]][c] over the cells c with bin[c] == b          (n_steps, n_bins), C order
+ * bin (G): the bin of every cell of the sequence's grid, -1 = the cell is left out; the caller bins the grid (for a query over the
+ * parameters of one study the map does not depend on the step).  source / chain: as blhip_posterior_marginal.  steps: rows of the
+ * sequence in any order, repeats allowed.  n_bins: 1 .. 2^31 - 1.  No floating-point atomics: the order of the additions is fixed by
+ * the map (bayesloop_amd/csrc/blhip_bins.hpp), two calls on the same inputs return the same bits, and so does a call the budget cuts
+ * into chunks.  The order of the map, the steps of a chunk, the partial sums and the result live in a workspace of the context within
+ * 0.9 * option mem_budget_bytes (blhip_host_bins_plan); a call that does not fit is cut along the steps.
+ * Validation happens on the host before anything is launched (blhip_host_bins_check: the checks of the map without a context).
+ * Errors (return -1, blhip_last_error; the context stays usable): no posterior kept / chain out of range / accumulator not finalised, a
+ * step out of range, a map whose length does not match the sequence, a bin outside -1 .. n_bins - 1, a NULL pointer, a budget below
+ * the plan's minimum. */
+int blhip_posterior_bins(blhip_ctx *ctx, int source, int64_t chain, const int64_t *steps, int64_t n_steps, const int32_t *bin, int64_t G,
+                         int64_t n_bins, double *host_out);
+/* The checks of a map, host-only (no GPU, no context): 0, or -1 with the message in err. */
+int blhip_host_bins_check(const int32_t *bin, int64_t G, int64_t n_bins, char *err, int errlen);
+/* The plan of such a call, host-only.  bin: the map, or NULL for the shape alone (no runs, no tables).  plan_out (12 values): cells per
+ * slab, slabs, steps per block, group width chosen for the map, runs (pairs of a slab and a bin it touches), groups, bytes of the
+ * map's tables, steps per chunk, chunks, workspace bytes (<= budget), the smallest budget accepted, bytes of LDS per block.
+ * Returns 0; -1 for bad arguments; 1 for a budget below the minimum (plan_out is still written). */
+int blhip_host_bins_plan(const int32_t *bin, int64_t G, int64_t n_bins, int64_t n_steps, double budget, int64_t *plan_out);
 
 #ifdef __cplusplus
 }
