@@ -185,7 +185,7 @@ int backward_pass(BatchRun &R, const int64_t K, BatchPath path, const PassPlan &
     HIPCHECK(hipEventRecord(ev[2], st));
     double *d_psB = ctx->psumB.as<double>();
     launch_pass(R, path, true, K, d_psB);
-    double *redB = R.redB = end_pass(ctx, st, ev[3], T * B * NRED, P.nblk, d_psB, ctx->redB, ctx->pinB, false);
+    double *redB = R.redB = end_pass(ctx, st, ev[3], T * B * NRED, path == PATH_CHAIN ? R.CR.pass_nblk(true) : P.nblk, d_psB, ctx->redB, ctx->pinB, false);
     E.mark("backward pass queued");
     if (P.late_fb) {
         if (P.late_copy) HIPCHECK(hipEventSynchronize(ctx->cev[1]));
@@ -849,7 +849,7 @@ int blhip_set_option(blhip_ctx *ctx, const char *key, double value) {
     // (a key the library never reads is an error, not a silent no-op: an A/B run over a removed option measured nothing -- ADVICE r05)
     static const char *const known[] = {
         "bins_gw", "bins_sb", "bins_slab", "carry_partials", "chain1d", "chain1d_clamp", "chain1d_long", "chain1d_shift", "chain_ax1", "chain_clamp", "chain_depad", "chain_prof", "chain_resident", "chain_resident_lag",
-        "chain_force_fail_batch", "chain_force_fail_stage", "chain_nd", "chain_table", "chain_wide", "comm_reduce_mode", "fast", "fast_S", "fold2", "fold2_cp", "fold_force_fail_batch", "fuse1d", "fuse_accumulate", "late_sums", "lik_program", "max_batch",
+        "chain_force_fail_batch", "chain_force_fail_stage", "chain_nd", "chain_table", "chain_wide", "comm_reduce_mode", "fast", "fast_S", "fold2", "fold2_cp", "fold4", "fold4_min_chains", "fold_force_fail_batch", "fuse1d", "fuse_accumulate", "late_sums", "lik_program", "max_batch",
         "mem_budget_bytes", "mfma", "mfma_S", "mfma_h", "mfma_h_max_cells", "online_block", "parser_device", "parser_pair_max", "peer_copy_mode", "persist1d", "predictive", "quiet", "recurrence", "resident",
         "resident_force_abort", "resident_lag", "resident_probe", "resident_probe_force_busy", "resident_probe_interval_s", "resident_probe_timeout_s",
         "resident_table", "resident_timeout_s", "share_prefix", "short_first_batch", "skip_prefix", "trace", "wide_h",

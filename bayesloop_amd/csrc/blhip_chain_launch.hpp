@@ -49,6 +49,10 @@ void chain_clamp_ntw1(hipStream_t s, const blc::ClampParams &Q, int nk, bool bwd
 void chain_clamp_ntw2(hipStream_t s, const blc::ClampParams &Q, int nk, bool bwd, bool store);
 void chain_clamp_ntw4(hipStream_t s, const blc::ClampParams &Q, int nk, bool bwd, bool store);
 
-constexpr int N_SLICES = 25;      // BLC_TU = 1 .. N_SLICES (blhip_chain_tu.hip)
+// ... the two-chain fold kernel's flavour with FOUR chains per block (ring lengths 6 .. 24, exact geometries; 20 kernels per slice)
+void fold4_ntw12(hipStream_t s, const blc::ChainParams &Q, int nk, int ntw);
+void fold4_ntw34(hipStream_t s, const blc::ChainParams &Q, int nk, int ntw);
+
+constexpr int N_SLICES = 27;      // BLC_TU = 1 .. N_SLICES (blhip_chain_tu.hip)
 
 }   // namespace blcl

@@ -134,6 +134,8 @@ struct ChainOptions {
     bool fuse_accumulate = true, fold2 = true, fold2_cp = true, chain_depad = true, share_prefix = true, skip_prefix = true;
     int chain_resident_lag = 4;                    // clamped to 2 .. blc::MAXLAG (lag 1 would need the sum of the step in flight)
     bool carry_partials = true;
+    bool fold4 = true;                             // four chains per accumulator cell (blc::chain_fold2_kernel QUAD) where chain_fold_plan admits it; 0: the two-chain kernel
+    int fold4_min_chains = 32;                     // ... for batches of at least so many chains
 };
 
 // plain facts about the batch: no pointer into device memory, no library state
@@ -221,9 +223,15 @@ constexpr double CHAIN_AXLIK_MAX_BYTES = 8.0e9;        // largest likelihood tab
 struct ChainFold {
     bool post_private = false;                     // ChainRun::post_private / fused / fold2 / round_start_b / round_nk_b / slots_used
     bool fused = false, fold2 = false;
+    bool fold4 = false;                            // ... with FOUR chains per block (strips of 8 columns: sequences and partial accumulators in [t][strip of 8][row][8])
     std::vector<int> round_start_b, round_nk_b;
     int slots_used = 0;
 };
+
+// the four-chain flavour of the two-chain fold kernel: ring lengths 6 .. 24 (radius <= 40: one band entry per lane fits the LDS beside the
+// buffers), strips of 8 columns -- one granule per lane of the scale wave, one block per strip and chain quad
+constexpr int FOLD4_NK_MIN = 6, FOLD4_NK_MAX = 24;
+inline bool fold4_geometry(int strips16, int cus) { return 2 * strips16 <= blc::MAX_STRIPS && 2 * strips16 <= cus; }
 
 // change-point batches: the two passes restart at the same places (backward step t restarts <=> forward step t + 1 does: unit-spaced
 // time stamps, transitionModels.py:316-317)
@@ -263,6 +271,28 @@ inline ChainFold chain_fold_plan(const ChainFacts &F, const ChainOptions &O, con
         f.round_start_b.push_back((int)F.B);
         f.slots_used = (int)std::min<int64_t>(cp.cpr, (F.B + 1) / 2);
     }
+    // FOUR chains per accumulator cell (8 + 16 / 4 = 12 B per chain, cell and step): filtering batches without restarts on an exact geometry,
+    // every round's ring within 6 .. 24 -- one round beyond it and the whole batch keeps the two-chain kernel (one layout per batch)
+    if (f.fold2 && O.fold4 && !cp.pad && !cp.has_reset && prog.LW0 > 0 && F.B >= O.fold4_min_chains && fold4_geometry(cp.strips, F.cus())) {
+        const int quads = F.cus() / (2 * cp.strips), per = 4 * quads;
+        std::vector<int> rs, rnk;
+        bool ok = true;
+        for (int64_t s0 = 0; s0 < F.B && ok; s0 += per) {
+            const int64_t s1 = std::min<int64_t>(F.B, s0 + per);
+            const int tp = cp.tap_id[cp.order[s1 - 1]];                   // (sorted by radius: the last chain of the round is its widest)
+            const int r0 = std::max(4, ((tp >= 0 ? taps.lw[tp] : 0) + 3) / 4 * 4);
+            const int nk = (blc::TM + 2 * r0) / 4;
+            ok = nk >= FOLD4_NK_MIN && nk <= FOLD4_NK_MAX;
+            rs.push_back((int)s0);
+            rnk.push_back(nk);
+        }
+        if (ok) {
+            rs.push_back((int)F.B);
+            f.fold4 = true;
+            f.round_start_b = std::move(rs); f.round_nk_b = std::move(rnk);
+            f.slots_used = (int)std::min<int64_t>(quads, (F.B + 3) / 4);
+        }
+    }
     return f;
 }
 
@@ -277,7 +307,7 @@ inline double chain_depad_bytes(const ChainFacts &F, long long Gk) { return (dou
 // of the padded layout afterwards (<= 512 rows: every flavour has a padded storing kernel; 1024 rows: forward passes only).  -> depad;
 // false: the batch keeps the launch-per-step kernels.  Either way nothing folds in the backward kernel.
 inline bool chain_padding_rule(const ChainFacts &F, const ChainOptions &O, const ChainResPlan &cp, bool admitted, ChainFold &f) {
-    f.fused = false; f.fold2 = false;
+    f.fused = false; f.fold2 = false; f.fold4 = false;
     return O.chain_depad && (cp.ntw <= 4 || !F.full) && admitted;
 }
 
@@ -359,6 +389,7 @@ struct ChainLaunch {
     int nslots = 0;                                // chains of the launch
     long long Gk = 0; int64_t T = 0;
     bool bwd = false, fold_now = false, two = false;       // a backward launch; ... that folds; ... with two chains per block
+    bool quad = false;                                     // ... with four (the QUAD flavour: `two` holds as well)
     bool ax1 = false, tab = false, evidence_only = false;
     int nk = 4;                                    // ring length (4: no stencil)
     bool share_prefix = false, skip_prefix = false;
@@ -369,13 +400,13 @@ inline int chain_band_radius(int nk) { return (4 * nk - blc::TM) / 2; }
 
 // HBM: only what the fit keeps -- forward the stored state (8 B; nothing for evidence-only fits), backward the stored state in + the
 // posterior out (16 B) or + the read-modify-write of the partial accumulator (24 B; shared by the two chains of a block of the two-chain
-// fold kernel: 8 + 16 / 2 = 16 B).  epi_flop / band_flop: per cell, the launch's epilogue and one band product of radius
+// fold kernel: 8 + 16 / 2 = 16 B; by four chains of its QUAD flavour: 8 + 16 / 4 = 12 B).  epi_flop / band_flop: per cell, the launch's epilogue and one band product of radius
 // chain_band_radius(nk) (blhip_book.hpp: EPI_FWD_FLOP / EPI_BWD_FLOP, band_stencil_flop)
 inline ChainLaunchCost chain_launch_cost(const ChainLaunch &L, double epi_flop, double band_flop) {
     double cells = (double)L.nslots * L.Gk * L.T;
     if (!L.bwd && L.skip_prefix)               // (chain-steps the forward pass does not run)
         for (int q = 0; q < L.nslots; ++q) cells -= (double)L.tshare[L.chains[q]] * L.Gk;
-    double bytes = L.bwd ? (L.fold_now ? (L.two ? 8.0 + 16.0 * ((L.nslots + 1) / 2) / (double)L.nslots : 24.0) : 16.0) : (L.evidence_only ? 0.0 : 8.0);
+    double bytes = L.bwd ? (L.fold_now ? (L.quad ? 8.0 + 16.0 * ((L.nslots + 3) / 4) / (double)L.nslots : L.two ? 8.0 + 16.0 * ((L.nslots + 1) / 2) / (double)L.nslots : 24.0) : 16.0) : (L.evidence_only ? 0.0 : 8.0);
     // (both-axes kernels: the transposing exchange of a step leaves the XCD's L2 as well -- 8 written + 8 read;
     //  with the blocks of a chain on one XCD the reads mostly hit that L2: the PMC counters say what really moves)
     if (L.ax1) bytes += 16.0;

@@ -10,7 +10,7 @@
 #if BLC_TU >= 19 && BLC_TU <= 22
 #include "blhip_chainax.hpp"      // (only the slices that hold its kernels: an edit of that header recompiles three units)
 #endif
-#if BLC_TU >= 23
+#if BLC_TU >= 23 && BLC_TU <= 25
 #include "blhip_chainclamp.hpp"   // (the clamp flavour of the one-axis kernels: three slices, one per geometry)
 #endif
 
@@ -133,6 +133,31 @@ void launch_fold2_w(hipStream_t s, const blc::ChainParams &Q, int nk, bool pad) 
 }
 #undef BLC_CASE
 
+// ... its flavour with four chains per block: blocks of (chain quad, strip of 8 columns)
+template <int NK, int NTW>
+void launch_fold4_k(hipStream_t s, const blc::ChainParams &Q) {
+    const size_t lds = blc::lds_doubles_fold4<NK, NTW>() * sizeof(double);
+    const dim3 grid((unsigned)(((Q.nslots + 3) / 4) * Q.strips));
+    arm_kernel(reinterpret_cast<const void *>(&blc::chain_fold2_kernel<NK, NTW, false, true>));
+    BL_LAUNCH((blc::chain_fold2_kernel<NK, NTW, false, true>), grid, dim3(blc::NT), lds, s, Q);
+}
+template <int NTW>
+void launch_fold4_w(hipStream_t s, const blc::ChainParams &Q, int nk) {
+    switch (nk) {
+        case 6: launch_fold4_k<6, NTW>(s, Q); break;
+        case 8: launch_fold4_k<8, NTW>(s, Q); break;
+        case 10: launch_fold4_k<10, NTW>(s, Q); break;
+        case 12: launch_fold4_k<12, NTW>(s, Q); break;
+        case 14: launch_fold4_k<14, NTW>(s, Q); break;
+        case 16: launch_fold4_k<16, NTW>(s, Q); break;
+        case 18: launch_fold4_k<18, NTW>(s, Q); break;
+        case 20: launch_fold4_k<20, NTW>(s, Q); break;
+        case 22: launch_fold4_k<22, NTW>(s, Q); break;
+        case 24: launch_fold4_k<24, NTW>(s, Q); break;
+        default: fail("internal: four-chain fold kernel with %d band blocks, %d tiles per wave", nk, NTW);
+    }
+}
+
 #if BLC_TU >= 19 && BLC_TU <= 22
 // walks on both parameters: forward (stored / evidence-only), backward (stored / folded); ring lengths 8 .. 24 in steps of 4
 template <int NK, int NTW, bool PAD>
@@ -156,7 +181,7 @@ void launch_w_ax(hipStream_t s, const blc::ChainParams &Q, int nk, bool bwd, boo
 }
 #endif
 
-#if BLC_TU >= 23
+#if BLC_TU >= 23 && BLC_TU <= 25
 // RegimeSwitch inside the one-axis kernels (blc::chain_clamp_kernel): forward (evidence-only / storing), backward (storing); ring lengths 4
 // (no stencil) and 8 .. 24 in steps of 4; 128, 256 and 512 rows (a 384-row grid runs padded inside 512)
 #define launch_clamp_fn(K, s, Q, lds) (blreg::hit<&K>(), launch_clamp_ptr(&K, s, Q, lds))
@@ -297,6 +322,18 @@ void chain_clamp_ntw1(hipStream_t s, const blc::ClampParams &Q, int nk, bool bwd
 void chain_clamp_ntw2(hipStream_t s, const blc::ClampParams &Q, int nk, bool bwd, bool store) { launch_w_clamp<2>(s, Q, nk, bwd, store); }
 #elif BLC_TU == 25
 void chain_clamp_ntw4(hipStream_t s, const blc::ClampParams &Q, int nk, bool bwd, bool store) { launch_w_clamp<4>(s, Q, nk, bwd, store); }
+#elif BLC_TU == 26
+void fold4_ntw12(hipStream_t s, const blc::ChainParams &Q, int nk, int ntw) {
+    if (ntw == 2) launch_fold4_w<2>(s, Q, nk);
+    else if (ntw == 1) launch_fold4_w<1>(s, Q, nk);
+    else fail("internal: four-chain fold kernel with %d tiles per wave", ntw);
+}
+#elif BLC_TU == 27
+void fold4_ntw34(hipStream_t s, const blc::ChainParams &Q, int nk, int ntw) {
+    if (ntw == 4) launch_fold4_w<4>(s, Q, nk);
+    else if (ntw == 3) launch_fold4_w<3>(s, Q, nk);
+    else fail("internal: four-chain fold kernel with %d tiles per wave", ntw);
+}
 #else
 #error "BLC_TU out of range"
 #endif

@@ -313,6 +313,9 @@ __device__ __forceinline__ double nan_if(bool nan, double x) {
 #ifndef BLC_FOLD_HOIST_MAX
 #define BLC_FOLD_HOIST_MAX 20
 #endif
+#ifndef BLC_FOLD4_HOIST_MAX
+#define BLC_FOLD4_HOIST_MAX 14      // (the four-chain flavour holds more per-lane state: beyond ring length 14 the band's registers spill)
+#endif
 typedef const double __attribute__((address_space(3))) *band_cp;
 // (Bv: a ring of NR >= OFF + NK entries, the tile's window begins at entry OFF -- compile-time, so the entries stay registers)
 // (AST: doubles between the tables of two shifts.  64 = one entry per lane; 16 = one entry per (k, i) pair, read by the four lanes
@@ -506,14 +509,23 @@ __global__ __launch_bounds__(NT, 1) void chain_kernel(const ChainParams P) {
     const double g1 = P.m1[gjc];
     const double cA = TAB ? 0.0 : P.colA[gjc], cB = TAB ? 0.0 : P.colB[gjc];
     double *const pchain = P.post + (long long)b * P.post_stride;
-    const unsigned rowx8 = P.strip_major ? (unsigned)WCOL * 8u : (unsigned)P.n1 * 8u;                        // bytes between rows
+    // (strip_major 2: the strip's two halves of 8 columns are strips of their own, n0 x 64 bytes each -- the second one begins n0 * 64 bytes
+    //  behind the first; the strip's first byte is where layout 1 has it)
+    const unsigned rowx8 = P.strip_major == 2 ? 8u * 8u : (P.strip_major ? (unsigned)WCOL * 8u : (unsigned)P.n1 * 8u);      // bytes between rows
     const unsigned strip0 = P.strip_major ? (unsigned)tj * (unsigned)(P.n0 * WCOL * 8) : (unsigned)tj * (unsigned)(WCOL * 8);   // the strip's first byte
+    // the lane's column inside the strip, in bytes, + the strip's first byte: ONE value for all the step's cells (layouts 0 and 1: 8 bytes per column)
+    const unsigned lane_b = strip0 + (unsigned)(lane & 7) * 8u + (unsigned)(lane & 8) * (P.strip_major == 2 ? (unsigned)P.n0 * 8u : 8u);
     const int row0 = wv * (NTW * TM);
     // The lane's coordinates are re-derived from a laundered lane id wherever they are used: carried through the time loop, every
     // index expression of the step (ring rows, LDS offsets, byte offsets of the 4 NTW cells) is loop-invariant and the optimiser
     // parks it in a VGPR -- more than a hundred of them (the time-resident single-chain kernel spilled for the same reason).
     auto fresh_lane = [&]() { int l = lane; asm volatile("" : "+v"(l)); return l; };
-    auto cell_off = [&](int l, int it, int r) { return __umul24(row0 + it * TM + (l >> 4) + 4 * r, rowx8) + strip0 + (unsigned)(l & 15) * 8u; };
+    // (the no-stencil kernels never see layout 2 -- the four-chain fold kernel filters -- and keep the lane's column re-derived per use: their
+    //  step is a few hundred cycles and sensitive to every register carried through the time loop)
+    auto cell_off = [&](int l, int it, int r) {
+        if constexpr (!FILTER) return __umul24(row0 + it * TM + (l >> 4) + 4 * r, rowx8) + strip0 + (unsigned)(l & 15) * 8u;
+        else return __umul24(row0 + it * TM + (l >> 4) + 4 * r, rowx8) + lane_b;
+    };
 
     const int kb = (!BWD && !FILTER && P.skip_prefix) ? tsh : 0;      // the first step this chain computes (see ChainParams::skip_prefix)
     if (kb >= P.T) return;                                              // (a chain without a restart that is not the provider: nothing of its own)
@@ -990,6 +1002,391 @@ __global__ __launch_bounds__(NT, 1) void chain_kernel(const ChainParams P) {
 // spins -- is chain_kernel<NK, NTW, true, false>'s.  Launched for rounds of 2 x (CUs / strips) chains when the batch folds.
 template <int NK, int NTW>
 constexpr size_t lds_doubles_fold2() { return (size_t)2 * NW * NTW * TM * WCOL + 2 * NK * (NK > 24 ? 16 : 64) + NW * NTW * TM + 2 * 2 * NW * 4 * 3 + 4 * NSLOT + 8; }      // (NK = 4: the band tables stay unused)
+
+// ---- ... FOUR chains per accumulator cell (the QUAD flavour of chain_fold2_kernel) ---------------------------------------------------------------
+// v_mfma_f64_4x4x4 multiplies four INDEPENDENT blocks, and with one band entry per lane (AST = 64) each block has its own A operand: blocks
+// 0 - 1 filter 8 grid columns of one chain, blocks 2 - 3 the SAME 8 columns of another.  A block of the launch then owns an 8-column strip of
+// FOUR chains and runs two alternating lane-PAIRS of chains exactly as the two-chain kernel alternates its two chains: lane (g, c) holds
+// chain-half h = c >> 3 and column 8 tj8 + (c & 7) of rows row + g + 4 r; LDS rows stay 16 doubles wide ([2 pairs][N0][2 halves x 8]), ring,
+// products, barriers and register sets are the two-chain kernel's.  The accumulator cell is shared by four chains: 8 + 16 / 4 = 12 B per
+// chain, cell and step.  What differs:
+//  * sequences and partial accumulators in the layout [t][strip of 8][row][8] (ChainParams::strip_major = 2, written by the storing forward
+//    kernel): a wave access is two runs of 256 contiguous bytes;
+//  * everything per chain is a per-LANE value (scale, weight, predicted sum, the sequence's base address): pair j, half h = chain 2 j + h of the
+//    block; the row sums are reductions over 8 lanes; the scale wave prepares two scales per pair-step;
+//  * each lane adds its own chain's weighted posterior to its accumulator registers over the time step's two pair-steps; the last pair-step
+//    adds the two halves across lanes (row_ror:8) and stores the cell once.  The rows of a tile are split between the halves: half h loads
+//    and stores rows 2 h and 2 h + 1 (the other rows' registers start from the zeros buffer), so a cell is read and written by one lane;
+//  * a block at the end of a launch may hold 1 - 3 chains: a missing chain duplicates the block's last one with weight 0 and publishes nothing.
+// Exact geometries of <= 512 rows, ring lengths 6 .. 24, Gaussian likelihood, no restarts (chain_fold_plan: fold4).
+template <int NK, int NTW>
+constexpr size_t lds_doubles_fold4() { return (size_t)2 * NW * NTW * TM * WCOL + 2 * NK * 64 + 4 * 2 * NW * 4 * 3 + 8 * NSLOT + 8; }
+
+template <int NK, int NTW>
+__device__ __forceinline__ void chain_fold4_body(const ChainParams &P) {
+    static_assert(NK >= 6 && NK <= 24 && NTW >= 1 && NTW <= 4, "four chains per block: ring lengths 6 .. 24 on <= 512 rows");
+    constexpr int R0 = (4 * NK - TM) / 2;
+    static_assert(R0 % 4 == 0, "band = 16 + 2 R0 columns, R0 a multiple of 4");
+    constexpr int N0 = NW * NTW * TM;
+    constexpr int XSZ = N0 * WCOL;
+    constexpr int AST = 64;                         // one band entry per lane: the two halves multiply different bands
+    constexpr int HC = WCOL / 2;                    // grid columns per strip
+    constexpr unsigned ROWB = HC * 8u, ROW4B = 4u * ROWB;      // bytes between rows / between a lane's cells (rows 4 r)
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double *const X = lds;                          // [2 pairs][N0][2 halves x 8]   exchange buffers
+    double *const As = X + 2 * XSZ;                 // [2 pairs][NK][64]  A operands
+    double *const red = As + 2 * NK * AST;          // [4 chains][2 parities][NW * 4][3]
+    double *const scal = red + 4 * 2 * NW * 4 * 3;  // [4 chains][NSLOT]
+    double *const iscal = scal + 4 * NSLOT;         // [4 chains][NSLOT]
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int cs4 = blockIdx.x / P.strips, tj = blockIdx.x - cs4 * P.strips;      // (P.strips: strips of 8 columns)
+    const int nch = min(4, P.nslots - 4 * cs4);                   // chains of this block
+    const int npair = (nch + 1) >> 1;
+    int bch[4], lw0[4];
+    long long o0[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        bch[q] = sldi(P.chain_ids, 4 * cs4 + min(q, nch - 1));
+        const int tap = sldi(P.tap_id, bch[q]);
+        lw0[q] = tap >= 0 ? sldi(P.tap_lw, tap) : 0;
+        o0[q] = tap >= 0 ? sldi(P.tap_off, tap) : 0;
+    }
+    const int hl = (lane >> 3) & 1;                 // the lane's chain-half
+    const long long G = (long long)P.n0 * P.n1;
+
+    // first step: the source (uniform) is consumed unfiltered -> identity bands; the chains' bands replace them after step 0
+    for (int e = tid; e < 2 * NK * AST; e += NT) As[e] = band_distance(e % (NK * AST), R0) == 0 ? 1.0 : 0.0;
+    if (tid < 8 * NSLOT) scal[tid] = 1.0;
+    for (int e = tid; e < 2 * XSZ; e += NT) {
+        const int q = e % XSZ, row = q >> 4, col = tj * HC + (q & 7);
+        X[e] = P.src0[(long long)row * P.n1 + col];
+    }
+    const double cA = P.colA[tj * HC + (lane & 7)];
+    const unsigned strip0 = (unsigned)tj * (unsigned)(P.n0 * HC * 8);
+    const int row0 = wv * (NTW * TM);
+    auto fresh_lane = [&]() { int l = lane; asm volatile("" : "+v"(l)); return l; };
+    auto cell_off = [&](int l, int it) { return __umul24(row0 + it * TM + (l >> 4), ROWB) + strip0 + (unsigned)(l & 7) * 8u; };
+
+    const int t_first = P.T - 1;
+    double *const pslot = P.part + (long long)cs4 * P.part_stride;
+    // per pair j: the lane's chain (2 j + h; a missing chain: the block's last one, weight 0), its slot of scal / iscal, its sequence, its rows of P.sfwd
+    int slot_l[2];
+    const double *post_l[2], *sfwd_l[2];
+    double wch[2], inpred[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int q = 2 * j + hl;
+        const int b = hl ? bch[2 * j + 1] : bch[2 * j];
+        slot_l[j] = min(q, nch - 1) * NSLOT;
+        post_l[j] = P.post + (long long)b * P.post_stride;
+        sfwd_l[j] = P.sfwd + (long long)b * P.T;
+        wch[j] = q < nch ? P.wchain[b] : 0.0;
+        inpred[j] = P.infirst[b];
+    }
+    double stt[NTW][4], al[NTW][4], pacc[NTW][4];
+    {
+        const double *p0 = post_l[0] + (long long)t_first * G;
+        const double *a0 = pslot + (long long)t_first * G;
+#pragma unroll
+        for (int it = 0; it < NTW; ++it)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const unsigned off = cell_off(lane, it) + r * ROW4B;
+                al[it][r] = blm::ld32(p0, off);
+                pacc[it][r] = (P.part_fresh || (r >> 1) != hl) ? blm::ld32(P.zeros, off & 4088u) : blm::ld32(a0, off);
+                stt[it][r] = 0.0;
+            }
+    }
+    double sf_next = 1.0;
+    if (wv == SCALE_WAVE || wv == 5 || wv == 0 || wv == NW - 1) __builtin_amdgcn_s_setprio(2);
+    bool dead = false;
+    typedef const double __attribute__((address_space(3))) *lds_cp;
+    unsigned long long gq0[4] = {0ull, 0ull, 0ull, 0ull}, gq1[4] = {0ull, 0ull, 0ull, 0ull};      // [2 j + h]
+    double Sprev[4] = {1.0, 1.0, 1.0, 1.0};
+    double mq = 1.0, iq = 1.0, dn_prev = -1.0;
+    int nq = 0;
+    double a_mE = 1.0, a_mR = 1.0, a_iE = 1.0, a_iR = 1.0;
+    int a_nE = 0, a_nR = 0;
+    // the anchors of the fit's table live on strips of 16 columns: strip tj >> 1, lane column ((tj & 1) << 3) | (c & 7) -- both halves the same
+    const int astrips = P.strips >> 1, atj = tj >> 1;
+    auto anchor_lane = [&](int l) { return (l & 0x30) | ((tj & 1) << 3) | (l & 7); };
+    AnchorEntry anc_next = anchor_load(P.anch, t_first, wv, astrips, atj, anchor_lane(lane));
+    int pend_j = -1, pend_k = 0;
+
+    const LoopParams Q = loop_params(P);
+    // wave 5: block totals of a finished pair-step -> partial sums of the strip + the granules, each chain separately (lanes 0 - 2: half 0, 8 - 10: half 1)
+    auto totals = [&](int j, int k) {
+        const int hh = (lane >> 3) & 1, q = lane & 7, c = 2 * j + hh;
+        if (wv == 5 && lane < 16 && q < 3 && c < nch) {
+            const double *rk = red + (c * 2 + (k & 1)) * (NW * 4 * 3);
+            double tot = 0.0;
+#pragma unroll
+            for (int w = 0; w < NW * 4; ++w) tot += rk[w * 3 + q];
+            const int t = Q.T - 1 - k;
+            const int b = hh ? (j ? bch[3] : bch[1]) : (j ? bch[2] : bch[0]);
+            Q.psum[(((long long)t * Q.B + b) * NRED + q) * Q.nblk + tj] = tot;
+            if (q == 2) {
+                const unsigned long long bits = (unsigned long long)__double_as_longlong(tot);
+                const unsigned long long tag = (unsigned long long)(unsigned)(k + 1) << 32;
+                unsigned long long *gw = Q.gran + ((((long long)(k & (NSLOT - 1)) * Q.nslots + 4 * cs4 + c) * Q.strips + tj) << 1);
+                blr::st_u64(gw, tag | (bits & 0xffffffffull));
+                blr::st_u64(gw + 1, tag | (bits >> 32));
+            }
+        }
+    };
+    __syncthreads();
+
+    const bool scale_wave = wv == SCALE_WAVE;
+    const int nsteps = Q.T * npair;
+#pragma unroll 1
+    for (int cstep = 0; cstep < nsteps; ++cstep) {
+        const int k = npair == 2 ? cstep >> 1 : cstep;
+        const int j = __builtin_amdgcn_readfirstlane(npair == 2 ? cstep & 1 : 0);
+        const int t = Q.T - 1 - k;
+        const int tn = (k + 1 < Q.T) ? t - 1 : t;
+        const int jn = k + 1;
+        double *const pslot_t = pslot + (long long)t * G;
+        double *const pslot_tn = pslot + (long long)tn * G;
+        double *const Xj = X + j * XSZ;
+        // scale wave: the granules of the sums the scales of step k + 2 of this pair's chains are made of (requested a step ahead)
+        const bool need = scale_wave && jn >= Q.lag && jn < Q.T;
+        const bool mine = need && lane < Q.strips;
+        unsigned long long hq0[2], hq1[2];
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+            hq0[hh] = j ? gq0[2 + hh] : gq0[hh]; hq1[hh] = j ? gq1[2 + hh] : gq1[hh];
+            if (scale_wave && 2 * j + hh < nch && jn + 1 >= Q.lag && jn + 1 < Q.T && lane < Q.strips) {
+                const unsigned long long *gn = Q.gran + ((((long long)((jn + 1 - Q.lag) & (NSLOT - 1)) * Q.nslots + 4 * cs4 + 2 * j + hh) * Q.strips + lane) << 1);
+                const unsigned long long n0_ = blr::ld_u64(gn), n1_ = blr::ld_u64(gn + 1);
+                if (j) { gq0[2 + hh] = n0_; gq1[2 + hh] = n1_; } else { gq0[hh] = n0_; gq1[hh] = n1_; }
+            }
+        }
+        const bool last_pair = j + 1 == npair;
+        const int tnext = last_pair ? tn : t;         // the pair-step that runs after this one: pair 1 of this step, or pair 0 of the next
+        const double sf_now = sf_next;
+        sf_next = (last_pair ? sfwd_l[0] : sfwd_l[1])[min(tnext + 1, Q.T - 1)];
+        __syncthreads();                                            // every wave's rows of this pair are in Xj
+        if (pend_j >= 0) {
+            double *const Xp = X + pend_j * XSZ;
+            const int l = fresh_lane(), g = l >> 4, c = l & 15;
+#pragma unroll
+            for (int it = 0; it < NTW; ++it)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) Xp[(row0 + it * TM + g + 4 * r) * WCOL + c] = stt[it][r];
+            totals(pend_j, pend_k);
+        }
+        // a block with ONE pair has just written the buffer it is about to read its rings from: the waves' rows have to be there first
+        if (npair == 1 && pend_j >= 0) __syncthreads();
+        pend_j = j; pend_k = k;
+
+        constexpr bool FASTEDGE = BLC_FASTEDGE && NTW * TM >= R0;       // (see ring_fill_first_wave)
+        const bool edge = row0 < R0 || row0 + NTW * TM + R0 > N0;
+        constexpr int NRM = BLC_CIRC_RING ? ring_mod<NK>() : NK;      // (circular ring: band_products_wc)
+        double Bv[NRM];
+        {
+            const int l = fresh_lane(), g = l >> 4, c = l & 15;
+            if (FASTEDGE && wv == 0) ring_fill_first_wave(Bv, Xj, g, c, 0, NK, -R0);
+            else if (FASTEDGE && wv == NW - 1 && R0 + 12 >= NTW * TM) ring_fill_last_wave<N0, NTW * TM>(Bv, Xj, g, c, 0, NK, -R0);
+            else if (!FASTEDGE && edge) {
+#pragma unroll
+                for (int kb = 0; kb < NK; ++kb) Bv[kb] = Xj[reflect1(row0 - R0 + 4 * kb + g, N0) * WCOL + c];
+            } else {
+                const double *s0 = Xj + (row0 - R0 + g) * WCOL + c;
+#pragma unroll
+                for (int kb = 0; kb < NK; ++kb) Bv[kb] = s0[kb * 4 * WCOL];
+            }
+        }
+        double scale = 1.0, wq = 0.0, wfloor = 0.0;
+        double mE = 1.0, mR = 1.0, iE = 1.0, iR = 1.0;
+        int nE = 0, nR = 0;
+        double sN = 0.0, sS = 0.0, sC = 0.0;
+        const double *const pnext = (last_pair ? post_l[0] : post_l[1]) + (long long)tnext * G;      // (per lane: its chain's sequence)
+
+        constexpr bool HOISTA = BLC_HOIST_A && BLC_BAND4 && NTW >= 2 && NK <= BLC_FOLD4_HOIST_MAX;
+        double Aw[HOISTA ? NK - 3 : 1];
+        if constexpr (HOISTA) {
+            const int l = fresh_lane();
+            const unsigned aoff = (unsigned)l * 8u + (unsigned)(j * NK * AST * 8);
+            lds_cp Al = (lds_cp)((const char __attribute__((address_space(3))) *)(lds_cp)As + aoff);
+#pragma unroll
+            for (int q = 0; q < NK - 3; ++q) Aw[q] = Al[q * AST];
+        }
+#pragma unroll
+        for (int it = 0; it < NTW; ++it) {
+            const int i = row0 + it * TM;
+            const int l = fresh_lane(), g = l >> 4, c = l & 15;
+            const int h = (l >> 3) & 1;
+            d4 acc = {0.0, 0.0, 0.0, 0.0};
+            if constexpr (HOISTA) {
+                acc = band_products_wc<NK, NRM>(Aw, Bv, BLC_CIRC_RING ? 4 * it : 0);
+            } else {
+                const unsigned aoff = (unsigned)l * 8u + (unsigned)(j * NK * AST * 8);
+                lds_cp Al = (lds_cp)((const char __attribute__((address_space(3))) *)(lds_cp)As + aoff);
+                acc = band_products_c<NK, NRM, AST>(Al, Bv, BLC_CIRC_RING ? 4 * it : 0);
+            }
+            if (it == 0) {
+                const int sl = (j ? slot_l[1] : slot_l[0]) + (k & (NSLOT - 1));
+                scale = scal[sl];
+                double ip = j ? inpred[1] : inpred[0];
+                if (k > 0) ip = ip * sf_now * iscal[sl];             // N_t = s'_t N_(t+1) / s_(t+1)
+                if (j) inpred[1] = ip; else inpred[0] = ip;
+                const double wc = j ? wch[1] : wch[0];
+                wq = wc * ip; wfloor = wc * 1e-300;
+                if (scale_wave) {
+#pragma unroll
+                    for (int hh = 0; hh < 2; ++hh) {
+                        const int cq = 2 * j + hh;
+                        if (cq < nch) {
+                            double sj = 1.0;
+                            if (need) {
+                                const unsigned long long *gp = Q.gran + ((((long long)((jn - Q.lag) & (NSLOT - 1)) * Q.nslots + 4 * cs4 + cq) * Q.strips + lane) << 1);
+                                const unsigned long long want = (unsigned long long)(unsigned)(jn - Q.lag + 1);
+                                unsigned long long q0 = hq0[hh], q1 = hq1[hh];
+                                bool ok = !mine || ((q0 >> 32) == want && (q1 >> 32) == want);
+                                if (!dead && !__all(ok)) {
+                                    const unsigned long long t0 = blr::now_ticks();
+                                    for (unsigned spins = 1; !__all(ok); ++spins) {
+                                        if (!ok) { q0 = blr::ld_u64(gp); q1 = blr::ld_u64(gp + 1); ok = (q0 >> 32) == want && (q1 >> 32) == want; }
+                                        blr::nap();
+                                        if ((spins & 255u) == 0u) {
+                                            if (blr::ld_flag(Q.abort_word) != 0u) { dead = true; break; }
+                                            if (blr::now_ticks() - t0 > Q.timeout_ticks) { blr::st_flag(Q.abort_word, 1u); dead = true; break; }
+                                        }
+                                    }
+                                }
+                                const double v = mine ? __longlong_as_double((long long)((q0 & 0xffffffffull) | (q1 << 32))) : 0.0;
+                                const double Sg = blk::wave_sum(v);
+                                const double sp = j ? Sprev[2 + hh] : Sprev[hh];
+                                sj = dead ? 1.0 : sp * scal[cq * NSLOT + ((jn - Q.lag) & (NSLOT - 1))] / Sg;
+                                if (j) Sprev[2 + hh] = Sg; else Sprev[hh] = Sg;
+                            }
+                            if (lane == 0) { scal[cq * NSLOT + (jn & (NSLOT - 1))] = sj; iscal[cq * NSLOT + (jn & (NSLOT - 1))] = 1.0 / sj; }
+                        }
+                    }
+                }
+                // anchors of the stride-4 likelihood recurrence: all four chains see the same likelihood -- the first pair computes them
+                if (j == 0) {
+                    anchor_unpack(anc_next, a_mE, a_nE, a_mR, a_nR);
+                    const double dn = anc_next.dn;
+                    if (dn != dn_prev) {
+                        const double d2 = -32.0 * cA * dn * Q.step0 * Q.step0;
+                        int tmp;
+                        exp_mn(d2, mq, nq);
+                        exp_mn(-d2, iq, tmp);
+                        dn_prev = dn;
+                    }
+                    a_iE = blmath::inv_m(a_mE); a_iR = blmath::inv_m(a_mR);
+                    anc_next = anchor_load(Q.anch, tn, wv, astrips, atj, anchor_lane(fresh_lane()));
+                }
+                mE = a_mE; nE = a_nE; mR = a_mR; nR = a_nR; iE = a_iE; iR = a_iR;
+            }
+
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double Lv = ldexp(mE, nE);
+                const double beta = acc[r] * scale;
+                const double p = al[it][r] * beta;
+                const double cn = beta * Lv;
+                const double pl = nan_if(Lv == 0.0, ldexp(p * iE, -nE));
+                stt[it][r] = cn;
+                pacc[it][r] += fmax(p * wq, wfloor);
+                sN += p; sS += pl; sC += cn;
+                mE *= mR; nE += nR;
+                mR *= mq; nR += nq;
+                iE *= iR; iR *= iq;
+            }
+            // the last pair of the time step adds the two halves' registers across lanes and stores the cells -- half h its rows 2 h and 2 h + 1
+            // (nobody else touches the slot's cells during the launch) -- and requests those of the next time step: its own rows from the slot,
+            // the other half's from the zeros; every pair-step requests the stored alpha of the pair-step after it
+            const unsigned off_t = cell_off(l, it);
+            if (last_pair) {
+                double tot[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) tot[r] = blk::dpp_add<0x128, 0xf>(pacc[it][r]);          // row_ror:8: lane c + lane c ^ 8
+                char *const ps = (char *)pslot_t + off_t + (h ? 2u * ROW4B : 0u);
+                __builtin_nontemporal_store(h ? tot[2] : tot[0], (double *)ps);
+                __builtin_nontemporal_store(h ? tot[3] : tot[1], (double *)(ps + ROW4B));
+                const char *const pz = (const char *)Q.zeros + (off_t & 2040u);
+                const char *const pn = (const char *)pslot_tn + off_t;
+                const char *const p01 = (Q.part_fresh || h) ? pz : pn, *const p23 = (Q.part_fresh || !h) ? pz : pn;
+                pacc[it][0] = __builtin_nontemporal_load((const double *)p01);
+                pacc[it][1] = __builtin_nontemporal_load((const double *)(p01 + ROW4B));
+                pacc[it][2] = __builtin_nontemporal_load((const double *)(p23 + 2 * ROW4B));
+                pacc[it][3] = __builtin_nontemporal_load((const double *)(p23 + 3 * ROW4B));
+            }
+            {
+                const char *const pa_ = (const char *)pnext + off_t;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) al[it][r] = __builtin_nontemporal_load((const double *)(pa_ + r * ROW4B));
+            }
+            if (it + 1 < NTW) {
+                constexpr bool CIRC = BLC_CIRC_RING != 0;
+                if (!CIRC) {
+#pragma unroll
+                    for (int kb = 0; kb < NK - 4; ++kb) Bv[kb] = Bv[kb + 4];
+                }
+                const int e0 = CIRC ? 4 * it + NK : NK - 4;
+                if (FASTEDGE && wv == NW - 1 && (it + 1) * TM + R0 + 12 >= NTW * TM) ring_fill_last_wave<N0, NTW * TM>(Bv, Xj, g, c, e0, 4, (it + 1) * TM + R0, CIRC ? NRM : 0);
+                else if (!FASTEDGE && edge) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) Bv[CIRC ? (e0 + q) % NRM : e0 + q] = Xj[reflect1(i + TM + R0 + 4 * q + g, N0) * WCOL + c];
+                } else {
+                    const double *s1 = Xj + (i + TM + R0 + g) * WCOL + c;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) Bv[CIRC ? (e0 + q) % NRM : e0 + q] = s1[q * 4 * WCOL];
+                }
+            }
+        }
+
+        // ---- row sums of the pair-step, each half's 8 lanes -> LDS (wave 5 adds them up after the next barrier) ----------------------------
+        {
+            double v[3] = {sN, sS, sC};
+            const int l = fresh_lane();
+            double *rk = red + ((2 * j + ((l >> 3) & 1)) * 2 + (k & 1)) * (NW * 4 * 3);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                double x = v[q];
+                x = blk::dpp_add<0x111, 0xf>(x);
+                x = blk::dpp_add<0x112, 0xf>(x);
+                x = blk::dpp_add<0x114, 0xf>(x);
+                if ((l & 7) == 7) rk[(wv * 4 + (l >> 4)) * 3 + q] = x;
+            }
+        }
+        if (k == 0 && last_pair) {                   // the chains' bands replace the identity of the first step
+            __syncthreads();
+            {
+                double *const Xp = X + pend_j * XSZ;
+                const int l = fresh_lane(), g = l >> 4, c = l & 15;
+#pragma unroll
+                for (int it = 0; it < NTW; ++it)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) Xp[(row0 + it * TM + g + 4 * r) * WCOL + c] = stt[it][r];
+                totals(pend_j, pend_k);
+                pend_j = -1;
+            }
+            for (int e = tid; e < 2 * NK * AST; e += NT) {
+                const int jj = e / (NK * AST), q = e - jj * (NK * AST);
+                const int cq = 2 * jj + ((q >> 3) & 1);                 // (the lane's MFMA block is (l >> 2) & 3, its chain-half block >> 1)
+                const int lw = cq == 0 ? lw0[0] : (cq == 1 ? lw0[1] : (cq == 2 ? lw0[2] : lw0[3]));
+                const long long o = cq == 0 ? o0[0] : (cq == 1 ? o0[1] : (cq == 2 ? o0[2] : o0[3]));
+                const int a = band_distance(q, R0);
+                As[e] = a == 0 ? (lw > 0 ? P.taps[o] : 1.0) : (a <= lw ? P.taps[o + a] : 0.0);
+            }
+        }
+    }
+    __syncthreads();
+    if (pend_j >= 0) totals(pend_j, pend_k);
+}
+
+// (an OVERLOAD of the family's template, not a fourth argument with a default: the registry names a kernel by its full argument list, and the
+//  two-chain kernels keep the names they have)
+template <int NK, int NTW, bool PAD, bool QUAD>
+__global__ __launch_bounds__(NT, 1) void chain_fold2_kernel(const ChainParams P) {
+    static_assert(QUAD && !PAD, "the four-argument flavour: four chains per block on an exact geometry");
+    chain_fold4_body<NK, NTW>(P);
+}
 
 template <int NK, int NTW, bool PAD = false>
 __global__ __launch_bounds__(NT, 1) void chain_fold2_kernel(const ChainParams P) {

@@ -286,7 +286,7 @@ void flush_partials(blhip_ctx *ctx, hipStream_t st, std::vector<hipEvent_t> *lat
     for_grid_y(ctx, ps.T, [&](long long t0, unsigned nt) {
         BL_LAUNCH(fold_parts_kernel, dim3((unsigned)(((G + 1) / 2 + NTHREADS - 1) / NTHREADS), nt), dim3(NTHREADS), 0, st, ctx->acc,
                            ctx->accpart.as<double>(), (long long)ps.T * ps.Gk, ps.slots_init, ps.n0, ps.n1, ps.T, r, rb,
-                           ctx->acc_first ? 1 : 0, ps.n0p, ps.Gk, ps.ax1, (int)t0);
+                           ctx->acc_first ? 1 : 0, ps.n0p, ps.Gk, ps.ax1, (int)t0, ps.sw == 8 ? 3 : 4);
     });
     HIPCHECK(hipGetLastError());
     if (later_ev) HIPCHECK(hipEventRecord(e1, st));
@@ -311,6 +311,7 @@ inline ChainOptions chain_options(const blhip_ctx *ctx) {
     O.fuse_accumulate = flag("fuse_accumulate"); O.fold2 = flag("fold2"); O.fold2_cp = flag("fold2_cp"); O.chain_depad = flag("chain_depad");
     O.share_prefix = flag("share_prefix"); O.skip_prefix = flag("skip_prefix"); O.carry_partials = flag("carry_partials");
     O.chain_resident_lag = std::max(2, std::min(blc::MAXLAG, (int)ctx->option("chain_resident_lag", 4.0)));
+    O.fold4 = flag("fold4"); O.fold4_min_chains = (int)ctx->option("fold4_min_chains", 32.0);
     return O;
 }
 
@@ -386,6 +387,8 @@ struct ChainRun {
     bool touched_parts = false;                    // the backward pass of this batch has written the carried slots
     // fused fold with TWO chains per block (blc::chain_fold2_kernel): the backward pass runs rounds of 2 x cpr chains of its own
     bool fold2 = false;
+    // ... with FOUR (its QUAD flavour): strips of 8 columns -- the stored sequence and the partial accumulators in [t][strip of 8][row][8]
+    bool fold4 = false;
     std::vector<int> round_start_b, round_nk_b;
     bool share_prefix = false;                     // change-point batches: states before a chain's first restart are stored once (see setup)
     bool skip_prefix = false;                      // ... and computed once: a chain's forward pass begins at its first restart
@@ -427,7 +430,7 @@ struct ChainRun {
         if (chain_needs_depad(F, cp, ax1, f.post_private))
             keep = depad = chain_padding_rule(F, opt, cp, chain_mem_admits(chain_depad_bytes(F, Gk), 0.8, (double)E.ctx->postpad.cap), f);
         keep = keep && chain_fold_settle(F, cp, tab, ax1, f);
-        post_private = f.post_private; fused = f.fused; fold2 = f.fold2; slots_used = f.slots_used;
+        post_private = f.post_private; fused = f.fused; fold2 = f.fold2; fold4 = f.fold4; slots_used = f.slots_used;
         round_start_b = std::move(f.round_start_b); round_nk_b = std::move(f.round_nk_b);
         if (!keep) return decline();
         E.mark("  fold plan");
@@ -442,15 +445,17 @@ struct ChainRun {
     void upload_metadata(const BatchEnv &E) {
         blhip_ctx *ctx = E.ctx;
         const int64_t T = E.T, B = E.B;
-        // (granule slots for 2 x cpr chains: the two-chain fold kernel runs rounds of that size)
-        gran_bytes = carve_size((size_t)blc::NSLOT * 2 * cp.cpr * cp.strips * 2 * 8);
+        // (granule slots for 2 x cpr chains: the two-chain fold kernel runs rounds of that size; its four-chain flavour rounds of
+        //  4 x floor(CUs / 2 strips) chains on twice the strips: at most twice as many granules)
+        const size_t gran_n = (size_t)blc::NSLOT * 2 * cp.cpr * cp.strips * 2 * (opt.fold4 ? 2 : 1);
+        gran_bytes = carve_size(gran_n * 8);
         ctx->resx.ensure(carve_size((size_t)B * 4) * 4 + gran_bytes + carve_size(64) + 2 * carve_size((size_t)T * B));
         char *rc = ctx->resx.as<char>();
         d_order = carve<int>(rc, (size_t)B);
         d_tapid = carve<int>(rc, (size_t)B);
         d_tapid1 = carve<int>(rc, (size_t)B);
         d_tshare = carve<int>(rc, (size_t)B);
-        CQ.gran = carve<unsigned long long>(rc, (size_t)blc::NSLOT * 2 * cp.cpr * cp.strips * 2);
+        CQ.gran = carve<unsigned long long>(rc, gran_n);
         d_abort = carve<unsigned>(rc, 16);
         CQ.abort_word = d_abort;
         d_ckF = carve<unsigned char>(rc, (size_t)T * B);
@@ -508,7 +513,7 @@ struct ChainRun {
         CQ.post_stride = (long long)T * Gk;
         CQ.m0 = E.DT->m0; CQ.m1 = E.DT->m1; CQ.colA = E.DT->colA; CQ.colB = E.DT->colB; CQ.rec = E.DT->rec; if (tab && !ax1) CQ.lik = E.DT->lik; CQ.step0 = E.step0;      // (both-axes kernels: CQ.lik is their table of the even steps, set by both_axes_buffers)
         CQ.timeout_ticks = (unsigned long long)(resident_timeout_s(E.ctx, T) * 1e8);
-        psz = std::max(psz, (size_t)T * B * NRED * cp.strips);
+        psz = std::max(psz, (size_t)T * B * NRED * cp.strips * (opt.fold4 ? 2 : 1));      // (the four-chain fold kernel: one slot per strip of 8 columns)
     }
 
     // the anchors of the likelihood recurrence: the same for every chain of the batch (same data, same grid) -- tabulated once, 32 bytes
@@ -545,7 +550,7 @@ struct ChainRun {
         const int64_t T = E.T, B = E.B;
         // (carried slots of earlier batches: a larger buffer or another layout takes them into the accumulator first)
         if (ctx->part.live && ((size_t)slots_used * T * Gk * 8 > ctx->accpart.cap || ctx->part.T != (int)T || ctx->part.Gk != Gk || ctx->part.n0 != E.g.n0 ||
-                               ctx->part.n1 != E.g.n1 || ctx->part.n0p != cp.n0p || ctx->part.ax1 != (ax1 ? 1 : 0)))
+                               ctx->part.n1 != E.g.n1 || ctx->part.n0p != cp.n0p || ctx->part.ax1 != (ax1 ? 1 : 0) || ctx->part.sw != part_width()))
             flush_partials(ctx, E.st, E.fold_ev);
         ctx->accpart.ensure((size_t)slots_used * T * Gk * 8);
         ctx->accw.ensure(carve_size((size_t)T * B * 8) + 2 * carve_size((size_t)B * 8) + carve_size(8192));
@@ -555,6 +560,11 @@ struct ChainRun {
         d_fold_inf = carve<double>(wc, (size_t)B);
         d_zeros = carve<double>(wc, 1024);      // (8 KB: a tile's four cells are read at base + 0 / 512 / 1024 / 1536 bytes, base < 4 KB)
     }
+
+    // columns per strip of the partial accumulators' layout
+    int part_width() const { return fold4 ? blc::WCOL / 2 : blc::WCOL; }
+    // partial-sum slots per (step, chain, sum) of a pass
+    int pass_nblk(bool bwd) const { return (bwd && fused && fold4) ? 2 * cp.strips : cp.strips; }
 
     // what the launch of chains order[s0 .. s1) is told
     blc::ChainParams round_params(const BatchEnv &E, bool bwd, double *psum, int s0, int s1, bool fold_now, bool first) const {
@@ -568,6 +578,8 @@ struct ChainRun {
         Q.post = E.d_post;
         Q.means = bwd ? (E.chain_means ? 1 : 0) : (E.ff.forward_only ? 1 : 0);
         Q.strip_major = (post_private || cp.pad || ax1) ? 1 : 0;            // (the stored sequence is private to the fit then)
+        if (fused && fold4) Q.strip_major = 2;                              // (... and read by the four-chain fold kernel: strips of 8 columns)
+        if (fold_now && fold4) { Q.strips = 2 * cp.strips; Q.nblk = 2 * cp.strips; }
         if (fold_now) {
             Q.sfwd = d_fold_sfwd; Q.wchain = d_fold_w; Q.infirst = d_fold_inf;
             Q.part = E.ctx->accpart.as<double>(); Q.part_stride = (long long)E.T * Gk;
@@ -581,7 +593,7 @@ struct ChainRun {
         blhip_ctx *ctx = E.ctx;
         hipStream_t st = E.st;
         const int64_t T = E.T, B = E.B;
-        HIPCHECK(hipMemsetAsync(psum, 0, (size_t)T * B * NRED * cp.strips * 8, st));
+        HIPCHECK(hipMemsetAsync(psum, 0, (size_t)T * B * NRED * pass_nblk(bwd) * 8, st));
         HIPCHECK(hipMemsetAsync(d_abort, 0, 64, st));
         const bool fold_now = bwd && fused, two = fold_now && fold2;
         const std::vector<int> &rstart = two ? round_start_b : cp.round_start, &rnk = two ? round_nk_b : cp.round_nk;
@@ -611,10 +623,11 @@ struct ChainRun {
                 blc::ClampParams CP{Q, bwd ? E.M->cmodeB : E.M->cmodeF, bwd ? E.M->limitB : E.M->limitF};
                 launch_chain_clamp(st, CP, rnk[r], cp.ntw, bwd, bwd || !E.ff.evidence_only);
             }
+            else if (two && fold4) launch_fold4(st, Q, rnk[r], cp.ntw);
             else if (two) launch_fold2(st, Q, rnk[r], cp.ntw, cp.pad);
             else launch_chain(st, Q, rnk[r], cp.ntw, bwd, store, cp.pad);
             ChainLaunch L;
-            L.nslots = Q.nslots; L.Gk = Gk; L.T = T; L.bwd = bwd; L.fold_now = fold_now; L.two = two; L.ax1 = ax1; L.tab = tab;
+            L.nslots = Q.nslots; L.Gk = Gk; L.T = T; L.bwd = bwd; L.fold_now = fold_now; L.two = two; L.quad = two && fold4; L.ax1 = ax1; L.tab = tab;
             L.evidence_only = E.ff.evidence_only; L.nk = rnk[r]; L.share_prefix = share_prefix; L.skip_prefix = skip_prefix;
             L.tshare = h_tshare.data(); L.chains = cp.order.data() + rstart[r];
             const ChainLaunchCost cost = chain_launch_cost(L, bwd ? EPI_BWD_FLOP : EPI_FWD_FLOP, band_stencil_flop(chain_band_radius(rnk[r])));
@@ -677,7 +690,7 @@ struct ChainRun {
         HIPCHECK(hipMemcpyAsync(d_fold_inf, hi, (size_t)B * 8, hipMemcpyHostToDevice, E.st));
         // the slots need no memset: the first launch of the pass reads zeros instead of them (part_fresh) -- except slots it does not
         // use (a first launch with fewer chains than slots), which later launches may
-        const int first_n = fold2 ? (round_start_b[1] - round_start_b[0] + 1) / 2 : cp.round_start[1] - cp.round_start[0];
+        const int first_n = fold4 ? (round_start_b[1] - round_start_b[0] + 3) / 4 : fold2 ? (round_start_b[1] - round_start_b[0] + 1) / 2 : cp.round_start[1] - cp.round_start[0];
         // (carried slots: only those no earlier batch has written)
         const int have = part_fresh0 ? first_n : ctx->part.slots_init;
         if (have < slots_used)
@@ -741,7 +754,7 @@ struct ChainRun {
             ps.maxlw = std::max(ps.maxlw, fold_max);
             ps.slots_init = std::max(ps.slots_init, slots_used);
             ps.nfold += nfold;
-            ps.n0 = E.g.n0; ps.n1 = E.g.n1; ps.T = (int)T; ps.n0p = cp.n0p; ps.ax1 = ax1 ? 1 : 0; ps.Gk = Gk;
+            ps.n0 = E.g.n0; ps.n1 = E.g.n1; ps.T = (int)T; ps.n0p = cp.n0p; ps.ax1 = ax1 ? 1 : 0; ps.Gk = Gk; ps.sw = part_width();
             (void)later_ev; (void)G; (void)st;
         }
         fold_done = true;

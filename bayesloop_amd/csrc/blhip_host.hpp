@@ -153,6 +153,7 @@ struct blhip_ctx {
         int nfold = 0;                      // chains they hold
         int64_t first_batch = 0;            // first batch of the call with contributions in them
         int n0 = 0, n1 = 0, T = 0, n0p = 0, ax1 = 0; long long Gk = 0;      // layout (fold_parts_kernel's arguments)
+        int sw = 16;                        // ... columns per strip: 16, or 8 where the four-chain fold kernel wrote them
     } part;
     DevBuf anchbuf;              // the anchors of the likelihood recurrence of a chain-resident batch, tabulated once per batch (blc::anchor_table_kernel)
     DevBuf axlik;                // ... its likelihood table of the even time steps (transposed layout): ceil(T / 2) x n0p^2 doubles

@@ -686,9 +686,10 @@ static __global__ __launch_bounds__(NTHREADS) void accumulate_small_kernel(doubl
 // already weighted and normalised, in the kernel's strip-major layout [t][strip][row][16]:
 //     A[t][row][col] = r A + rb sum_slots part[slot][t][col / 16][row][col % 16]          (two cells per lane)
 // (n0p: rows per strip of the partials -- the kernel's padded row count when the grid's is not 128 / 256 / 512; pstep: doubles per time
-//  step of a partial accumulator on that padded geometry)
+//  step of a partial accumulator on that padded geometry; swl: log2 of the strip width -- 4, or 3 where the four-chain fold kernel wrote
+//  strips of 8 columns, [t][strip][row][8])
 static __global__ __launch_bounds__(NTHREADS) void fold_parts_kernel(double *A, const double *part, long long part_stride, int nslots, int n0, int n1,
-                                                               int T, double r, double rb, int first, int n0p, long long pstep, int ax, int t0) {
+                                                               int T, double r, double rb, int first, int n0p, long long pstep, int ax, int t0, int swl) {
     const long long G = (long long)n0 * n1;
     const int t = t0 + (int)blockIdx.y;          // (t0: launches of more steps than gridDim.y holds go in pieces, for_grid_y)
     if (ax && ax_layout_b(t)) {            // the transposed layout of the both-axes kernels: one cell per lane
@@ -714,7 +715,7 @@ static __global__ __launch_bounds__(NTHREADS) void fold_parts_kernel(double *A, 
             const int row = (int)(c / n1), col = (int)(c - (long long)row * n1);
             double *ap = A + (long long)t * G + c;
             double acc = first ? 0.0 : *ap * r;
-            const double *src = part + (long long)t * pstep + ((long long)(col >> 4) * n0p + row) * 16 + (col & 15);
+            const double *src = part + (long long)t * pstep + (((long long)(col >> swl) * n0p + row) << swl) + (col & ((1 << swl) - 1));
             double sum = 0.0;
             for (int k = 0; k < nslots; ++k) sum += src[(long long)k * part_stride];
             *ap = fma(rb, sum, acc);
@@ -727,7 +728,7 @@ static __global__ __launch_bounds__(NTHREADS) void fold_parts_kernel(double *A, 
     double2 *ap = reinterpret_cast<double2 *>(A + (long long)t * G + c);
     double2 acc = first ? make_double2(0.0, 0.0) : *ap;
     if (!first) { acc.x *= r; acc.y *= r; }
-    const double *src = part + (long long)t * pstep + ((long long)(col >> 4) * n0p + row) * 16 + (col & 15);
+    const double *src = part + (long long)t * pstep + (((long long)(col >> swl) * n0p + row) << swl) + (col & ((1 << swl) - 1));
     double2 sum = make_double2(0.0, 0.0);
     for (int k = 0; k < nslots; ++k) {
         const double2 v = *reinterpret_cast<const double2 *>(src + (long long)k * part_stride);

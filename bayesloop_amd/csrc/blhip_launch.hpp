@@ -522,6 +522,12 @@ void launch_fold2(hipStream_t s, const blc::ChainParams &Q, int nk, int ntw, boo
     HIPCHECK(hipGetLastError());
 }
 
+// ... four chains per block (its QUAD flavour: exact geometries, ring lengths 6 .. 24)
+void launch_fold4(hipStream_t s, const blc::ChainParams &Q, int nk, int ntw) {
+    if (ntw >= 3) blcl::fold4_ntw34(s, Q, nk, ntw); else blcl::fold4_ntw12(s, Q, nk, ntw);
+    HIPCHECK(hipGetLastError());
+}
+
 // the smallest supported tile whose tile grid fits the chip (every tile = one co-resident block)
 // (Two 256-thread blocks per CU -- 512 tiles of 32 x 64 for the 1024^2 grid, so that one block computes while the other waits for a
 // strip -- was tried: the 512 blocks were not all co-resident, the hand-off waits timed out and the fit fell back.  One tile per CU.)
