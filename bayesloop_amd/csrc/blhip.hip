@@ -849,7 +849,7 @@ int blhip_set_option(blhip_ctx *ctx, const char *key, double value) {
     // (a key the library never reads is an error, not a silent no-op: an A/B run over a removed option measured nothing -- ADVICE r05)
     static const char *const known[] = {
         "bins_gw", "bins_sb", "bins_slab", "carry_partials", "chain1d", "chain1d_clamp", "chain1d_long", "chain1d_shift", "chain_ax1", "chain_clamp", "chain_depad", "chain_prof", "chain_resident", "chain_resident_lag",
-        "chain_force_fail_batch", "chain_force_fail_stage", "chain_nd", "chain_table", "chain_wide", "comm_reduce_mode", "fast", "fast_S", "fold2", "fold2_cp", "fold4", "fold4_min_chains", "fold_force_fail_batch", "fuse1d", "fuse_accumulate", "late_sums", "lik_program", "max_batch",
+        "chain_force_fail_batch", "chain_force_fail_stage", "chain_nd", "chain_nd_stages", "chain_table", "chain_wide", "comm_reduce_mode", "fast", "fast_S", "fold2", "fold2_cp", "fold4", "fold4_min_chains", "fold_force_fail_batch", "fuse1d", "fuse_accumulate", "late_sums", "lik_program", "max_batch",
         "mem_budget_bytes", "mfma", "mfma_S", "mfma_h", "mfma_h_max_cells", "online_block", "parser_device", "parser_pair_max", "peer_copy_mode", "persist1d", "predictive", "quiet", "recurrence", "resident",
         "resident_force_abort", "resident_lag", "resident_probe", "resident_probe_force_busy", "resident_probe_interval_s", "resident_probe_timeout_s",
         "resident_table", "resident_timeout_s", "share_prefix", "short_first_batch", "skip_prefix", "trace", "wide_h",

@@ -14,6 +14,8 @@
 //             segment that is not active) is skipped -- the plain kernel copies there, which is the same values
 //   epilogue  step_kernel's: p = x L, posterior = a_t x, c = x L, the seven sums
 // The result differs from the plain path's only through the order in which the normaliser's (and the other sums') partial sums are added.
+// Batches with NotEqual or Deterministic passes and resumed / carried fits take the stage flavour of the same body,
+// chain_nd_stage_kernel (below).
 //
 // LDS layout (doubles): buf[2][G] | taps[npass][LWMAX + 1] | grid values of every parameter | red[RED].  Every walk of the program has a
 // tap slot of its own; the block stages a slot only when the chain's tap id on that pass CHANGES (a hyper-study's chain keeps its sigma: once
@@ -92,6 +94,63 @@ inline bool chain_nd_route(int option, bool envelope, long long G, long long B, 
     return B >= CHAIN_ND_MIN_CHAINS && !beyond_axis && 1.25 * chain_nd_kernel_us(G, B, W, threads, cus) <= chain_nd_plain_us(G, B, walks, W);
 }
 
+// ---- the stage flavour (chain_nd_stage_kernel): batches with NotEqual / Deterministic passes, resumed and carried fits -------------------
+enum { CHAIN_ND_WALK = 0, CHAIN_ND_NOTEQUAL = 1, CHAIN_ND_SHIFT = 2 };      // what a pass of the program is
+
+// doubles of one tap slot there: a walk keeps its half kernel (radius + 1), a shift all 2 lw + 1 weights of its asymmetric stencil
+// (lw = ceil|d| + 34 <= 46 for the shifts of up to 12 cells the N-D path admits).  NotEqual needs nothing beside the reduction scratch.
+inline int chain_nd_stage_slot(int lw_walk, int lw_shift) {
+    const int a = (lw_walk < 0 ? 0 : lw_walk) + 1, b = lw_shift > 0 ? 2 * lw_shift + 1 : 0;
+    return a > b ? a : b;
+}
+// doubles of LDS a block needs: as chain_nd_lds_doubles, with one slot of `slot` doubles per pass of the program
+inline size_t chain_nd_stage_lds_doubles(long long G, int slot, int npass, long long n_sum) {
+    return 2 * (size_t)G + (size_t)(npass < 0 ? 0 : npass) * (size_t)(slot < 1 ? 1 : slot) + (size_t)(n_sum < 0 ? 0 : n_sum) + CHAIN_ND_RED;
+}
+inline bool chain_nd_stage_fits(long long G, int slot, int npass, long long n_sum) {
+    return G >= 1 && npass <= CHAIN_ND_MAXPASS && chain_nd_stage_lds_doubles(G, slot, npass, n_sum) * sizeof(double) <= CHAIN_ND_LDS_LIMIT;
+}
+inline int chain_nd_stage_threads(long long G, int slot, int npass, long long n_sum) {
+    return chain_nd_stage_lds_doubles(G, slot, npass, n_sum) * sizeof(double) <= CHAIN_ND_SMALL_BYTES ? CHAIN_ND_NT_SMALL : CHAIN_ND_NT_LARGE;
+}
+inline long long chain_nd_stage_max_cells(int slot, int npass, long long n_sum) {
+    const long long room = (long long)(CHAIN_ND_LDS_LIMIT / sizeof(double)) - (long long)(npass < 0 ? 0 : npass) * (long long)(slot < 1 ? 1 : slot) -
+                           (n_sum < 0 ? 0 : n_sum) - CHAIN_ND_RED;
+    return room < 2 ? 0 : room / 2;
+}
+// The cost model of the stage flavour's default route, in the shape of chain_nd_route's: microseconds per time step and direction, fitted
+// to HyperStudy full fits at T = 256 against the plain path (profiles/chain_nd_notes.md).  Over the passes that are on in the batch:
+//   filters  walks and shifts (one launch each on the plain path); W: taps of the batch's slowest chain, 2 x radius + 1 per filter
+//   sweeps   sweeps over the chain's cells the kernel adds per step: three per NotEqual (its three launches on the plain path: ne_max,
+//            ne_invert, ne_clamp), one per shift (the sum of its output); shifts: the shifts among the filters
+//   plain path  4.7 per filter and for the fused step kernel + 2.5 per NotEqual launch (small kernels) + 0.3 per tap beyond radius 3
+//               + 20 per million cells of the batch
+//   kernel      rounds of blocks x (5 (256 threads) or 7 (1024) + (0.125 x W + 0.2 x sweeps) per thousand cells)
+// The kernel takes a batch of at least CHAIN_ND_MIN_CHAINS chains WITHOUT a shift for which 1.25 x kernel <= plain: NotEqual alone and
+// walk + NotEqual were measured faster on the kernel in every class (1260, 2160, 8000 cells x 16, 64, 256 chains), and so were resumed and
+// carried blocks.  A batch with a Deterministic shift that is on stays on the plain path by default: its 2 (ceil|d| + 34) + 1 taps per
+// cell were measured slower on the kernel at 1260 cells x 16 and 64 chains and at 8000 cells x 16 and 64 chains (faster at 2160 cells and
+// at 256 chains); chain_nd = 2 takes it.
+constexpr bool CHAIN_ND_STAGE_MEASURED = true;
+inline double chain_nd_stage_plain_us(long long G, long long B, int filters, int W, int sweeps, int shifts) {
+    const int wide = W - 7 * filters;
+    return 4.7 * (filters + 1) + 2.5 * (sweeps - shifts) + 0.3 * (wide > 0 ? wide : 0) + 20e-6 * (double)B * (double)G;
+}
+inline double chain_nd_stage_kernel_us(long long G, long long B, int W, int sweeps, int threads, int cus) {
+    const long long slots = (long long)(cus < 1 ? 1 : cus) * (threads == CHAIN_ND_NT_SMALL ? 4 : 1);
+    return (double)((B + slots - 1) / slots) * ((threads == CHAIN_ND_NT_SMALL ? 5.0 : 7.0) + (0.125e-3 * (double)W + 0.2e-3 * (double)sweeps) * (double)G);
+}
+// options chain_nd (0 off, 1 the default rule, 2 wherever the envelope admits the batch) and chain_nd_stages (0: such batches keep the
+// plain path, 1: they follow chain_nd)
+inline bool chain_nd_stage_route(int option, int stages_option, bool envelope, long long G, long long B, int filters, int W, int sweeps, int shifts,
+                                 bool beyond_axis, int threads, int cus) {
+    if (!envelope || option == 0 || stages_option == 0) return false;
+    if (option >= 2) return true;
+    if (!CHAIN_ND_STAGE_MEASURED) return false;
+    return B >= CHAIN_ND_MIN_CHAINS && shifts == 0 && !beyond_axis &&
+           1.25 * chain_nd_stage_kernel_us(G, B, W, sweeps, threads, cus) <= chain_nd_stage_plain_us(G, B, filters, W, sweeps, shifts);
+}
+
 struct ChainNd {
     NdGrid g;
     int B, T, npass;
@@ -104,6 +163,11 @@ struct ChainNd {
     const double *lik;           // (T, G)
     double *post; long long post_stride;       // [B][T][G]: forward: a_t out (null: not kept); backward: a_t in -> posterior out
     double *psum;                // [T][B][NRED] (nblk = 1): the block's totals
+    // the stage flavour alone (chain_nd_stage_kernel)
+    unsigned char pass_kind[CHAIN_ND_MAXPASS];   // CHAIN_ND_WALK / _NOTEQUAL / _SHIFT
+    const double *limit;         // [npass][B] NotEqual's 10**v dV
+    const double *carry_in;      // [B][G] resumed fit: what forward step 0 of kind SRC_PREV continues (normalised: tot = 1); null otherwise
+    double *carry_out;           // [B][G] carried fit that keeps no sequence: the last forward state, as the sequence would hold it; null otherwise
 };
 
 // e / d for 0 <= e < 2^23, d >= 1, with rd ~ 1 / d (two roundings: |rd d - 1| <= 2^-23): e converts exactly, the float product is within
@@ -124,8 +188,25 @@ __device__ __forceinline__ int reflect_any32(int i, int n) {
     return i < n ? i : p - 1 - i;
 }
 
-template <bool BWD, int NT>
-__global__ __launch_bounds__(NT) void chain_nd_kernel(const ChainNd P) {
+// maximum over a block of NW waves; valid in every thread; red: NW doubles
+template <int NW>
+__device__ __forceinline__ double chain_nd_block_max(double v, double *red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    double s = red[0];
+#pragma unroll
+    for (int k = 1; k < NW; ++k) s = fmax(s, red[k]);
+    return s;
+}
+
+// The body of both kernels.  STG: the stage flavour (chain_nd_stage_kernel) -- NotEqual and Deterministic passes, resumed and carried fits;
+// without it the code is chain_nd_kernel's as it always was.
+template <bool BWD, int NT, bool STG>
+__device__ __forceinline__ void chain_nd_body(const ChainNd &P) {
     constexpr int CPT = chain_nd_cpt(NT);
     extern __shared__ double lds_nd[];
     const int G = (int)P.g.G;
@@ -167,29 +248,72 @@ __global__ __launch_bounds__(NT) void chain_nd_kernel(const ChainNd P) {
         }
         const double *lik = P.lik + (size_t)t * G;
         double *pt = po ? po + (size_t)t * G : nullptr;
+        // (the stage flavour's large block has 128 registers a thread and its stage loops beside the 2 x CPT doubles: there the stored a_t
+        //  are loaded behind the passes -- one more global latency per backward step, and no spill)
+        constexpr bool A_EARLY = !(STG && NT == CHAIN_ND_NT_LARGE);
         double L[CPT], A[BWD ? CPT : 1];
 #pragma unroll
         for (int k = 0; k < CPT; ++k) {
             const int e = tid + k * NT;
             L[k] = e < G ? lik[e] : 0.0;
-            if (BWD) A[k] = e < G ? pt[e] : 0.0;
+            if (BWD && A_EARLY) A[k] = e < G ? pt[e] : 0.0;
         }
         double scale = 1.0;
         if (kind == SRC_PREV) {
             scale = 1.0 / tot;
+            if constexpr (STG && !BWD) {
+                if (step == 0 && P.carry_in) {                // (a resumed fit: tot is still 1)
+                    const double *cin = P.carry_in + (size_t)b * G;
+                    for (int e = tid; e < G; e += NT) cur[e] = cin[e];
+                }
+            }
         } else {
             const double *sh = P.shared[kind];
             for (int e = tid; e < G; e += NT) cur[e] = sh[e];
         }
+        // (STG) the sum of the output of the chain's last stage of this step: the epilogue's scale is its inverse.  `staged`, like every
+        // branch below that holds a barrier, depends on the chain's metadata of the step alone: uniform for the block
+        bool staged = false;
+        double stage_sum = 1.0;
         for (int q = 0; q < P.npass; ++q) {
             const int id = __builtin_amdgcn_readlane(ids, q);
             if (id < 0) continue;
+            const int pk = STG ? (int)P.pass_kind[q] : CHAIN_ND_WALK;
+            if constexpr (STG) {
+                if (pk == CHAIN_ND_NOTEQUAL) {
+                    // ne_max / ne_invert / ne_clamp_kernel on the chain's cells, in place: every thread touches the cells it owns (the last
+                    // pass, the load or the epilogue wrote them from this thread); the reductions hold the barriers
+                    double m = -INFINITY;
+                    for (int e = tid; e < G; e += NT) m = fmax(m, cur[e]);
+                    m = chain_nd_block_max<NT / 64>(m, red);
+                    double sv[1] = {0.0};
+                    for (int e = tid; e < G; e += NT) {
+                        const double v = m - cur[e];
+                        cur[e] = v;
+                        sv[0] += v;
+                    }
+                    blk::block_sums<1, NT / 64>(sv, red);
+                    const double total = sv[0], lim = P.limit[(size_t)q * B + b];
+                    double su[1] = {0.0};
+                    for (int e = tid; e < G; e += NT) {
+                        double v = cur[e] / total;
+                        v = v < lim ? lim : v;
+                        cur[e] = v;
+                        su[0] += v;
+                    }
+                    blk::block_sums<1, NT / 64>(su, red);
+                    stage_sum = su[0];
+                    staged = true;
+                    continue;
+                }
+            }
             double *w = tapw + (size_t)q * P.tap_slot;
             if (id != __builtin_amdgcn_readlane(slot_id, q)) {
                 // (slot q was last read in an earlier step's pass q: barriers in between; the barrier below publishes it)
                 const int nlw = P.tap_lw[id];
                 const double *wg = P.taps + P.tap_off[id];
-                for (int j = tid; j <= nlw; j += NT) w[j] = wg[j];
+                const int nw = STG && pk == CHAIN_ND_SHIFT ? 2 * nlw : nlw;       // a shift: all 2 lw + 1 weights
+                for (int j = tid; j <= nw; j += NT) w[j] = wg[j];
                 if (lane == q) { slot_id = id; slot_lw = nlw; }
             }
             const int lw = __builtin_amdgcn_readlane(slot_lw, q);
@@ -197,7 +321,34 @@ __global__ __launch_bounds__(NT) void chain_nd_kernel(const ChainNd P) {
             __syncthreads();
             const int n = P.pass_n[q], inner = P.pass_inner[q];
             const float rn = 1.0f / (float)n, ri = 1.0f / (float)inner;
-            if (lw <= n) {
+            if (STG && pk == CHAIN_ND_SHIFT) {
+                // shift_axis_kernel: out[i] = sum_m w[m + lw] ext[i + m] over blk::extend_index(rule 2), m ascending, fma -- the same
+                // cells in the same order, so the same bits per cell
+                const double *wc = w + lw;
+                double sv[1] = {0.0};
+                for (int e = tid; e < G; e += NT) {
+                    const int r = small_div(e, inner, ri);
+                    const int i = r - small_div(r, n, rn) * n;
+                    const double *row = cur + (e - i * inner);
+                    // blk::extend_index(i + m, n, 2) for consecutive m without a remainder per tap: y = the position of i + m in the
+                    // period 2 (n + 24) of the padded row's half-sample reflection, walked along with m
+                    const int np = n + 24, per = 2 * np;
+                    int y = (i - lw + 12) % per;
+                    y += y < 0 ? per : 0;
+                    double acc = 0.0;
+#pragma unroll 1
+                    for (int m = -lw; m <= lw; ++m) {
+                        const int k = y < np ? y : per - 1 - y;
+                        acc = fma(wc[m], row[min(max(k - 12, 0), n - 1) * inner], acc);
+                        y = y + 1 == per ? 0 : y + 1;
+                    }
+                    oth[e] = acc;
+                    sv[0] += acc;
+                }
+                blk::block_sums<1, NT / 64>(sv, red);
+                stage_sum = sv[0];
+                staged = true;
+            } else if (lw <= n) {
                 for (int e = tid; e < G; e += NT) {
                     const int r = small_div(e, inner, ri);
                     const int i = r - small_div(r, n, rn) * n;
@@ -224,8 +375,20 @@ __global__ __launch_bounds__(NT) void chain_nd_kernel(const ChainNd P) {
             }
             double *sw = cur; cur = oth; oth = sw;
         }
+        if constexpr (STG) {
+            if (staged) scale = 1.0 / stage_sum;
+        }
         // the epilogue touches the cells the thread itself wrote last (same e -> thread map in the load, the passes and here)
+        if constexpr (BWD && !A_EARLY) {
+#pragma unroll
+            for (int k = 0; k < CPT; ++k) {
+                const int e = tid + k * NT;
+                A[k] = e < G ? pt[e] : 0.0;
+            }
+        }
         double s[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        double *co = nullptr;
+        if constexpr (STG && !BWD) co = (step == T - 1 && P.carry_out) ? P.carry_out + (size_t)b * G : nullptr;
 #pragma unroll
         for (int k = 0; k < CPT; ++k) {
             const int e = tid + k * NT;
@@ -236,6 +399,9 @@ __global__ __launch_bounds__(NT) void chain_nd_kernel(const ChainNd P) {
                     p = x * L[k];
                     cur[e] = p;
                     if (pt) pt[e] = p;
+                    if constexpr (STG) {
+                        if (co) co[e] = p;
+                    }
                 } else {
                     p = A[BWD ? k : 0] * x;
                     const double cn = x * L[k];
@@ -265,6 +431,25 @@ __global__ __launch_bounds__(NT) void chain_nd_kernel(const ChainNd P) {
         kind = kind_next;
         ids = ids_next;
     }
+}
+
+template <bool BWD, int NT>
+__global__ __launch_bounds__(NT) void chain_nd_kernel(const ChainNd P) {
+    chain_nd_body<BWD, NT, false>(P);
+}
+
+// The stage flavour: what chain_nd_kernel does, and per step, for its chain, what nd_step does with blhip_nd_stages.hpp --
+//   NotEqual       (transitionModels.py:462-471) block maximum, v = max - x, u = v / sum v with the cells below limit = 10**value dV set to
+//                  it, sum u: three sweeps over the chain's cells in LDS, in place
+//   Deterministic  (:571-602) the asymmetric stencil of TapTable::get_shift along the op's axis (2 lw + 1 weights in the pass's tap slot)
+//                  and the sum of the result
+// After a stage the epilogue's scale is 1 / (sum of the chain's last stage of the step); a walk behind a stage acts on the stage's output
+// unscaled (linear), as filter_axis_kernel does.  A chain that runs no stage at a step keeps 1 / tot: every chain has its block, nothing is
+// copied through.  Forward step 0 of a resumed fit loads the chain's carried state (sum 1); a carried fit that keeps no sequence
+// writes its last forward state to carry_out.
+template <bool BWD, int NT>
+__global__ __launch_bounds__(NT) void chain_nd_stage_kernel(const ChainNd P) {
+    chain_nd_body<BWD, NT, true>(P);
 }
 
 }  // namespace bln

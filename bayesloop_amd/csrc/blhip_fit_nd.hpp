@@ -16,10 +16,24 @@ void launch_chain_nd_t(hipStream_t s, const bln::ChainNd &Q, bool bwd, size_t ld
         BL_LAUNCH((bln::chain_nd_kernel<false, NT>), dim3((unsigned)Q.B), dim3(NT), lds, s, Q);
     }
 }
-void launch_chain_nd(hipStream_t s, const bln::ChainNd &Q, bool bwd, int threads, size_t lds) {
+// ... and its stage flavour (NotEqual / Deterministic passes, resumed and carried fits)
+template <int NT>
+void launch_chain_nd_stage_t(hipStream_t s, const bln::ChainNd &Q, bool bwd, size_t lds) {
+    if (bwd) {
+        arm_kernel(reinterpret_cast<const void *>(&bln::chain_nd_stage_kernel<true, NT>));
+        BL_LAUNCH((bln::chain_nd_stage_kernel<true, NT>), dim3((unsigned)Q.B), dim3(NT), lds, s, Q);
+    } else {
+        arm_kernel(reinterpret_cast<const void *>(&bln::chain_nd_stage_kernel<false, NT>));
+        BL_LAUNCH((bln::chain_nd_stage_kernel<false, NT>), dim3((unsigned)Q.B), dim3(NT), lds, s, Q);
+    }
+}
+void launch_chain_nd(hipStream_t s, const bln::ChainNd &Q, bool bwd, int threads, size_t lds, bool stages = false) {
     if (lds > bln::CHAIN_ND_LDS_LIMIT || Q.g.G > (long long)threads * bln::chain_nd_cpt(threads))
         fail("internal: chain-resident N-D kernel: %zu bytes of LDS, %lld cells on %d threads", lds, Q.g.G, threads);
-    if (threads == bln::CHAIN_ND_NT_SMALL) launch_chain_nd_t<bln::CHAIN_ND_NT_SMALL>(s, Q, bwd, lds);
+    if (stages) {
+        if (threads == bln::CHAIN_ND_NT_SMALL) launch_chain_nd_stage_t<bln::CHAIN_ND_NT_SMALL>(s, Q, bwd, lds);
+        else launch_chain_nd_stage_t<bln::CHAIN_ND_NT_LARGE>(s, Q, bwd, lds);
+    } else if (threads == bln::CHAIN_ND_NT_SMALL) launch_chain_nd_t<bln::CHAIN_ND_NT_SMALL>(s, Q, bwd, lds);
     else launch_chain_nd_t<bln::CHAIN_ND_NT_LARGE>(s, Q, bwd, lds);
     HIPCHECK(hipGetLastError());
 }
@@ -148,8 +162,9 @@ void upload_nd_meta(NdEnv &E, bool chain_nd) {
             src0B[k] = kb == SRC_PREV ? pst[b] : (kb == SRC_UNIFORM ? D.uniform : (kb == SRC_INDEP ? D.indep : D.reset));
         }
     }
-    HIPCHECK(hipMemcpyAsync(M.kindF, (has_stage ? P.stepKF : P.kindF).data(), nT, hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(M.kindB, (has_stage ? P.stepKB : P.kindB).data(), nT, hipMemcpyHostToDevice, st));
+    // (the chain-resident kernel loads by the source kind and knows itself whether its chain ran a stage)
+    HIPCHECK(hipMemcpyAsync(M.kindF, (has_stage && !chain_nd ? P.stepKF : P.kindF).data(), nT, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(M.kindB, (has_stage && !chain_nd ? P.stepKB : P.kindB).data(), nT, hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(M.tapF, P.tapF.data(), P.tapF.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(M.tapB, P.tapB.data(), P.tapB.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(M.taps, P.taps.w.data(), P.taps.w.size() * 8, hipMemcpyHostToDevice, st));
@@ -225,13 +240,25 @@ void nd_step_pass(const NdEnv &E, bool bwd, double *d_ps) {
 // ---- the chain-resident path (blhip_chain_nd.hpp): every step of every chain of the batch in one launch per pass --------------------------
 struct NdChainRun {
     bool on = false;
-    // takes a batch of walks and restarts that is neither resumed nor carried; option chain_nd: 0 off, 1 the batches the cost model gives
-    // it (at least CHAIN_ND_MIN_CHAINS chains), 2 wherever it fits
+    bool stages = false;                             // the stage flavour: a batch with NotEqual / Deterministic passes, a resumed or carried fit
+    int slot = 0;                                    // ... doubles of one of its tap slots
+    // A batch of walks and restarts that is neither resumed nor carried takes chain_nd_kernel; option chain_nd: 0 off, 1 the batches the
+    // cost model gives it (at least CHAIN_ND_MIN_CHAINS chains), 2 wherever it fits.  A batch with stages, a resumed or a carried one takes
+    // chain_nd_stage_kernel under the same option where chain_nd_stage_route admits it; option chain_nd_stages = 0 keeps those plain.
     void setup(blhip_ctx *ctx, const NdFacts &F, const NdBatchProgram &P, const FitFlags &ff, long long G, int64_t B) {
-        const bool program_ok = !F.has_stage && !ff.resume && !ff.carry && F.npass <= bln::CHAIN_ND_MAXPASS;
+        stages = F.has_stage || ff.resume || ff.carry;
+        const int cus = std::min(ctx->num_cus, 256);
+        if (stages) {
+            slot = bln::chain_nd_stage_slot(P.lw_walk_max, P.lw_shift_max);
+            on = bln::chain_nd_stage_route((int)ctx->option("chain_nd", 1.0), (int)ctx->option("chain_nd_stages", 1.0),
+                                           bln::chain_nd_stage_fits(G, slot, F.npass, F.n_sum), G, B, P.stage_filters, P.stage_W, P.stage_sweeps,
+                                           P.stage_shifts, P.stage_beyond_axis, bln::chain_nd_stage_threads(G, slot, F.npass, F.n_sum), cus);
+            return;
+        }
+        const bool program_ok = F.npass <= bln::CHAIN_ND_MAXPASS;
         on = bln::chain_nd_route((int)ctx->option("chain_nd", 1.0), program_ok && bln::chain_nd_fits(G, P.lw_max, F.npass, F.n_sum), G, B,
                                  program_ok ? P.walks_on : 0, program_ok ? P.W_taps : 0, program_ok && P.beyond_axis,
-                                 bln::chain_nd_threads(G, P.lw_max, F.npass, F.n_sum), std::min(ctx->num_cus, 256));
+                                 bln::chain_nd_threads(G, P.lw_max, F.npass, F.n_sum), cus);
     }
     void pass(const NdEnv &E, bool bwd, double *ps) const {
         const NdFacts &F = *E.F;
@@ -240,11 +267,20 @@ struct NdChainRun {
         bln::ChainNd Q{};
         Q.g = E.ng; Q.B = (int)E.B; Q.T = (int)E.T; Q.npass = F.npass;
         for (int q = 0; q < F.npass; ++q) { const int ax = E.p->ops[F.pass_ops[q]].axis; Q.pass_n[q] = E.ng.n[ax]; Q.pass_inner[q] = (int)E.ng.stride[ax]; }
-        Q.tap_slot = lw_max + 1;
+        Q.tap_slot = stages ? slot : lw_max + 1;
         Q.kind = bwd ? M.kindB : M.kindF; Q.tap = bwd ? M.tapB : M.tapF; Q.taps = M.taps; Q.tap_off = M.off; Q.tap_lw = M.lw;
         Q.shared[SRC_PREV] = nullptr; Q.shared[SRC_PRIOR] = E.DT.prior; Q.shared[SRC_RESET] = E.DT.reset; Q.shared[SRC_UNIFORM] = E.DT.uniform;
         Q.shared[SRC_INDEP] = E.DT.indep;
         Q.lik = E.DT.lik; Q.post = E.d_post; Q.post_stride = (long long)E.T * E.G; Q.psum = ps;
+        if (stages) {
+            for (int q = 0; q < F.npass; ++q) Q.pass_kind[q] = (unsigned char)F.pass_kind[q];
+            Q.limit = M.limit;
+            Q.carry_in = !bwd && E.ff.resume ? E.d_carry_src : nullptr;
+            Q.carry_out = !bwd && E.ff.carry && !E.d_post ? E.d_state : nullptr;
+            launch_chain_nd(E.st, Q, bwd, bln::chain_nd_stage_threads(E.G, slot, F.npass, F.n_sum),
+                            bln::chain_nd_stage_lds_doubles(E.G, slot, F.npass, F.n_sum) * sizeof(double), true);
+            return;
+        }
         launch_chain_nd(E.st, Q, bwd, bln::chain_nd_threads(E.G, lw_max, F.npass, F.n_sum), bln::chain_nd_lds_doubles(E.G, lw_max, F.npass, F.n_sum) * sizeof(double));
     }
 };
@@ -318,13 +354,14 @@ void do_fit_nd(blhip_ctx *ctx, const blhip_problem *p, int64_t n_chains, const d
         E.nblk = (int)std::min<long long>((G + NTHREADS - 1) / NTHREADS, 256);
         E.d_carry_src = d_carry_src;
         if (!CR.on) ctx->state.ensure((size_t)3 * B * G * 8);
+        else if (ff.carry && ff.evidence_only) ctx->state.ensure((size_t)B * G * 8);          // (no sequence: the kernel leaves the last states here)
         E.d_state = ctx->state.as<double>(); E.d_tmp[0] = E.d_state + (size_t)B * G; E.d_tmp[1] = E.d_state + (size_t)2 * B * G;
         if (!ff.evidence_only) { ctx->post.ensure((size_t)B * T * G * 8); E.d_post = ctx->post.as<double>(); }
         const size_t psz = nT * NRED * (CR.on ? 1 : E.nblk);
         ctx->psumF.ensure(psz * 8); ctx->redF.ensure(nT * NRED * 8);
         if (ff.full) { ctx->psumB.ensure(psz * 8); ctx->redB.ensure(nT * NRED * 8); }
         upload_nd_meta(E, CR.on);
-        if (ff.resume) E.d_unit = upload_unit_sums(ctx, p, st, B, E.nblk, false);
+        if (ff.resume && !CR.on) E.d_unit = upload_unit_sums(ctx, p, st, B, E.nblk, false);       // (the kernel starts from tot = 1)
 
         float ms = 0;
         double *redF = run_nd_pass(E, CR, false, ev, ctx->psumF, ctx->redF, ctx->pinF, ms);

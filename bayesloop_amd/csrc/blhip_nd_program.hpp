@@ -13,13 +13,17 @@ struct NdFacts {
     int npass = 0;
     bool time_dependent = false, has_stage = false, has_shift = false;
     long long n_sum = 0;                             // sum of the axis lengths (the chain-resident kernel keeps the grid values in LDS)
+    std::vector<int> pass_kind;                      // per pass: 0 a walk, 1 NotEqual, 2 a Deterministic shift (bln::CHAIN_ND_WALK ..)
 };
 
 inline NdFacts nd_facts(const blhip_problem *p) {
     NdFacts F;
     for (int k = 0; k < p->n_ops; ++k) {
         const int kind = p->ops[k].kind;
-        if (kind == BLHIP_OP_GRW || kind == BLHIP_OP_NOTEQUAL || kind == BLHIP_OP_DETERMINISTIC) F.pass_ops.push_back(k);
+        if (kind == BLHIP_OP_GRW || kind == BLHIP_OP_NOTEQUAL || kind == BLHIP_OP_DETERMINISTIC) {
+            F.pass_ops.push_back(k);
+            F.pass_kind.push_back(kind == BLHIP_OP_GRW ? 0 : (kind == BLHIP_OP_NOTEQUAL ? 1 : 2));
+        }
         if (kind == BLHIP_OP_NOTEQUAL || kind == BLHIP_OP_DETERMINISTIC) F.has_stage = true;
         if (kind == BLHIP_OP_DETERMINISTIC) F.has_shift = true;
         if (kind == BLHIP_OP_CHANGEPOINT || kind == BLHIP_OP_BREAKPOINT || kind == BLHIP_OP_DETERMINISTIC) F.time_dependent = true;
@@ -97,6 +101,14 @@ struct NdBatchProgram {
     // batch, the taps of its slowest chain, a walk wider than its axis (the kernel's multi-period reflection)
     int walks_on = 0, W_taps = 0;
     bool beyond_axis = false;
+    // what the stage flavour of the chain-resident kernel is handed, of every program: the widest radius among the walks' tap sets and
+    // among the shifts' (a shift's slot holds 2 lw + 1 weights); and the inputs of ITS cost model, over the passes that are on somewhere
+    // in the batch -- the launches the plain path spends per step (one per walk, three per NotEqual, one per shift, and the fused step
+    // kernel), the taps of the slowest chain (2 x the widest radius + 1 per walk and per shift), the walks and shifts among them, the
+    // sweeps over its cells the kernel adds (three per NotEqual, one per shift), the shifts among the filters, a walk wider than its axis
+    int lw_walk_max = 0, lw_shift_max = 0;
+    int stage_launches = 1, stage_W = 0, stage_filters = 0, stage_sweeps = 0, stage_shifts = 0;
+    bool stage_beyond_axis = false;
 };
 
 // The transition of chain values `val` into a step, evaluated at time stamp tau (list order; only the ops of the active sub-model of a
@@ -181,5 +193,22 @@ inline void build_nd_program(const blhip_problem *p, const NdFacts &F, int64_t c
         }
         if (lw_q > 0) { P.walks_on += 1; P.W_taps += 2 * lw_q + 1; }
         if (lw_q > p->n[p->ops[F.pass_ops[q]].axis]) P.beyond_axis = true;
+    }
+    for (int q = 0; q < npass; ++q) {
+        const int pk = F.pass_kind[q];
+        bool on = false;
+        int lw_q = 0;
+        for (size_t k = 0; k < nT; ++k) {
+            const int f = P.tapF[(size_t)q * nT + k], r = P.tapB[(size_t)q * nT + k];
+            on = on || f >= 0 || r >= 0;
+            if (pk == 1) continue;                                                  // (NotEqual's 0 is a flag, not a tap set)
+            if (f >= 0) lw_q = std::max(lw_q, P.taps.lw[f]);
+            if (r >= 0) lw_q = std::max(lw_q, P.taps.lw[r]);
+        }
+        if (pk == 0) P.lw_walk_max = std::max(P.lw_walk_max, lw_q);
+        if (pk == 2) P.lw_shift_max = std::max(P.lw_shift_max, lw_q);
+        if (pk == 1 && on) { P.stage_launches += 3; P.stage_sweeps += 3; }
+        if (pk != 1 && lw_q > 0) { P.stage_launches += 1; P.stage_filters += 1; P.stage_W += 2 * lw_q + 1; P.stage_sweeps += pk == 2 ? 1 : 0; P.stage_shifts += pk == 2 ? 1 : 0; }
+        if (pk == 0 && lw_q > p->n[p->ops[F.pass_ops[q]].axis]) P.stage_beyond_axis = true;
     }
 }
