@@ -12,7 +12,7 @@ import os
 from .exceptions import BackendError
 
 LIB_NAME = 'libblhip.so'
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 OM_POISSON, OM_GAUSSIAN, OM_GAUSSIAN_MEAN, OM_TABLE = 1, 2, 3, 100
 OM_BERNOULLI, OM_LAPLACE, OM_WHITE_NOISE, OM_AR1, OM_SCALED_AR1 = 4, 5, 6, 7, 8
@@ -27,6 +27,7 @@ OP_STATIC, OP_GRW, OP_CHANGEPOINT, OP_REGIMESWITCH, OP_INDEPENDENT, OP_BREAKPOIN
 OP_BIVARIATE, OP_BIVARIATE_ARG, OP_ALPHASTABLE, OP_ALPHASTABLE_ARG = 7, 8, 9, 10
 OP_DETERMINISTIC, OP_DETERMINISTIC_ARG = 11, 12
 FORWARD_ONLY, EVIDENCE_ONLY, KEEP_POSTERIOR, ACCUMULATE, RESUME, CARRY = 1, 2, 4, 8, 16, 32
+SERIES_RAGGED = 0x10000      # BLHIP_SERIES_RAGGED: blhip_host_series_check only
 
 c_double_p = C.POINTER(C.c_double)
 
@@ -159,6 +160,9 @@ PROTOTYPES = {
     'blhip_posterior_bins': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int64, c_double_p]),
     'blhip_host_bins_check': (C.c_int, [C.POINTER(C.c_int32), C.c_int64, C.c_int64, C.c_char_p, C.c_int]),
     'blhip_host_bins_plan': (C.c_int, [C.POINTER(C.c_int32), C.c_int64, C.c_int64, C.c_int64, C.c_double, C.POINTER(C.c_int64)]),
+    'blhip_set_series': (C.c_int, [C.c_void_p, c_double_p, C.c_int64]),
+    'blhip_host_series_check': (C.c_int, [C.POINTER(Problem), C.c_int64, C.c_int, C.c_char_p, C.c_int]),
+    'blhip_host_series_plan': (C.c_int, [C.POINTER(Problem), C.c_int64, C.c_int, C.c_double, C.POINTER(C.c_int64)]),
     'blhip_host_taps': (C.c_int64, [C.c_int, C.c_int64, c_double_p, C.c_int, c_double_p, C.c_int64, C.POINTER(C.c_int)]),
 }
 

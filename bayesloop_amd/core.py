@@ -754,6 +754,139 @@ class Study(object):
         if not silent:
             print('    + Computed mean parameter values.')
 
+    # ---- many data series, one study ------------------------------------------------------------------------------------------
+    SERIES_MIN = 2                     # fewer series than this: the loop.  Measured (profiles/series_fit_notes.md): the smallest count at which
+                                       # fitMany is not slower than the loop over fit (2 series: 0.77 against 1.66 ms; 1: 0.97 against 0.85)
+    _series_loop_announced = frozenset()      # (reasons already announced on stderr; replaced, not mutated)
+
+    def _seriesWorker(self):
+        """A copy of this study that shares its models, grid and prior and has no data and no results: what the loop of fitMany fits."""
+        import copy
+        W = copy.copy(self)
+        W._posteriorSequence, W._posterior_pending = [], None
+        W.posteriorMeanValues, W.logEvidence, W.localEvidence, W.lastTiming = [], 0, [], {}
+        W.rawData, W.formattedData, W.rawTimestamps, W.formattedTimestamps = np.array([]), np.array([]), None, None
+        return W
+
+    def fitMany(self, series, timestamps=None, forwardOnly=False, evidenceOnly=False, silent=False):
+        """Fits every data series of ``series`` with this study's models, grid, prior and hyper-parameter values: the result holds, for
+        every series s, what ``S.loadData(series[s], timestamps_s); S.fit(...)`` leaves on ``S`` -- the user's loop around ``Study.fit``
+        (reference core.py:330-486).  ``series``: a sequence of arrays as ``loadData`` takes them, of any lengths; ``timestamps``: None, one
+        array for all series, or one per series.  Grid and prior are NOT re-estimated per series, and this study is left as it was.
+
+        One-parameter models whose likelihood the device tabulates from data records (Poisson, GaussianMean, Bernoulli, WhiteNoise) run as
+        ONE device call per batch of series on the chain-resident 1-D kernel, a chain per series (blhip_set_series); everything else runs
+        the loop on a copy of this study, announced once on stderr.  Returns a :class:`SeriesFits`."""
+        import sys
+        self._checkConsistencyModels()
+        series = [d if isinstance(d, np.ndarray) else np.array(d, dtype=float) for d in series]
+        n = len(series)
+        if n == 0:
+            raise ConfigurationError('No data loaded.')
+        if timestamps is None:
+            stamps = [None] * n
+        elif np.ndim(timestamps[0]) > 0:
+            if len(timestamps) != n:
+                raise ConfigurationError('fitMany: {} arrays of time stamps for {} series.'.format(len(timestamps), n))
+            stamps = list(timestamps)
+        else:
+            stamps = [timestamps] * n
+        W = self._seriesWorker()
+        loaded = []
+        one = self.observationModel.segmentLength == 1
+        for d, ts in zip(series, stamps):
+            W.loadData(d, timestamps=ts, silent=True)
+            if len(W.rawData) == 0:
+                raise ConfigurationError('No data loaded.')
+            if not loaded:
+                W._checkConsistency()                       # (the models: once)
+            if one:                                         # (what _formatData makes of segments of one point, without its strided view:
+                W.formattedData, W.formattedTimestamps = W.rawData[:, None], W.rawTimestamps       # thousands of short series)
+            else:
+                W._formatData()
+            loaded.append((W.rawData, W.rawTimestamps, np.array(W.formattedData, dtype=float), np.asarray(W.formattedTimestamps)))
+        R = SeriesFits(self._seriesWorker(), loaded, forwardOnly, evidenceOnly)
+        reason = self._fitSeriesDevice(R, W, forwardOnly, evidenceOnly)
+        if reason is not None:
+            if reason not in Study._series_loop_announced:
+                Study._series_loop_announced = Study._series_loop_announced | {reason}
+                sys.stderr.write('[bayesloop_amd] fitMany runs the loop over Study.fit, one device call per series: {}\n'.format(reason))
+            R._reset()
+            for s in range(n):
+                W.rawData, W.rawTimestamps = loaded[s][0], loaded[s][1]
+                W._posteriorSequence, W._posterior_pending, W.posteriorMeanValues = [], None, []
+                W.fit(forwardOnly=forwardOnly, evidenceOnly=evidenceOnly, silent=True)
+                R._take(s, W)
+            _engine_mod.get_engine().release_posterior(W)
+        if not silent:
+            print('+ Fitted {} data series ({}).'.format(n, 'one device call per batch of series' if reason is None else 'loop over fit'))
+        return R
+
+    def _checkConsistencyModels(self):
+        if not self.observationModel:
+            raise ConfigurationError('No observation model chosen.')
+        if not self.transitionModel:
+            raise ConfigurationError('No transition model chosen.')
+
+    def _fitSeriesDevice(self, R, W, forwardOnly, evidenceOnly):
+        """The fast path of fitMany: fills ``R`` and returns None, or returns the reason why the call takes the loop."""
+        from .exceptions import BackendError
+        eng = _engine_mod.get_engine()
+        loaded = R._loaded
+        n = len(loaded)
+        if not getattr(eng, 'series_fits', False):
+            return 'the engine has no series fits'
+        if getattr(eng, 'options', {}).get('series_fit', 1.0) == 0:
+            return 'option series_fit is 0'
+        if n < self.SERIES_MIN:
+            return 'fewer than {} series'.format(self.SERIES_MIN)
+        if _tm_mod.needs_host_transition(self.transitionModel):
+            return 'the transition model runs on the host'
+        om = self.observationModel
+        if len(self.gridSize) != 1 or om.segmentLength != 1 or device_code(om) == _abi.OM_TABLE:
+            return 'observation model "{}" has no one-parameter likelihood table the device builds from data records'.format(om)
+        lengths = [len(f[2]) for f in loaded]
+        T = max(lengths)
+        longest = lengths.index(T)
+        ragged = any(ln != T for ln in lengths) or any(not np.array_equal(f[3], loaded[longest][3]) for f in loaded)
+        shape = loaded[longest][2].shape[1:]
+        if any(f[2].shape[1:] != shape for f in loaded):
+            return 'the series differ in the shape of a data point'
+        # Series shorter than the longest are padded at the END with NaN.  A NaN step has likelihood one (observationModels.py:
+        # processedPdf), so a padded forward step multiplies by one and its normaliser is the mass the transition kept: one, up to
+        # rounding.  Backwards the pass starts from the uniform message at the padded end; times a likelihood of one it stays uniform, and
+        # a reflecting walk or a clamp (Static, GaussianRandomWalk, RegimeSwitch: what a padded call admits) maps the uniform message to
+        # itself up to rounding, so it arrives uniform at the series' own last step -- where the loop's fit starts it.  Padded steps
+        # therefore change a series' results at rounding level only; their entries are cut from the result.  The same time-independence
+        # is why series with different time stamps may share the stamps of the longest one.
+        data = np.full((n, T) + shape, np.nan)
+        for s, f in enumerate(loaded):
+            data[s, :lengths[s]] = f[2]
+        data = data.reshape(n, T, 1, -1)
+        W.rawData, W.rawTimestamps = loaded[longest][0], loaded[longest][1]
+        W._formatData()
+        problem, program = W._compile(silent=True)
+        flags = (_abi.SERIES_RAGGED if ragged else 0)
+        why = eng.series_check(problem, n, flags)
+        if why is not None:
+            return why
+        ov = np.repeat(W._opValueMatrix(program), n, axis=0)
+        keep = not evidenceOnly
+        per = n if evidenceOnly else eng.series_batch(problem, n, evidence_only=False)
+        R._reset()
+        for first in range(0, n, per):
+            count = min(per, n - first)
+            R._materialize_posterior()                   # (an earlier batch of this call: the context keeps one batch's sequences)
+            try:
+                res = eng.fit_series(problem, data[first:first + count], ov[first:first + count], forward_only=forwardOnly,
+                                     evidence_only=evidenceOnly, keep_posterior=keep, owner=R)
+            except BackendError as e:
+                if 'series fit:' in str(e):
+                    return str(e)
+                raise
+            R._takeBatch(eng, first, count, T, res)
+        return None
+
     def optimize(self, parameterList=[], forwardOnly=False, **kwargs):
         """COBYLA maximisation of the log-evidence over hyper-parameters (reference core.py:488-565); every
         objective evaluation is an evidence-only fit on the GPU."""
@@ -931,6 +1064,142 @@ class Study(object):
             self.getParameterDistribution(kwargs.pop('t'), name, plot=True, density=density, **kwargs)
         else:
             self.plotParameterEvolution(name, color=kwargs.pop('color', 'b'), gamma=kwargs.pop('gamma', 0.5), **kwargs)
+
+
+class SeriesFits(object):
+    """The result of :meth:`Study.fitMany`: for every series s what ``S.loadData(series[s]); S.fit(...)`` would have left on the study.
+    The posterior sequences of the last batch stay on the GPU until they are read (``posteriorSequence(s)``, a later fit on the same
+    engine, pickling), as a study's does: this object owns them."""
+
+    def __init__(self, template, loaded, forwardOnly, evidenceOnly):
+        self._template = template               # the study without data and results (models, grid, prior)
+        self._loaded = loaded                   # per series: raw data, raw time stamps, formatted data, formatted time stamps
+        self.forwardOnly, self.evidenceOnly = bool(forwardOnly), bool(evidenceOnly)
+        self.formattedTimestamps = [f[3] for f in loaded]
+        self._reset()
+
+    def _reset(self):
+        n = len(self._loaded)
+        self.logEvidence = np.zeros(n)
+        self.localEvidence = [[] for _ in range(n)]
+        self.posteriorMeanValues = [[] for _ in range(n)]
+        self._seq = [[] for _ in range(n)]       # host copies; [] never computed (evidenceOnly), None after a zero normaliser
+        self._device = None                      # (engine, first series, count, T of the batch): the sequences the context still holds
+        self.lastTiming = {}
+
+    def __len__(self):
+        return len(self._loaded)
+
+    @property
+    def log10Evidence(self):
+        return self.logEvidence / np.log(10)
+
+    # ---- filled by Study.fitMany -------------------------------------------------------------------------------------------------
+    def _take(self, s, W):
+        """the loop: the results the fit of series s left on the worker study"""
+        self.logEvidence[s] = W.logEvidence
+        self.localEvidence[s] = np.array(W.localEvidence)
+        self.posteriorMeanValues[s] = W.posteriorMeanValues if len(W.posteriorMeanValues) == 0 else np.array(W.posteriorMeanValues)
+        self._seq[s] = W.posteriorSequence
+        self.lastTiming = W.lastTiming
+
+    def _takeBatch(self, eng, first, count, T, res):
+        """the fast path: chains [0, count) of a series fit are the series [first, first + count); entries of padded steps are cut"""
+        for c in range(count):
+            s = first + c
+            Ts = len(self._loaded[s][2])
+            self.logEvidence[s] = float(res.log_evidence[c])
+            self.localEvidence[s] = res.local_evidence[c, :Ts].copy()
+            if res.abort_step[c] >= 0:          # a zero normaliser: as Study._zeroNormaliser leaves a fresh study
+                self.logEvidence[s] = -np.inf
+                self._seq[s] = [] if self.evidenceOnly else None
+            elif not self.evidenceOnly:
+                self.posteriorMeanValues[s] = res.posterior_mean[c, :, :Ts].copy()
+        if not self.evidenceOnly:
+            self._device = (eng, first, count, T)
+        self.lastTiming = res.timing
+
+    def _materialize_posterior(self):
+        dev, self._device = self._device, None
+        if dev is None:
+            return
+        eng, first, count, T = dev
+        gs = list(self._template.gridSize)
+        for c in range(count):
+            s = first + c
+            if self._seq[s] is not None:
+                pending = DevicePosterior(eng, 0, T, gs, chain=c)
+                self._seq[s] = np.array(pending.engine.posterior(pending.chain, pending.T, pending.grid_size, t0=0, t1=len(self._loaded[s][2])))
+
+    def __getstate__(self):
+        self._materialize_posterior()
+        state = dict(self.__dict__)
+        state['_device'] = None
+        return state
+
+    def _chain(self, s):
+        """-> (engine, chain, T) while the sequence of series s is on the device, else None"""
+        dev = self._device
+        if dev is not None and dev[1] <= s < dev[1] + dev[2] and self._seq[s] is not None:
+            return dev[0], s - dev[1], dev[3]
+        return None
+
+    def _index(self, s):
+        s = int(s)
+        if not -len(self) <= s < len(self):
+            raise IndexError('series index {} out of range ({} series)'.format(s, len(self)))
+        return s % len(self)
+
+    # ---- results -----------------------------------------------------------------------------------------------------------------
+    def posteriorSequence(self, s):
+        """The (T_s, *gridSize) posterior sequence of series s (None after a zero normaliser, [] after an evidence-only fit)."""
+        s = self._index(s)
+        on = self._chain(s)
+        if on is not None:
+            eng, chain, T = on
+            pending = DevicePosterior(eng, 0, T, list(self._template.gridSize), chain=chain)
+            return pending.engine.posterior(pending.chain, pending.T, pending.grid_size, t0=0, t1=len(self._loaded[s][2]))
+        return self._seq[s]
+
+    def _requirePosterior(self, s):
+        post = self.posteriorSequence(s)
+        if post is None or len(post) == 0:
+            raise PostProcessingError('Cannot plot posterior sequence as it has not yet been computed. Run complete fit.')
+        return post
+
+    def getParameterMeanValues(self, s, name):
+        return self.posteriorMeanValues[self._index(s)][self._template._parameterIndex(name)]
+
+    def getParameterDistributions(self, s, name, density=True):
+        """(values, (T_s, n) array) of one parameter of series s; reduced on the GPU while the sequence is there."""
+        s = self._index(s)
+        tpl = self._template
+        k = tpl._parameterIndex(name)
+        on = self._chain(s)
+        if on is not None:
+            eng, chain, T = on
+            marginal = DevicePosterior(eng, 0, T, list(tpl.gridSize), chain=chain).marginal(k)[:len(self._loaded[s][2])]
+        else:
+            post = self._requirePosterior(s)
+            axes = tuple(a + 1 for a in range(len(tpl.gridSize)) if a != k)
+            marginal = np.sum(post, axis=axes) if axes else np.array(post)
+        if density:
+            marginal = marginal / tpl.latticeConstant[k]
+        return tpl.marginalGrid[k], marginal
+
+    def study(self, s):
+        """A Study in the state the loop's fit of series s would have left: a copy, its posterior on the host."""
+        s = self._index(s)
+        W = self._template._seriesWorker()
+        W.rawData, W.rawTimestamps, W.formattedData, W.formattedTimestamps = self._loaded[s]
+        seq = self.posteriorSequence(s)
+        W._posteriorSequence = seq if seq is None or len(seq) == 0 else np.array(seq)
+        W.logEvidence = float(self.logEvidence[s])
+        W.localEvidence = np.array(self.localEvidence[s])
+        means = self.posteriorMeanValues[s]
+        W.posteriorMeanValues = means if len(means) == 0 else np.array(means)
+        W.lastTiming = dict(self.lastTiming)
+        return W
 
 
 class HyperStudy(Study):

@@ -61,6 +61,7 @@ namespace {
 #include "blhip_program.hpp"   // TapTable, Geometry, validate, build_records, build_program
 #include "blhip_launch.hpp"    // Tile, launch_* (the launch tables), plan_resident
 #include "blhip_chain_plan.hpp"   // plan_chainres, ChainFacts / ChainOptions and the stages of the chain-resident route on two-parameter grids (no HIP call)
+#include "blhip_series.hpp"    // series_check, series_plan, series_chain_bytes: series fits (no HIP call)
 #include "blhip_batch.hpp"     // plan_batches, upload_tables / _metadata, chains_per_batch, plan_geometry, folds, results
 #include "blhip_book.hpp"      // resident_unlag / chain_unlag, forward_ / backward_bookkeeping, account
 #include "blhip_nd_program.hpp"   // NdFacts, NdBatchProgram, build_nd_program: the transition program on grids with 3 and 4 parameters (no HIP call)
@@ -456,6 +457,26 @@ void collect_fold_times(blhip_ctx *ctx, hipStream_t st, std::vector<hipEvent_t> 
 void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const double *op_values,
             const double *log_w, uint32_t flags, blhip_result *res) {
     Trace tr(ctx->option("trace", 0.0) != 0.0);
+    // Series armed (blhip_set_series): THIS fit takes them over, whatever becomes of it.  Chain c observes series c; problem->data is
+    // ignored (the checks and the shared tables below read series 0 in its place).
+    struct SeriesScope {
+        blhip_ctx *c;
+        explicit SeriesScope(blhip_ctx *ctx) : c(ctx) { c->series.data = c->series.armed; c->series.S = c->series.armed_S; c->series.armed = nullptr; c->series.armed_S = 0; }
+        ~SeriesScope() { c->series.data = nullptr; c->series.S = 0; }
+    } series_scope(ctx);
+    const bool series = ctx->series.data != nullptr;
+    blhip_problem p_series;
+    if (series) {
+        if (!p_in) fail("problem is NULL");
+        if (n_chains != ctx->series.S) fail("series fit: %lld series are armed, the fit has %lld chains", (long long)ctx->series.S, (long long)n_chains);
+        p_series = *p_in;
+        p_series.data = ctx->series.data;
+        p_in = &p_series;
+        char why[256] = "";
+        if (series_check(p_in, n_chains, (int)flags, why, (int)sizeof why) != 0) fail("series fit: %s", why);
+        if (ctx->option("series_fit", 1.0) == 0.0) fail("series fit: option series_fit = 0");
+        ctx->series.om = p_in->obs_model;
+    }
     validate(p_in, n_chains, op_values);
     if (p_in->ndim > 2) { ctx->prior_token = 0; do_fit_nd(ctx, p_in, n_chains, op_values, log_w, flags, res); return; }      // (that path lays the tables buffer out its own way)
     // closed-form models without an in-kernel likelihood: their (T, G) table is built on the device, the step kernels
@@ -497,6 +518,9 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
         BatchProgram &BP = programs.take(bi);
         tr.mark("build_program");
         const GeometryPlan gp = plan_geometry(ctx, p, g, BP.prog, B, DT.d, ff.resume, ff.carry, &BP.taps);
+        if (series && !gp.chain1d)
+            fail("series fit: the chain-resident 1-D kernel does not take this batch (%d cells, radius %d%s; options chain1d / chain1d_long / chain1d_shift / "
+                 "chain1d_clamp / fuse1d)", g.n1, BP.prog.LW1, BP.prog.multi ? ", a composed transition" : "");
         const int base_variant = gp.fast ? 1 : (gp.fused1d ? 4 : 0);
         ctx->timing.fwd_kernel_variant = ctx->timing.bwd_kernel_variant = base_variant;
         ctx->timing.cells_per_launch = std::max<int64_t>(ctx->timing.cells_per_launch, B * g.G);
@@ -811,6 +835,22 @@ int blhip_set_lik_program(blhip_ctx *ctx, const int32_t *ops, int64_t n_ops, con
     });
 }
 
+int blhip_set_series(blhip_ctx *ctx, const double *data, int64_t S) {
+    return guarded(ctx, [&] {
+        ctx->series.armed = nullptr; ctx->series.armed_S = 0;
+        if (!data || S < 1) fail("blhip_set_series: data is NULL or S < 1");
+        ctx->series.armed = data; ctx->series.armed_S = S;
+    });
+}
+
+int blhip_host_series_check(const blhip_problem *problem, int64_t S, int flags, char *err, int errlen) {
+    return series_check(problem, S, flags, err, errlen);
+}
+
+int blhip_host_series_plan(const blhip_problem *problem, int64_t S, int flags, double budget, int64_t *plan_out) {
+    return series_plan(problem, S, flags, budget, plan_out);
+}
+
 int blhip_lik_program_eval(blhip_ctx *ctx, int ndim, const int64_t *n, const double *const *marginal, int64_t T, int data_dim,
                            const double *data, double *out) {
     return guarded(ctx, [&] {
@@ -852,7 +892,7 @@ int blhip_set_option(blhip_ctx *ctx, const char *key, double value) {
         "chain_force_fail_batch", "chain_force_fail_stage", "chain_nd", "chain_nd_stages", "chain_table", "chain_wide", "comm_reduce_mode", "fast", "fast_S", "fold2", "fold2_cp", "fold4", "fold4_min_chains", "fold_force_fail_batch", "fuse1d", "fuse_accumulate", "late_sums", "lik_program", "max_batch",
         "mem_budget_bytes", "mfma", "mfma_S", "mfma_h", "mfma_h_max_cells", "online_block", "parser_device", "parser_pair_max", "peer_copy_mode", "persist1d", "predictive", "quiet", "recurrence", "resident",
         "resident_force_abort", "resident_lag", "resident_probe", "resident_probe_force_busy", "resident_probe_interval_s", "resident_probe_timeout_s",
-        "resident_table", "resident_timeout_s", "share_prefix", "short_first_batch", "skip_prefix", "trace", "wide_h",
+        "resident_table", "resident_timeout_s", "series_fit", "share_prefix", "short_first_batch", "skip_prefix", "trace", "wide_h",
         "wide_h_fused_max", "wide_h_split", "wide_v"};
     bool ok = false;
     for (const char *k : known) ok = ok || std::strcmp(key, k) == 0;

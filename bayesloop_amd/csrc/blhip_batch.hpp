@@ -11,6 +11,16 @@ void ensure_post_scaled(blhip_ctx *ctx) {
     const unsigned gx = (unsigned)std::min<long long>((G + NTHREADS - 1) / NTHREADS, 4096);
     // (rows [post_row0, post_row1) only: the time-resident kernel has normalised the others itself)
     const int64_t r0 = ctx->post_row0, nrows = ctx->post_row1 - ctx->post_row0;
+    // (a series fit keeps thousands of chains of a hundred rows each: a launch per chain was more than half of its kernel time.  The
+    //  chains' rows follow each other: every row of every chain in one launch per max_grid_y rows)
+    if (ctx->post_series && r0 == 0 && nrows == ctx->post_T && nrows > 0) {
+        for_grid_y(ctx, (long long)ctx->post_chains * nrows, [&](long long y0, unsigned ny) {
+            BL_LAUNCH(scale_rows_kernel, dim3(gx, ny), dim3(NTHREADS), 0, ctx->stream, ctx->post.as<double>() + (size_t)y0 * G, G, ctx->postinv.as<double>() + y0);
+        });
+        HIPCHECK(hipGetLastError());
+        ctx->post_scaled = true;
+        return;
+    }
     for (int64_t b = 0; b < ctx->post_chains && nrows > 0; ++b)
         for_grid_y(ctx, nrows, [&](long long y0, unsigned ny) {
             BL_LAUNCH(scale_rows_kernel, dim3(gx, ny), dim3(NTHREADS), 0, ctx->stream,
@@ -369,8 +379,9 @@ int64_t chains_per_batch(blhip_ctx *ctx, const blhip_problem *p, const Geometry 
         const double slots = std::max(1, std::min(ctx->num_cus, 256) / ((g.n1 + blc::WCOL - 1) / blc::WCOL));
         budget -= std::min(0.5 * budget, std::min<double>(slots, (double)n_chains) * (double)T * Gk * 8.0);
     }
-    const double per_chain = (ff.evidence_only ? 2.0 : (double)T + 2.0) * Gk * 8.0 +
-                             (double)T * NRED * 8.0 * 2 * 64.0 /*partials, rough*/;
+    // (series fits: + the chain's own (T, n) likelihood table -- series_chain_bytes, the figure blhip_host_series_plan counts with)
+    const double per_chain = ctx->series.data ? series_chain_bytes(T, G, ff.evidence_only)
+                                              : (ff.evidence_only ? 2.0 : (double)T + 2.0) * Gk * 8.0 + (double)T * NRED * 8.0 * 2 * 64.0 /*partials, rough*/;
     int64_t Bmax = (int64_t)std::max(1.0, std::floor(budget / per_chain));
     // (1-D grids: a chain is a few KB and a batch of the chain-resident 1-D kernel costs a fixed ~1 ms of launches, syncs and read-backs --
     //  the reference's published break-point study, 23 400 chains: 61 ms with batches of 1024, 52 with 4096, 54 with 8192)
@@ -505,7 +516,8 @@ GeometryPlan plan_geometry(blhip_ctx *ctx, const blhip_problem *p, const Geometr
             //  hundred cells with a narrow stencil: 200 cells, radius 27: 2.4 against 2.8 us per step)
             // (clamps without a Deterministic model -- the reference's regime-switch tutorial is ONE such chain: a step of a few hundred cells
             //  costs the block ~2 us against a launch of the generic kernel)
-            gp.chain1d = c1d_mode == 2.0 || (shift1d && (B >= 2 || !prog.has_shift)) || (!shift1d && est_c1d < est_other);
+            // (series fits -- blhip_set_series -- have no other kernel: the cost model does not apply, the envelope above does)
+            gp.chain1d = ctx->series.data != nullptr || c1d_mode == 2.0 || (shift1d && (B >= 2 || !prog.has_shift)) || (!shift1d && est_c1d < est_other);
             if (gp.chain1d) { gp.fusedK = 1; gp.f1_TJ = g.n1; }
         }
         if (shift1d && !gp.chain1d) gp.fused1d = false;
@@ -844,6 +856,7 @@ void keep_posterior(blhip_ctx *ctx, const Geometry &g, int64_t T, int64_t B, con
     HIPCHECK(hipMemcpyAsync(ctx->postinv.p, out.invN.data(), (size_t)T * B * 8, hipMemcpyHostToDevice, st));
     sync_stream(ctx, st);
     ctx->post_valid = true; ctx->post_scaled = false; ctx->post_chains = B; ctx->post_T = T; ctx->post_G = g.G;
+    ctx->post_series = ctx->series.data != nullptr;
     ctx->post_row0 = row0; ctx->post_row1 = row1;
     ctx->post_n0 = g.n0; ctx->post_n1 = g.n1;
     // normalised now, as part of the fit (core.py:441 is inside Study.fit)

@@ -55,6 +55,49 @@ __global__ __launch_bounds__(256) void lik1d_table_kernel(const bl1f::F1Params P
         out[(long long)t * P.n + j] = blk::likelihood<OM>(Q, 0, j, OM == blk::OM_POISSON ? P.colA[j] : 0.0, 0.0, P.m1[j]);
 }
 
+// SERIES FITS (blhip_set_series: chain b of the batch observes its own data series): the batch's (B, T, n) table, series on gridDim.z,
+// steps on gridDim.y, in ONE launch -- from the same device functions as the tables above (blk::likelihood<OM> over the series' records,
+// blk::table_model_likelihood over its data), so a chain's rows are bit for bit the rows a fit of that series alone reads or evaluates.
+// Two adjacent cells per thread: rows of an even number of cells start on 16 bytes (the table's base is 256-byte aligned) and leave as
+// one 16-byte store per thread, consecutive lanes writing consecutive 16 bytes; odd rows keep 8-byte stores (every second row would
+// straddle).  Blocks of 64 .. 256 threads, as many waves as the row's pairs fill (200 cells: 128 threads).  y0: the first step of this
+// launch (for_grid_y).
+template <class F>
+__device__ __forceinline__ void series_row_store(double *__restrict__ row, int n, F &&value) {
+    const int pairs = (n + 1) >> 1;
+    const bool wide = (n & 1) == 0;                       // (uniform across the launch)
+    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < pairs; q += gridDim.x * blockDim.x) {
+        const int j = 2 * q;
+        const double a = value(j);
+        if (j + 1 < n) {
+            const double c = value(j + 1);
+            if (wide) *reinterpret_cast<double2 *>(row + j) = make_double2(a, c);
+            else { row[j] = a; row[j + 1] = c; }
+        } else {
+            row[j] = a;
+        }
+    }
+}
+
+// rec: (B, T, rec_len) records of the batch's series (build_records of every series)
+template <int OM>
+__global__ __launch_bounds__(256) void series_lik_kernel(const bl1f::F1Params P, double *__restrict__ out, int y0) {
+    const long long t = (long long)y0 + blockIdx.y, s = blockIdx.z;
+    blk::StepParams Q{};
+    Q.d = P.d; Q.n1 = P.n; Q.m0 = nullptr; Q.m1 = P.m1;
+    Q.rec = P.rec + (s * P.T + t) * P.rec_len;
+    series_row_store(out + (s * P.T + t) * P.n, P.n,
+                     [&](int j) { return blk::likelihood<OM>(Q, 0, j, OM == blk::OM_POISSON ? P.colA[j] : 0.0, 0.0, P.m1[j]); });
+}
+
+// data: (B, T, d) data of the batch's series (segment length 1); om: blk::OM_BERNOULLI / OM_WHITE_NOISE
+__global__ __launch_bounds__(256) void series_table_kernel(int om, double *__restrict__ out, int n, const double *__restrict__ m1,
+                                                           const double *__restrict__ data, int d, int T, int y0) {
+    const long long t = (long long)y0 + blockIdx.y, s = blockIdx.z;
+    const double *x = data + (s * T + t) * d;
+    series_row_store(out + (s * T + t) * n, n, [&](int j) { return blk::table_model_likelihood(om, m1[j], 0.0, x, 1, d); });
+}
+
 // 2^-k for 2^k <= |v| < 2^(k + 1): the power of two that brings v into [1, 2).  1 for zero, subnormal, infinite, NaN and for the top binade,
 // whose reciprocal power is not a normal number
 __device__ __forceinline__ double pow2_recip(double v) {
@@ -121,6 +164,7 @@ __device__ __forceinline__ void chain1d_body(const bl1f::F1Params &P) {
     int tap_now = -2, lw = 0;
     if (SHIFT && wv == 0) blk::spline_consts(vt + n + 24, n + 24, lane);      // (read by wave 0 only: no barrier)
     const int t0 = P.t_first;
+    const long long lrow0 = P.row0 ? P.row0[b] : 0;          // series fits: the chain's own rows of the likelihood table
     // backward: the stored forward row of the step that runs next waits in registers (requested a step ahead)
     double al[NCPT];
     auto cell_of = [&](int q) { return M == 2 ? 2 * (tid + (q >> 1) * NT) + (q & 1) : tid + q * NT; };      // the q-th cell of this thread
@@ -216,7 +260,7 @@ __device__ __forceinline__ void chain1d_body(const bl1f::F1Params &P) {
             }
         }
         Q.rec = P.rec + (long long)t * P.rec_len;
-        Q.lik = P.lik ? P.lik + (long long)t * n : nullptr;
+        Q.lik = P.lik ? P.lik + (lrow0 + t) * n : nullptr;
         double *row = post ? post + (long long)t * n : nullptr;
         double aN = 0.0, aS = 0.0, aC = 0.0, aM = 0.0, aU = 0.0, aX = 0.0;
         // the epilogue of one cell: o = the transition's output (scaled)

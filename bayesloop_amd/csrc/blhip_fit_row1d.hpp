@@ -14,6 +14,9 @@ struct Row1dRun {
     unsigned *d_abort1 = nullptr;
     size_t p1d_bytes = 0;
     const double *d_fwd_sums = nullptr;    // the forward pass's partial sums (the chain kernel's backward launch reads them)
+    const long long *d_row0 = nullptr;     // series fits: where each chain's rows begin in the batch's (B, T, n) table
+    std::vector<double> h_series;          // ... the records (or data) of the batch's series, alive until the uploads are done (the pass is waited for)
+    std::vector<long long> h_row0;
 
     void setup(const BatchEnv &E) {
         on = E.gp->fused1d;
@@ -52,7 +55,9 @@ struct Row1dRun {
         // (rows beyond bl1c::NMAX: the long-row kernel has no likelihood of its own -- the table for any number of chains)
         const bool c1d_table = chain && (B >= 4 || E.g.n1 > bl1c::NMAX) && !d_lik && (p->obs_model == BLHIP_OM_POISSON || p->obs_model == BLHIP_OM_GAUSSIAN_MEAN);
         d_lik1 = nullptr;
-        if (c1d_table) {
+        d_row0 = nullptr;
+        if (ctx->series.data) series_table(E);
+        else if (c1d_table) {
             ctx->lik1d.ensure((size_t)T * G * 8);
             d_lik1 = ctx->lik1d.as<double>();
             bl1f::F1Params Q = F1;
@@ -128,11 +133,56 @@ struct Row1dRun {
     }
 
 private:
+    // Series fits: chain b of the batch observes series E.c0 + b.  Their records (the models with an in-kernel likelihood) or data (the
+    // table models) go up once per batch, ONE launch tabulates all of them, and the chain kernel reads chain b's rows at row0[b] = b T.
+    void series_table(const BatchEnv &E) {
+        blhip_ctx *ctx = E.ctx;
+        const blhip_problem *p = E.p;
+        const int64_t T = E.T, B = E.B;
+        const int om = ctx->series.om;
+        if (!chain) fail("series fit: the batch is not one of the chain-resident 1-D kernel");
+        if (E.c0 < 0 || E.c0 + B > ctx->series.S) fail("internal: series fit: chains [%lld, %lld) of %lld series", (long long)E.c0, (long long)(E.c0 + B), (long long)ctx->series.S);
+        const size_t per = (size_t)T * p->seg_len * p->data_dim;       // doubles of one series
+        const double *mine = ctx->series.data + (size_t)E.c0 * per;   // (the batch index enters HERE: series c0 .. c0 + B - 1)
+        const bool records = om == BLHIP_OM_POISSON || om == BLHIP_OM_GAUSSIAN_MEAN;
+        int rec_len = p->data_dim;
+        if (records) {
+            h_series.clear();
+            std::vector<double> one;
+            blhip_problem q = *p;
+            q.obs_model = om;
+            for (int64_t b = 0; b < B; ++b) {
+                int d = 0;
+                q.data = mine + (size_t)b * per;
+                build_records(&q, one, rec_len, d);
+                if (rec_len != E.rec_len || d != E.d) fail("internal: series fit: record layout");
+                h_series.insert(h_series.end(), one.begin(), one.end());
+            }
+        } else {
+            h_series.assign(mine, mine + (size_t)B * per);
+        }
+        h_row0.resize((size_t)B);
+        for (int64_t b = 0; b < B; ++b) h_row0[(size_t)b] = (long long)b * T;
+        ctx->databuf.ensure(carve_size(h_series.size() * 8) + carve_size((size_t)B * 8));
+        char *cur = ctx->databuf.as<char>();
+        double *d_ser = carve<double>(cur, h_series.size());
+        long long *d_r0 = carve<long long>(cur, (size_t)B);
+        HIPCHECK(hipMemcpyAsync(d_ser, h_series.data(), h_series.size() * 8, hipMemcpyHostToDevice, E.st));
+        HIPCHECK(hipMemcpyAsync(d_r0, h_row0.data(), (size_t)B * 8, hipMemcpyHostToDevice, E.st));
+        ctx->lik1d.ensure((size_t)B * T * E.G * 8);
+        d_lik1 = ctx->lik1d.as<double>();
+        d_row0 = d_r0;
+        bl1f::F1Params Q = F1;
+        Q.rec = d_ser;
+        for_grid_y(ctx, T, [&](long long y0, unsigned ny) { build_series_table(E.st, om, Q, d_ser, p->data_dim, d_lik1, y0, ny); });
+    }
+
     void launch_c1d(const BatchEnv &E, bool bwd, double *psum) {
         const int64_t T = E.T;
         const DeviceMeta &M = *E.M;
         bl1f::F1Params Q = F1;
         if (d_lik1) Q.lik = d_lik1;
+        Q.row0 = d_row0;
         Q.K = 1; Q.dir = bwd ? -1 : 1; Q.t_first = bwd ? (int)(T - 1) : 0; Q.psum = psum; Q.prev_slot = bwd ? 2 : 0;
         Q.srckind = bwd ? M.kindB : M.kindF; Q.tap = bwd ? M.tapB1 : M.tapF1;
         if (E.gp->shift1d) Q.cmode = bwd ? M.cmodeB : M.cmodeF;

@@ -45,6 +45,9 @@ struct F1Params {
     int no_shift;                                  // ... and none of its steps is a Deterministic shift: long rows may take two cells per thread (M = 2)
     // chain-resident kernel, backward: the forward pass's own sums ([T][B][NRED][nblk], slot 0 = the sum of the stored row a_t), or nullptr
     const double *fwd_sums;
+    // chain-resident kernel, series fits (blhip_set_series): chain b reads row (row0[b] + t) of `lik` -- its own (T, n) table inside the
+    // batch's (B, T, n) one.  nullptr: every chain reads row t of the table they share
+    const long long *row0;
 };
 
 // One step over the cells of a block's window that are still exact after it (lo .. hi - 1): stencil out of LDS, likelihood, new state

@@ -95,6 +95,7 @@ struct blhip_ctx {
     bool post_scaled = true;     // false: the kept rows still carry their raw sums; postinv holds 1 / sum per (chain, step)
     DevBuf postinv;
     int64_t post_chains = 0, post_T = 0, post_G = 0;
+    bool post_series = false;    // kept by a series fit (blhip_set_series): the rows of all chains are normalised in one launch
     int64_t post_row0 = 0, post_row1 = 0;        // rows of the kept sequence that still carry their raw sums
     int post_n0 = 1, post_n1 = 1, acc_n0 = 1, acc_n1 = 1;
     // accumulator
@@ -132,7 +133,11 @@ struct blhip_ctx {
     DevBuf hsrc;                 // the axis-1 pre-pass's output of one step (blhip_hwide.hpp)
     DevBuf stagebuf, stagemeta;  // composed transitions: two stage outputs (+ their partials) of a step, the stages' per-chain programs (blhip_batch.hpp)
     DevBuf p1d, p1w;             // hand-off buffers / weight table of the persistent 1-D kernel (blhip_persist1d.hpp)
-    DevBuf lik1d;                // (T, n) likelihood table the chains of a 1-D batch share (blhip_chain1d.hpp)
+    DevBuf lik1d;                // (T, n) likelihood table the chains of a 1-D batch share (blhip_chain1d.hpp); series fits: (B, T, n), one table per chain
+    // Series fits (blhip_set_series): `armed` arms the next blhip_fit, which takes the arrays over (`data` != nullptr while that fit runs:
+    // chain c observes series c) and disarms.  om: the caller's observation model (the fit itself may see BLHIP_OM_TABLE).  The records /
+    // data and the row offsets of a batch go to `databuf`.
+    struct SeriesFit { const double *armed = nullptr; int64_t armed_S = 0; const double *data = nullptr; int64_t S = 0; int om = 0; } series;
     // the likelihood program blhip_set_lik_program armed for the problems whose obs_model is BLHIP_OM_PROGRAM (blhip_likprog.hpp): host
     // copies of its arrays, and the device buffer a table build uploads them to
     struct LikProgram { std::vector<int32_t> ops; std::vector<double> consts, step; int64_t n_step = 0; bool armed = false; } likprog;

@@ -356,6 +356,20 @@ void build_lik1d_table(hipStream_t s, int om, const bl1f::F1Params &P, double *o
     HIPCHECK(hipGetLastError());
 }
 
+// the (B, T, n) likelihood table of a series batch (bl1c::series_lik_kernel / series_table_kernel): P.rec = the series' records -- or, for
+// the table models, `data` = their data, (B, T, d) -- on the device; steps [y0, y0 + ny) of every series
+void build_series_table(hipStream_t s, int om, const bl1f::F1Params &P, const double *data, int dd, double *out, long long y0, unsigned ny) {
+    if (P.B < 1 || P.B > 65535) fail("internal: series table for %d chains", P.B);
+    const int pairs = (P.n + 1) / 2;
+    const dim3 block((unsigned)std::min(256, (pairs + 63) / 64 * 64));
+    const dim3 grid((unsigned)std::min(16, (pairs + 255) / 256), ny, (unsigned)P.B);
+    if (om == BLHIP_OM_POISSON) BL_LAUNCH((bl1c::series_lik_kernel<OM_POISSON>), grid, block, 0, s, P, out, (int)y0);
+    else if (om == BLHIP_OM_GAUSSIAN_MEAN) BL_LAUNCH((bl1c::series_lik_kernel<OM_GAUSSIAN_MEAN>), grid, block, 0, s, P, out, (int)y0);
+    else if (om == BLHIP_OM_BERNOULLI || om == BLHIP_OM_WHITE_NOISE) BL_LAUNCH(bl1c::series_table_kernel, grid, block, 0, s, om, out, P.n, P.m1, data, dd, P.T, (int)y0);
+    else fail("internal: series table for observation model %d", om);
+    HIPCHECK(hipGetLastError());
+}
+
 // cells per thread: 2 adjacent ones (sharing their stencil operands) for rows longer than a block, else 1 (option chain1d_pair: 0 / 1 force)
 void launch_chain1d(hipStream_t s, int om, const bl1f::F1Params &P, bool bwd, int pair_mode) {
     if (P.n > bl1c::NMAX) return launch_chain1d_long(s, om, P, bwd);

@@ -473,11 +473,49 @@ class HipEngine:
                 (_abi.KEEP_POSTERIOR if keep_posterior else 0) | (_abi.ACCUMULATE if accumulate else 0) | \
                 (_abi.RESUME if resume else 0) | (_abi.CARRY if carry else 0)
         lw = None if log_chain_weight is None else _f64(log_chain_weight)
+        series, self._series_next = getattr(self, '_series_next', None), None
+        if series is not None:                        # (fit_series: armed last, so that nothing comes between the arming and its fit)
+            self._check(self.lib.blhip_set_series(self.ctx, _abi.dptr(series), series.shape[0]))
         self._check(self.lib.blhip_fit(self.ctx, C.byref(cp), n, _abi.dptr(ov), _abi.dptr(lw), flags, C.byref(res)))
         del keep
         if keep_posterior and not evidence_only:
             self._posterior_owner = None if owner is None else weakref.ref(owner)
         return FitResult(logE, local, means, astep, aphase, self.last_timing())
+
+    # ---- many data series in one call (Study.fitMany) --------------------------------------------------------------
+    series_fits = True       # takes fit_series: Study.fitMany then asks series_check / series_batch and leaves its loop to the device
+
+    def series_check(self, problem: FitProblem, n_series, flags=0):
+        """None when a series fit of `problem` is admitted (blhip_host_series_check; flags: _abi.RESUME ..., _abi.SERIES_RAGGED), else the
+        library's reason."""
+        cp, keep = self._problem(problem)
+        err = C.create_string_buffer(512)
+        rc = self.lib.blhip_host_series_check(C.byref(cp), int(n_series), int(flags), err, 512)
+        return None if rc == 0 else (err.value.decode() or 'refused')
+
+    def series_batch(self, problem: FitProblem, n_series, evidence_only=False):
+        """Series per batch of a series fit on this context: blhip_host_series_plan for its memory budget, and option max_batch."""
+        budget = C.c_double()
+        self._check(self.lib.blhip_mem_budget(self.ctx, C.byref(budget)))
+        cp, keep = self._problem(problem)
+        out = (C.c_int64 * 4)()
+        rc = self.lib.blhip_host_series_plan(C.byref(cp), int(n_series), _abi.EVIDENCE_ONLY if evidence_only else 0, budget.value, out)
+        if rc != 0:
+            raise BackendError('series fit: a memory budget of %.0f bytes is below one series (%d bytes; option mem_budget_bytes)'
+                               % (budget.value, int(out[3])) if rc > 0 else 'series fit: blhip_host_series_plan refused the problem')
+        return max(1, min(int(out[0]), int(self.options.get('max_batch', out[0]))))
+
+    def fit_series(self, problem: FitProblem, series, op_values, **kw) -> FitResult:
+        """`fit` with chain c observing series[c]: series is (S, T, seg_len, data_dim) with T, seg_len, data_dim those of `problem`, whose
+        own data is ignored (blhip_set_series).  len(op_values) must be S."""
+        data = np.ascontiguousarray(series, dtype=np.float64)
+        if data.ndim != 4 or data.shape[0] != len(op_values) or data.shape[1] != problem.T:
+            raise BackendError('fit_series: series must be (len(op_values), T, seg_len, data_dim)')
+        self._series_next = data
+        try:
+            return self.fit(problem, op_values, **kw)
+        finally:
+            self._series_next = None
 
     # ---- carried states of streaming fits (OnlineStudy.step) -------------------------------------------------------
     def carry_mix(self, slot, weights, accumulate=False):

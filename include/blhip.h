@@ -8,6 +8,7 @@
  *
  *   blhip_fit            Study.fit                        bayesloop/core.py:330-486
  *                        (+ the per-hyper-point loop of   bayesloop/core.py:1349-1366 / 1473-1489 when n_chains > 1)
+ *   blhip_set_series     the user's loop `for d in series: S.loadData(d); S.fit()` around Study.fit   bayesloop/core.py:330-486
  *   blhip_accum_*        the evidence-weighted average    bayesloop/core.py:1295, 1362-1366, 1339, 1375-1382, 1416-1419
  *   blhip_posterior_*    the posteriorSequence attribute  bayesloop/core.py:356, 408, 436-441
  *   blhip_posterior_query / _bins   Parser.__call__ over a loop of time stamps   bayesloop/parser.py:256-440 (probabilities; :399-418 distributions)
@@ -43,7 +44,7 @@
 extern "C" {
 #endif
 
-#define BLHIP_ABI_VERSION 13
+#define BLHIP_ABI_VERSION 14
 
 typedef struct blhip_ctx blhip_ctx;
 
@@ -397,6 +398,32 @@ int blhip_host_lik_program_check(const int32_t *ops, int64_t n_ops, int64_t n_co
  * and copies the (T, G) table to host memory `out`: what the cell-by-cell tests read. */
 int blhip_lik_program_eval(blhip_ctx *ctx, int ndim, const int64_t *n, const double *const *marginal, int64_t T, int data_dim,
                            const double *data, double *out);
+
+/* ---- series fits (ABI v14; Study.fitMany of bayesloop_amd: the user's loop `for d in series: S.loadData(d); S.fit()` around Study.fit,
+ *      bayesloop/core.py:330-486, as ONE blhip_fit) ---------------------------------------------------------------------------------------
+ * Many short data series on a one-parameter grid -- one Poisson rate per neuron, one Bernoulli rate per subject -- are many single chains,
+ * none of which fills the chip.  blhip_set_series arms the context: in the NEXT blhip_fit chain c observes series c.
+ *   data: (S, T, seg_len, data_dim) on the host, T / seg_len / data_dim those of that fit's problem; NOT copied: the caller keeps it alive
+ *         until that fit has returned.  Series shorter than T are padded with NaN at the end by the caller (a NaN step has likelihood 1).
+ *   The next blhip_fit must be called with n_chains == S; chain c's row of op_values is still its own; problem->data is ignored.  The
+ *   call disarms itself with that fit, whether it succeeds or fails.  BLHIP_RESUME, BLHIP_CARRY and BLHIP_ACCUMULATE are refused.
+ * Every batch of such a fit runs on the chain-resident 1-D kernel (one block per chain, the whole pass in LDS) over a (B, T, n) likelihood
+ * table built in one launch from the series' data by the device functions a single fit evaluates; a fit the kernel's envelope does not
+ * take (row length, radius against the LDS of a CU, options chain1d / chain1d_long / chain1d_shift / chain1d_clamp / fuse1d, option
+ * series_fit = 0) fails with the reason, and the caller runs its loop.
+ * blhip_host_series_check (host only, no GPU, no context): 0 when the path admits the problem -- a 1-D grid, BLHIP_OM_POISSON /
+ * _GAUSSIAN_MEAN / _BERNOULLI / _WHITE_NOISE, seg_len 1, a row of at most 8192 cells, no backward_init, no AlphaStable / Bivariate op, none
+ * of the three flags above (flags: those of blhip_fit) --, else 1 with the reason in err (errlen bytes, may be NULL).  With
+ * BLHIP_SERIES_RAGGED in flags (this function only: the series differ in length or in their time stamps) the program must be
+ * time-independent as well: Static, GRW and REGIMESWITCH ops outside serial models only.
+ * blhip_host_series_plan (host only): plan_out (4 values) = chains per batch (at most 4096), batches, bytes of such a batch, the smallest
+ * budget accepted; a chain counts its state ping-pong, stored sequence and partial sums as in any fit plus its (T, n) likelihood table,
+ * T n 8 bytes.  Batch b covers the chains [b * per, min(S, (b + 1) * per)).  Returns 0; -1 for bad arguments or a problem the check
+ * refuses; 1 for a budget below the minimum (plan_out[3] is still written). */
+#define BLHIP_SERIES_RAGGED 0x10000
+int blhip_set_series(blhip_ctx *ctx, const double *data /* (S, T, seg_len, data_dim), host */, int64_t S);
+int blhip_host_series_check(const blhip_problem *problem, int64_t S, int flags, char *err, int errlen);
+int blhip_host_series_plan(const blhip_problem *problem, int64_t S, int flags, double budget, int64_t *plan_out);
 
 /* ---- multi-GPU exchange of a sharded hyper-study (HyperStudy.fit(nJobs > 1), core.py:1307-1340, 1443-1495) -------------
  * One process per GPU, one context per process; each rank fits its share of the hyper-grid points with blhip_fit and
