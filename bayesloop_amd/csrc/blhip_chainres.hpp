@@ -527,6 +527,23 @@ __global__ __launch_bounds__(NT, 1) void chain_kernel(const ChainParams P) {
         else return __umul24(row0 + it * TM + (l >> 4) + 4 * r, rowx8) + lane_b;
     };
 
+    // (the forward filtering kernels: the 4 NTW cells of a lane differ by WAVE-UNIFORM amounts, (16 it + 4 r) rows.  The lane's part is ONE byte
+    //  offset made in front of the time loop and carried through it; the per-cell part is added to the step's base address on the scalar unit.
+    //  The same bytes as cell_off(), which cost a vector add and a v_mad_u32_u24 per cell and step)
+    constexpr bool LANEOFF = FILTER && !BWD;
+    unsigned lane_off = LANEOFF ? __umul24(row0 + (lane >> 4), rowx8) + lane_b : 0u;
+    if constexpr (LANEOFF) asm volatile("" : "+v"(lane_off));
+    // (the base walks from cell to cell, 4 rows at a time, and is pinned to scalar registers after every stride: left alone the optimiser
+    //  turns it back into sixteen loop-invariant 64-bit offsets, more than the scalar file holds, and adds them on the vector unit)
+    const unsigned row4b = 4u * rowx8;
+    // (a pointer to global memory by type: what comes out of the asm statement has no provenance the compiler could take the address space from)
+    typedef char __attribute__((address_space(1))) *gbytes;
+    typedef double __attribute__((address_space(1))) *gdoubles;
+    auto next_cell = [&](gbytes &p) { p += row4b; asm volatile("" : "+s"(p)); };
+    // (the lane's offset is laundered at every use as well: widened to 64 bits in front of the loop, it no longer fits the store's
+    //  scalar-base + 32-bit-offset form)
+    auto lane_off_now = [&]() { asm volatile("" : "+v"(lane_off)); return lane_off; };
+
     const int kb = (!BWD && !FILTER && P.skip_prefix) ? tsh : 0;      // the first step this chain computes (see ChainParams::skip_prefix)
     if (kb >= P.T) return;                                              // (a chain without a restart that is not the provider: nothing of its own)
     const int t_first = BWD ? P.T - 1 : kb;
@@ -741,6 +758,7 @@ __global__ __launch_bounds__(NT, 1) void chain_kernel(const ChainParams P) {
         double *const pslot_t = FOLD ? pslot + (long long)t * G : nullptr;
         double *const pslot_tn = FOLD ? pslot + (long long)tn * G : nullptr;
         double wq = 0.0, wfloor = 0.0;                 // w / N_t and w * 1e-300: w max(p / N, 1e-300) = max(p wq, wfloor)
+        gbytes pcell = (gbytes)pstep;                  // (LANEOFF) the wave-uniform part of the address of the cell the epilogue stores next
 
         // the band's entries of this lane, once per step for all the wave's tiles (band_products_w)
 #if !BLC_HOIST_LOOP
@@ -772,8 +790,14 @@ __global__ __launch_bounds__(NT, 1) void chain_kernel(const ChainParams P) {
                 const unsigned aoff = AST == 16 ? (unsigned)(((l >> 4) << 2) | (l & 3)) * 8u : (unsigned)l * 8u;
                 lds_cp Al = (lds_cp)((const char __attribute__((address_space(3))) *)(lds_cp)As + aoff);
                 if (nofilter) {                              // (the change point comes after the walk in the model's list: the source unfiltered)
+                    // (forward kernels: the copy is pinned to its arm -- a plain one is four moves in front of EVERY tile's products, which then
+                    //  overwrite them)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[r] = OWNREG ? own[OWNREG ? it : 0][r] : S[(i + g + 4 * r) * WCOL + c];
+                    for (int r = 0; r < 4; ++r) {
+                        double v = OWNREG ? own[OWNREG ? it : 0][r] : S[(i + g + 4 * r) * WCOL + c];
+                        if constexpr (!BWD) asm volatile("" : "+v"(v));
+                        acc[r] = v;
+                    }
                 } else if constexpr (WHOLE_RING && HOISTA) {
                     acc = it == 0 ? band_products_w<NK, 0, NRING>(Aw, Bv) : (it == 1 ? band_products_w<NK, (NTW > 1 ? 4 : 0), NRING>(Aw, Bv) :
                           (it == 2 ? band_products_w<NK, (NTW > 2 ? 8 : 0), NRING>(Aw, Bv) : band_products_w<NK, (NTW > 3 ? 12 : 0), NRING>(Aw, Bv)));
@@ -833,6 +857,10 @@ __global__ __launch_bounds__(NT, 1) void chain_kernel(const ChainParams P) {
                         exp_mn(d1, mR, nR);
                     }
                     if (dn != dn_prev) {                 // (wave-uniform: the records are)
+                        // (a real branch: with ONE exponential inside, the forward filtering kernels' block was if-converted -- range reduction
+                        //  and polynomial ran every step in every wave and three selects threw them away.  The backward kernels, with two, and
+                        //  the no-stencil ones branch already: their code stays as it is)
+                        if constexpr (FILTER && !BWD) asm volatile("");
                         const double d2 = -32.0 * cA * dn * P.step0 * P.step0;
                         int tmp;
                         exp_mn(d2, mq, nq);
@@ -861,7 +889,8 @@ __global__ __launch_bounds__(NT, 1) void chain_kernel(const ChainParams P) {
                         // (rows nobody else reads stay out of the LDS: a neighbour's ring reaches R0 rows into this wave's)
                         if (it * TM + 4 * r < R0 || it * TM + 4 * r + 4 > NTW * TM - R0) D[li * WCOL + c] = a;
                     } else if (TALL && FILTER) nst[it][r] = a; else if (FILTER) D[li * WCOL + c] = a; else stt[it][r] = a;
-                    if (STORE && t >= tsh) stnt(pstep, off, a);
+                    if constexpr (LANEOFF) { if (STORE) { __builtin_nontemporal_store(a, (gdoubles)(pcell + lane_off_now())); next_cell(pcell); } }      // (tsh = 0: no shared prefixes with a stencil)
+                    else if (STORE && t >= tsh) stnt(pstep, off, a);
                     sN += a;
                     if (!FILTER && want_x) sS = fma(a, rst[it][r], sS);
                     acc[r] = a;
