@@ -757,6 +757,8 @@ class Study(object):
     # ---- many data series, one study ------------------------------------------------------------------------------------------
     SERIES_MIN = 2                     # fewer series than this: the loop.  Measured (profiles/series_fit_notes.md): the smallest count at which
                                        # fitMany is not slower than the loop over fit (2 series: 0.77 against 1.66 ms; 1: 0.97 against 0.85)
+                                       # (two-parameter grids, profiles/series_fit_2d_notes.md: 2 series are faster in every case measured --
+                                       #  200 x 200 Gaussian, T = 500, evidence-only: 1.8 against 3.3 ms -- so they need no SERIES_MIN_2D)
     _series_loop_announced = frozenset()      # (reasons already announced on stderr; replaced, not mutated)
 
     def _seriesWorker(self):
@@ -774,9 +776,13 @@ class Study(object):
         (reference core.py:330-486).  ``series``: a sequence of arrays as ``loadData`` takes them, of any lengths; ``timestamps``: None, one
         array for all series, or one per series.  Grid and prior are NOT re-estimated per series, and this study is left as it was.
 
-        One-parameter models whose likelihood the device tabulates from data records (Poisson, GaussianMean, Bernoulli, WhiteNoise) run as
-        ONE device call per batch of series on the chain-resident 1-D kernel, a chain per series (blhip_set_series); everything else runs
-        the loop on a copy of this study, announced once on stderr.  Returns a :class:`SeriesFits`."""
+        ONE device call per batch of series, a chain per series (blhip_set_series), for one-parameter models whose likelihood the device
+        tabulates from data records (Poisson, GaussianMean, Bernoulli, WhiteNoise: the chain-resident 1-D kernel) and for two-parameter
+        grids of 32 - 1024 rows with Gaussian, Laplace, AR1 or ScaledAR1 and Static, a GaussianRandomWalk on the first parameter, change-
+        and break-points, or (Gaussian only) walks on both parameters, when the series have one length and one set of time stamps (the
+        chain-resident kernels blc::chain_kernel / blc::chainax_kernel; DESIGN 8.11).  Everything else -- and a call one of whose batches
+        those kernels do not take or fail -- runs the loop on a copy of this study, announced once on stderr with the reason.  Returns a
+        :class:`SeriesFits`."""
         import sys
         self._checkConsistencyModels()
         series = [d if isinstance(d, np.ndarray) else np.array(d, dtype=float) for d in series]
@@ -843,8 +849,8 @@ class Study(object):
         if _tm_mod.needs_host_transition(self.transitionModel):
             return 'the transition model runs on the host'
         om = self.observationModel
-        if len(self.gridSize) != 1 or om.segmentLength != 1 or device_code(om) == _abi.OM_TABLE:
-            return 'observation model "{}" has no one-parameter likelihood table the device builds from data records'.format(om)
+        if device_code(om) == _abi.OM_TABLE or (len(self.gridSize) == 1 and om.segmentLength != 1):
+            return 'observation model "{}" has no likelihood the device builds from data records'.format(om)
         lengths = [len(f[2]) for f in loaded]
         T = max(lengths)
         longest = lengths.index(T)
@@ -862,14 +868,15 @@ class Study(object):
         data = np.full((n, T) + shape, np.nan)
         for s, f in enumerate(loaded):
             data[s, :lengths[s]] = f[2]
-        data = data.reshape(n, T, 1, -1)
+        data = data.reshape(n, T, om.segmentLength, -1)
         W.rawData, W.rawTimestamps = loaded[longest][0], loaded[longest][1]
         W._formatData()
         problem, program = W._compile(silent=True)
-        flags = (_abi.SERIES_RAGGED if ragged else 0)
+        flags = (_abi.SERIES_RAGGED if ragged else 0) | (_abi.EVIDENCE_ONLY if evidenceOnly else (_abi.FORWARD_ONLY if forwardOnly else 0))
         why = eng.series_check(problem, n, flags)
         if why is not None:
-            return why
+            # (more than one parameter: the library's reason speaks of the grid; which model the call was for goes in front)
+            return why if len(self.gridSize) == 1 else 'observation model "{}": {}'.format(om, why)
         ov = np.repeat(W._opValueMatrix(program), n, axis=0)
         keep = not evidenceOnly
         per = n if evidenceOnly else eng.series_batch(problem, n, evidence_only=False)

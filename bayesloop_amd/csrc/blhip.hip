@@ -399,7 +399,9 @@ BatchRun setup_batch(const FitCall &F, int64_t bi, int64_t c0, int64_t B, BatchP
     R.R1.setup(E);
     if (!R.R1.on) R.SR.setup(E, rr);
     ChainRun &CR = R.CR;
-    R.RR.setup(E, F.n_chains, gp.fast, rr.use_rec, R.psz);
+    // (series fits: a call of ONE series -- the last device call of 3 + 3 + 1 -- stays on the chain kernels, which read per-chain data; the
+    //  time-resident kernel reads the shared tables)
+    if (!ctx->series.data) R.RR.setup(E, F.n_chains, gp.fast, rr.use_rec, R.psz);
     if (!R.RR.on) CR.setup(E, gp.fast, rr.use_rec, R.psz);
     if (R.RR.on || CR.on) ctx->psumF.ensure(R.psz * 8);
     if (CR.on && CR.depad) {                 // a padded batch that hands its posteriors out: scratch sequence for the kernels, ctx->post stays the result
@@ -428,6 +430,9 @@ BatchStep run_attempts(BatchSchedule &sched, BatchRun &R, int base_variant, int6
             return s;
         }
         if (s.action == BATCH_INTERNAL_ERROR) fail("internal: the launch-per-step pass failed after the resident pass gave up");
+        // (series on a two-parameter grid: the kernels a repeat would run on read series 0's tables -- the caller runs its loop)
+        if (const char *why = series_route_refusal(ctx->series.data != nullptr, R.E.p->ndim, CR.on, CR.clamp, true))
+            fail("series fit: %s (a grid of 2 parameters, batch %lld of the call)", why, (long long)R.E.bi);
         if (s.action == BATCH_REPEAT_K1) { usedK = 1; continue; }
         // a resident pass gave up or failed: the launch-per-step kernels take over (timing of the failed attempt is dropped)
         ctx->timing.resident_fallbacks += 1;
@@ -458,7 +463,8 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
             const double *log_w, uint32_t flags, blhip_result *res) {
     Trace tr(ctx->option("trace", 0.0) != 0.0);
     // Series armed (blhip_set_series): THIS fit takes them over, whatever becomes of it.  Chain c observes series c; problem->data is
-    // ignored (the checks and the shared tables below read series 0 in its place).
+    // ignored (the checks and the shared tables below read series 0 in its place; the recurrence's envelope every series: plan_recurrence).
+    // One-parameter grids: Row1dRun::series_table; two-parameter grids: ChainRun::series_tables, and no route but the chain kernels'.
     struct SeriesScope {
         blhip_ctx *c;
         explicit SeriesScope(blhip_ctx *ctx) : c(ctx) { c->series.data = c->series.armed; c->series.S = c->series.armed_S; c->series.armed = nullptr; c->series.armed_S = 0; }
@@ -518,7 +524,7 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
         BatchProgram &BP = programs.take(bi);
         tr.mark("build_program");
         const GeometryPlan gp = plan_geometry(ctx, p, g, BP.prog, B, DT.d, ff.resume, ff.carry, &BP.taps);
-        if (series && !gp.chain1d)
+        if (series && p->ndim == 1 && !gp.chain1d)
             fail("series fit: the chain-resident 1-D kernel does not take this batch (%d cells, radius %d%s; options chain1d / chain1d_long / chain1d_shift / "
                  "chain1d_clamp / fuse1d)", g.n1, BP.prog.LW1, BP.prog.multi ? ", a composed transition" : "");
         const int base_variant = gp.fast ? 1 : (gp.fused1d ? 4 : 0);
@@ -529,6 +535,10 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
         tr.mark("buckets + metadata H2D");
 
         BatchRun R = setup_batch(F, bi, c0, B, BP, gp, M, sched.allow_chainres(bi));
+        // (series on a two-parameter grid: every route but blc::chain_kernel / blc::chainax_kernel reads series 0's tables)
+        if (const char *why = series_route_refusal(series, p->ndim, R.CR.on && !R.RR.on && !R.R1.on, R.CR.clamp, false))
+            fail("series fit: %s (a grid of 2 parameters, %d x %d, batch of %lld chains; options chain_resident / chain_table / chain_ax1 / chain_depad)",
+                 why, g.n0, g.n1, (long long)B);
         int64_t usedK = gp.fusedK;
         if (run_attempts(sched, R, base_variant, usedK).action == BATCH_REWIND) {
             programs.drop();

@@ -184,7 +184,9 @@ RowRecurrence plan_recurrence(blhip_ctx *ctx, const blhip_problem *p, int n0, in
     rr.step0 = step;
     rr.use_rec = p->obs_model == BLHIP_OM_GAUSSIAN && dev <= 8.0 * 2.3e-16 * mx && ctx->option("recurrence", 1.0) != 0.0;
     // ... and arguments inside its envelope (exponents are added in int, exp_mn clamps): beyond it the per-cell exponential
-    if (rr.use_rec && !(rec_envelope_bound(m0h, n0, p->marginal[1], n1, p->data, p->T * p->seg_len, p->data_dim) <= REC_ENVELOPE)) rr.use_rec = false;
+    // (series fits: p->data is the (S, T, seg_len, data_dim) block of ALL the call's series -- the bound is over every record of every one)
+    const int64_t n_rec = (ctx->series.data ? ctx->series.S : 1) * p->T * p->seg_len;
+    if (rr.use_rec && !(rec_envelope_bound(m0h, n0, p->marginal[1], n1, p->data, n_rec, p->data_dim) <= REC_ENVELOPE)) rr.use_rec = false;
     return rr;
 }
 
@@ -360,6 +362,9 @@ int64_t chains_per_batch(blhip_ctx *ctx, const blhip_problem *p, const Geometry 
                              ctx->option("mem_budget_bytes", 0.70 * (double)total_b)) * 0.9;
     // the chain-resident kernels lay their sequences out on a padded geometry (rows 128 / 256 / 512, columns a multiple of 16)
     double Gk = (double)G;
+    // (rows to the next multiple of 128 -- also for 513 .. 896 rows, which the kernels lay out on 1024: the figure every fit's batches
+    //  have been cut with; chain_geometry, the planner's rule, would change the batch sizes of existing fits on such grids.  Series fits
+    //  do not read it: series_chain_bytes below counts with chain_geometry)
     if (p->ndim == 2 && chain_rows_ok(g.n0))
         Gk = (double)((g.n0 + 127) / 128 * 128) * (double)((g.n1 + blc::WCOL - 1) / blc::WCOL * blc::WCOL);
     {   // walks on both parameters: the transposing kernels lay their sequences out on a SQUARE geometry (blhip_chainax.hpp)
@@ -367,7 +372,7 @@ int64_t chains_per_batch(blhip_ctx *ctx, const blhip_problem *p, const Geometry 
         for (int k = 0; k < p->n_ops; ++k)
             if (p->ops[k].kind == BLHIP_OP_GRW) { if (g.axis_map[p->ops[k].axis] == 0) w0 = true; else w1 = true; }
         if (p->ndim == 2 && w0 && w1 && std::max(g.n0, g.n1) <= 512) {
-            const double n = std::max(g.n0, g.n1) <= 128 ? 128.0 : (std::max(g.n0, g.n1) <= 256 ? 256.0 : 512.0);
+            const double n = (double)chain_square_side(g.n0, g.n1);
             Gk = std::max(Gk, n * n);
         }
     }
@@ -380,7 +385,7 @@ int64_t chains_per_batch(blhip_ctx *ctx, const blhip_problem *p, const Geometry 
         budget -= std::min(0.5 * budget, std::min<double>(slots, (double)n_chains) * (double)T * Gk * 8.0);
     }
     // (series fits: + the chain's own (T, n) likelihood table -- series_chain_bytes, the figure blhip_host_series_plan counts with)
-    const double per_chain = ctx->series.data ? series_chain_bytes(T, G, ff.evidence_only)
+    const double per_chain = ctx->series.data ? series_chain_bytes(p, ctx->series.om, ff.evidence_only)
                                               : (ff.evidence_only ? 2.0 : (double)T + 2.0) * Gk * 8.0 + (double)T * NRED * 8.0 * 2 * 64.0 /*partials, rough*/;
     int64_t Bmax = (int64_t)std::max(1.0, std::floor(budget / per_chain));
     // (1-D grids: a chain is a few KB and a batch of the chain-resident 1-D kernel costs a fixed ~1 ms of launches, syncs and read-backs --

@@ -15,6 +15,21 @@ constexpr int CHAIN_TALL_ROWS = 1024;         // ... and the one geometry beyond
 inline bool chain_rows_ok(int n0) { return n0 >= CHAIN_MIN_ROWS && n0 <= CHAIN_TALL_ROWS; }
 inline bool chain_tall(int n0) { return n0 > 512 && n0 <= CHAIN_TALL_ROWS; }
 
+// The geometry the kernels lay a chain of an n0 x n1 grid out on -- the ONE copy of the rule: plan_chainres plans with it, and the series
+// plan (blhip_series.hpp: blhip_host_series_plan, and chains_per_batch for a series fit) counts a chain's bytes with it.  Strips: rows 128 / 256 / 384 / 512, or 1024 beyond 512, columns a
+// multiple of 16.  Square (walks on both parameters, blc::chainax_kernel; grids of up to 512 rows and columns): the next of 128 / 256 / 512.
+struct ChainGeometry { int n0p = 0, n1p = 0; };
+inline int chain_square_side(int n0, int n1) { return std::max(n0, n1) <= 128 ? 128 : (std::max(n0, n1) <= 256 ? 256 : 512); }
+inline ChainGeometry chain_geometry(int n0, int n1, bool square) {
+    ChainGeometry c;
+    if (square) { c.n0p = c.n1p = chain_square_side(n0, n1); return c; }
+    c.n0p = chain_tall(n0) ? CHAIN_TALL_ROWS : (n0 + 127) / 128 * 128;
+    c.n1p = (n1 + blc::WCOL - 1) / blc::WCOL * blc::WCOL;
+    return c;
+}
+// tabulated likelihoods (blc::chain_kernel TAB): geometries of at most 512 rows, and no padded one of 384 / 512 rows (chain_settle)
+inline bool chain_table_geometry_ok(int n0p, bool pad) { return n0p <= 512 && !(pad && n0p >= 384); }
+
 // The chain-resident path (blhip_chainres.hpp): which chains of the batch run together, in which order, with which band width.
 struct ChainResPlan {
     int ntw = 0, strips = 0, cpr = 0;            // product tiles per wave, strips per chain, chains per launch
@@ -36,9 +51,8 @@ bool plan_chainres(const Geometry &g, const ChainProgram &prog, const TapTable &
     // any grid of 32 .. 512 rows: the kernels work on the next geometry of 128 / 256 / 384 / 512 rows x a multiple of 16 columns;
     // 513 .. 1024 rows: 1024 rows x a multiple of 16 columns (one copy of the strip in LDS: blc::chain_kernel TALL; change-point batches keep their state in registers there too)
     if (!chain_rows_ok(g.n0)) return false;
-    cp.n0p = (g.n0 + 127) / 128 * 128;
-    cp.n1p = (g.n1 + blc::WCOL - 1) / blc::WCOL * blc::WCOL;
-    if (chain_tall(g.n0)) cp.n0p = CHAIN_TALL_ROWS;
+    const ChainGeometry cg = chain_geometry(g.n0, g.n1, false);
+    cp.n0p = cg.n0p; cp.n1p = cg.n1p;
     cp.pad = cp.n0p != g.n0 || cp.n1p != g.n1;
     cp.strips = cp.n1p / blc::WCOL;
     cp.ntw = cp.n0p / (blc::NW * blc::TM);
@@ -49,7 +63,7 @@ bool plan_chainres(const Geometry &g, const ChainProgram &prog, const TapTable &
     cp.ax1 = false;
     // walks on both parameters (blhip_chainax.hpp): an exact square geometry (the blocks of a chain change between column strips and row strips)
     // -- the next square geometry of 128 / 256 / 512 rows = columns that holds the grid (PAD kernels where it is larger)
-    const int ax_n = std::max(g.n0, g.n1) <= 128 ? 128 : (std::max(g.n0, g.n1) <= 256 ? 256 : 512);
+    const int ax_n = chain_square_side(g.n0, g.n1);
     const bool ax1_geom = cp.allow_ax1 && std::max(g.n0, g.n1) <= 512 && g.n0 >= 32 && g.n1 >= 32 && ax_n / blc::WCOL <= cus;
     std::vector<int> lw(B, 0);
     cp.ckF.assign((size_t)T * B, (unsigned char)SRC_PREV);
@@ -153,6 +167,7 @@ struct ChainFacts {
     bool chain_means = false, allow_chainres = true, resident_ok = true;
     int num_cus = 256;
     bool acc_aligned = true;                       // the average posterior's buffer is 16-byte aligned
+    bool series = false;                           // a series fit (blhip_set_series): every chain of the batch observes its OWN data
     int cus() const { return std::min(num_cus, 256); }      // compute units a launch counts on: one block per CU
 };
 
@@ -210,7 +225,7 @@ inline bool chain_settle(const ChainFacts &F, const ChainOptions &O, ChainAdmit 
         }
     }
     if (on && A.tab && cp.ntw > 4) on = false;
-    if (on && A.tab && cp.pad && cp.ntw >= 3 && !cp.ax1) on = false;      // (padded 384 / 512-row geometries with a likelihood table: no kernel -- never selected by a test or workload, pruned in round 5)
+    if (on && A.tab && !cp.ax1 && !chain_table_geometry_ok(cp.n0p, cp.pad)) on = false;      // (padded 384 / 512-row geometries with a likelihood table: no kernel -- never selected by a test or workload, pruned in round 5)
     if (on && F.LW1 > 0 && !cp.ax1) on = false;
     return on;
 }
@@ -342,6 +357,8 @@ inline ChainPrefix chain_prefix_plan(const ChainFacts &F, const ChainOptions &O,
     const int64_t T = F.T, B = F.B;
     const bool may_share = fused && O.share_prefix;
     const bool may_skip = (fused || F.evidence_only) && O.skip_prefix;
+    // (series fits: the chains differ from their FIRST step on -- each observes its own data --, nothing of a prefix is anybody else's)
+    if (F.series) return P;
     if (!((may_share || may_skip) && cp.has_reset && prog.LW0 == 0 && !cp.mixed && !ax1 && B >= 2)) return P;      // (blc::chainax_kernel reads neither tshare nor skip_prefix)
     P.tfirst.assign((size_t)B, (int)T);
     bool plain = true;
@@ -357,6 +374,20 @@ inline ChainPrefix chain_prefix_plan(const ChainFacts &F, const ChainOptions &O,
         if (b != P.prov) { P.tsh[b] = std::min(P.tfirst[b], P.tfirst[P.prov]); P.saved += P.tsh[b]; }
     if (P.saved > 0) { P.share = may_share || may_skip; P.skip = may_skip; }
     return P;
+}
+
+// ---- series fits on two-parameter grids: route or fail ----------------------------------------------------------------------------------------
+// Only blc::chain_kernel and blc::chainax_kernel read a chain's OWN records / anchors / table.  Every other route of a batch -- the
+// time-resident kernel of a single chain, the launch-per-step kernels, the clamping chain kernels, and the launch-per-step repeat after a
+// chain-resident pass gave up or failed a check -- reads the batch's shared tables, which hold series 0.  -> nullptr: the batch may run
+// (`chain_on`: ChainRun took it; `clamp`: on its clamping kernels; `repeat`: its passes ask for a repeat on other kernels); else why the
+// fit has to fail (the caller then runs its loop)
+inline const char *series_route_refusal(bool series, int ndim, bool chain_on, bool clamp, bool repeat) {
+    if (!series || ndim != 2) return nullptr;
+    if (!chain_on) return "the chain-resident kernels do not take this batch";
+    if (clamp) return "the batch would run on the clamping chain-resident kernels";
+    if (repeat) return "a chain-resident pass gave up or failed its check";
+    return nullptr;
 }
 
 // ---- behind the passes: where the batch's posteriors are and in which layout the separate fold reads them (finish_batch, blhip.hip) ----------

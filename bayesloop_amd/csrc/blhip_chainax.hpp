@@ -193,9 +193,10 @@ __global__ __launch_bounds__(NT, 1) void chainax_kernel(const ChainParams Parg) 
                (unsigned)((g & 2) + 4 * (2 * rp + (g & 1))) * 8u;
     };
 
+    const double *const recb = P.rec + (long long)b * P.rec_chain;      // (series fits: the chain's own records; rec_chain = 0: the batch's shared ones)
     double xd[DMAX], xn[DMAX];
 #pragma unroll
-    for (int q = 0; q < DMAX; ++q) xd[q] = q < P.d ? P.rec[(long long)t_first * P.rec_len + q] : __builtin_nan("");
+    for (int q = 0; q < DMAX; ++q) xd[q] = q < P.d ? recb[(long long)t_first * P.rec_len + q] : __builtin_nan("");
     // backward: the stored alpha / fold: the accumulator cells of the lane's cells at this step -- requested behind the gather (whose tagged
     // loads must not queue behind HBM loads: loads return in order), a whole filter phase ahead of the epilogue that consumes them
     double al[BWD ? NTW : 1][4];
@@ -297,7 +298,7 @@ __global__ __launch_bounds__(NT, 1) void chainax_kernel(const ChainParams Parg) 
         const double sf_now = sfn;
         if (FOLD) sfn = P.sfwd[(long long)b * P.T + min(tn + 1, P.T - 1)];
 #pragma unroll
-        for (int q = 0; q < DMAX; ++q) xn[q] = q < P.d ? P.rec[(long long)tn * P.rec_len + q] : __builtin_nan("");
+        for (int q = 0; q < DMAX; ++q) xn[q] = q < P.d ? recb[(long long)tn * P.rec_len + q] : __builtin_nan("");
 
         // ---- the first filter, along the lines of the layout the state is in -> the strips of the other layout ----------------------------
         // (state in layout A: axis 0 along the rows; in layout B: axis 1 along the columns)

@@ -107,6 +107,10 @@ struct ChainParams {
     // them a step ahead instead of evaluating two exponentials per lane and step -- every chain of a hyper-study sees the SAME likelihood, so
     // the 512 chains of BASELINE C4 repeated each anchor 512 times (5.6 % of its forward pass, 2.8 % of the folding backward pass)
     const double *anch;
+    // series fits (blhip_set_series on a two-parameter grid): chain b of the batch observes its OWN data -- doubles between the records /
+    // anchors / likelihood tables of two chains of the batch; the kernels re-base the pointer once, in the prologue.  0: every chain reads
+    // the same ones (every other fit).  blc::chain_kernel and blc::chainax_kernel only: a series fit never folds.
+    long long rec_chain, anch_chain, lik_chain;
 };
 
 // ---- the anchors of the stride-4 likelihood recurrence (blhip_mfma.hpp) of a lane's rows at one time step --------------------------------------
@@ -217,7 +221,7 @@ __device__ __forceinline__ LoopParams loop_params(const ChainParams &P) {
 
 // Every field of the argument block as a scalar value of its own (see own_sgpr): the both-axes kernels' step loops reloaded one 16-register
 // tuple of the block 15 - 17 times per step (272 of 508 v_readlane in chainax_kernel<12, 4, backward, fold>) for single fields of it.
-static_assert(sizeof(ChainParams) == 352, "own_chain_params copies ChainParams field by field: a new field needs its line there (and this size)");
+static_assert(sizeof(ChainParams) == 376, "own_chain_params copies ChainParams field by field: a new field needs its line there (and this size)");
 __device__ __forceinline__ ChainParams own_chain_params(const ChainParams &P) {
     ChainParams Q;
     Q.n0 = own_sgpr(P.n0);
@@ -272,6 +276,9 @@ __device__ __forceinline__ ChainParams own_chain_params(const ChainParams &P) {
     Q.lik_nat = own_sgpr(P.lik_nat);
     Q.xch_mode = own_sgpr(P.xch_mode);
     Q.anch = own_sgpr(P.anch);
+    Q.rec_chain = own_sgpr(P.rec_chain);
+    Q.anch_chain = own_sgpr(P.anch_chain);
+    Q.lik_chain = own_sgpr(P.lik_chain);
     return Q;
 }
 
@@ -547,9 +554,13 @@ __global__ __launch_bounds__(NT, 1) void chain_kernel(const ChainParams P) {
     const int kb = (!BWD && !FILTER && P.skip_prefix) ? tsh : 0;      // the first step this chain computes (see ChainParams::skip_prefix)
     if (kb >= P.T) return;                                              // (a chain without a restart that is not the provider: nothing of its own)
     const int t_first = BWD ? P.T - 1 : kb;
+    // series fits: the chain's own records / anchors / likelihood table (ChainParams::rec_chain ..; 0: the batch's shared ones)
+    const double *const recb = P.rec + (long long)b * P.rec_chain;
+    const double *const anchb = P.anch + (long long)b * P.anch_chain;
+    const double *const likb = P.lik + (long long)b * P.lik_chain;
     double xd[DMAX], xn[DMAX];
 #pragma unroll
-    for (int q = 0; q < DMAX; ++q) xd[q] = q < P.d ? P.rec[(long long)t_first * P.rec_len + q] : __builtin_nan("");
+    for (int q = 0; q < DMAX; ++q) xd[q] = q < P.d ? recb[(long long)t_first * P.rec_len + q] : __builtin_nan("");
     // (TALL: 1024 rows leave no room for a whole step of stored alpha beside the new state -- a ring of ALD tiles, re-filled ALD tiles ahead)
     constexpr int ALD = NTW > 4 ? 2 : NTW;        // (a divisor of NTW: a tile keeps its slot from step to step)
     double al[ALD][4];                     // backward: the stored alpha of the lane's cells; a slot is re-filled for the NEXT step right
@@ -603,7 +614,7 @@ __global__ __launch_bounds__(NT, 1) void chain_kernel(const ChainParams P) {
     //  different time steps once prefixes are skipped -- evaluate their anchors themselves: C5's forward pass lost 30 % with the table)
     constexpr bool ANCT = !TAB && FILTER;
     AnchorEntry anc{1.0, 1.0, 0.0, 0.0};
-    if constexpr (ANCT) anc = anchor_load(P.anch, t_first, wv, P.strips, tj, lane);
+    if constexpr (ANCT) anc = anchor_load(anchb, t_first, wv, P.strips, tj, lane);
 #ifdef BLC_PROF
     const bool prof_me = blockIdx.x == 0 && lane == 0 && (wv == 0 || wv == 2);
 #endif
@@ -664,9 +675,9 @@ __global__ __launch_bounds__(NT, 1) void chain_kernel(const ChainParams P) {
         const double sf_now = sfn;
         if (FOLD) sfn = P.sfwd[(long long)b * P.T + min(tn + 1, P.T - 1)];
 #pragma unroll
-        for (int q = 0; q < DMAX; ++q) xn[q] = q < P.d ? P.rec[(long long)tn * P.rec_len + q] : __builtin_nan("");
+        for (int q = 0; q < DMAX; ++q) xn[q] = q < P.d ? recb[(long long)tn * P.rec_len + q] : __builtin_nan("");
         AnchorEntry anc_next{1.0, 1.0, 0.0, 0.0};
-        if constexpr (ANCT) anc_next = anchor_load(P.anch, tn, wv, P.strips, tj, fresh_lane());
+        if constexpr (ANCT) anc_next = anchor_load(anchb, tn, wv, P.strips, tj, fresh_lane());
 
         // ---- ring over the source state -----------------------------------------------------------------------------------------------
         double *S = TALL ? X : X + (k & 1) * XSZ;
@@ -733,7 +744,7 @@ __global__ __launch_bounds__(NT, 1) void chain_kernel(const ChainParams P) {
         // (TAB) the likelihood of the lane's cells at this step: requested in front of the products, consumed by the epilogues
         double lk[TAB ? NTW : 1][4];
         if (TAB) {
-            const double *const lrow = P.lik + (long long)t * n0t * n1t;
+            const double *const lrow = likb + (long long)t * n0t * n1t;
             const int l = fresh_lane();
 #pragma unroll
             for (int it = 0; it < NTW; ++it)

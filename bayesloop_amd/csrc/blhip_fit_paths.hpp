@@ -326,6 +326,7 @@ inline ChainFacts chain_facts(const BatchEnv &E, bool fast, bool use_rec) {
     F.n0 = E.g.n0; F.n1 = E.g.n1; F.G = E.G; F.T = E.T; F.B = E.B;
     F.chain_means = E.chain_means; F.allow_chainres = E.allow_chainres; F.resident_ok = E.ctx->resident.ok; F.num_cus = E.ctx->num_cus;
     F.acc_aligned = ((uintptr_t)E.ctx->acc & 15) == 0;
+    F.series = E.ctx->series.data != nullptr;
     return F;
 }
 
@@ -423,8 +424,9 @@ struct ChainRun {
         upload_metadata(E);
         if (ax1 && !both_axes_buffers(E)) return decline();
         fill_params(E, psz);
-        // (no-stencil batches: only their folding backward pass reads the anchors)
-        if (!tab && !ax1 && (prog.LW0 > 0 || F.full) && !anchor_table(E)) return decline();
+        // (no-stencil batches: only their folding backward pass reads the anchors; series fits never fold: the filtering flavours only)
+        if (F.series) { if (!clamp && !series_tables(E, prog.LW0 > 0)) return decline(); }
+        else if (!tab && !ax1 && (prog.LW0 > 0 || F.full) && !anchor_table(E)) return decline();
         ChainFold f = chain_fold_plan(F, opt, prog, *E.taps, cp, tab, ax1, clamp);
         bool keep = true;
         if (chain_needs_depad(F, cp, ax1, f.post_private))
@@ -484,7 +486,9 @@ struct ChainRun {
         const double tab_bytes = (double)((T + 1) / 2) * (double)Gk * 8.0;
         // the exchange buffers and the table are not part of chains_per_batch's budget: a long series on a large geometry declines the
         // path here instead of failing in the allocator
-        const bool want_tab = tab || B <= 2;
+        // (series fits: the table of the even steps is ONE data series' -- off; every chain evaluates its likelihood from its own records)
+        const bool few = B <= 2 && ctx->series.data == nullptr;
+        const bool want_tab = tab || few;
         if (!chain_mem_admits((double)xch_bytes + (want_tab ? tab_bytes : 0.0), 0.8, (double)ctx->xch.cap + (double)ctx->axlik.cap)) return false;
         ctx->xch.ensure(xch_bytes);
         CQ.xch = ctx->xch.as<double>(); CQ.xch_chain = 2 * Gk; CQ.tap_id1 = d_tapid1;
@@ -495,7 +499,7 @@ struct ChainRun {
             blcl::chainax_lik_transpose(E.st, E.DT->lik, ctx->axlik.as<double>(), cp.n0p, E.g.n0, E.g.n1, (int)T);
             HIPCHECK(hipGetLastError());
             CQ.lik = ctx->axlik.as<double>(); CQ.lik_nat = E.DT->lik;
-        } else if (B <= 2 && tab_bytes < CHAIN_AXLIK_MAX_BYTES) {
+        } else if (few && tab_bytes < CHAIN_AXLIK_MAX_BYTES) {
             ctx->axlik.ensure((size_t)tab_bytes);
             blcl::chainax_lik_table(E.st, cp.n0p, E.g.n0, E.g.n1, (int)T, E.d, E.rec_len, E.DT->m0, E.DT->colA, E.DT->colB, E.DT->rec, ctx->axlik.as<double>());
             HIPCHECK(hipGetLastError());
@@ -531,6 +535,77 @@ struct ChainRun {
         HIPCHECK(hipGetLastError());
         CQ.anch = ctx->anchbuf.as<double>();
         E.mark("  anchor table queued");
+        return true;
+    }
+
+    // Series fits (blhip_set_series): chain b of the batch observes series E.c0 + b.  The batch's records go up as rec[(b T + t) rec_len + q]
+    // (build_records per series); the filtering Gaussian flavours get their anchors from anchor_table_kernel run over B T "steps" -- chain
+    // b's table begins anchor_index(T, 0, strips, 0, 0) doubles behind chain b - 1's --, the table models one (T, G) table per chain from
+    // lik_table_kernel run over the batch's B T data segments.  The no-stencil flavours and blc::chainax_kernel evaluate from the records.
+    // The kernels re-base their pointers by ChainParams::rec_chain / anch_chain / lik_chain.  -> false: the tables do not fit
+    bool series_tables(const BatchEnv &E, bool filters) {
+        blhip_ctx *ctx = E.ctx;
+        const blhip_problem *p = E.p;
+        const int64_t T = E.T, B = E.B;
+        const int om = ctx->series.om;
+        if (E.c0 < 0 || E.c0 + B > ctx->series.S) fail("internal: series fit: chains [%lld, %lld) of %lld series", (long long)E.c0, (long long)(E.c0 + B), (long long)ctx->series.S);
+        if (tab && ax1) return false;                     // (two table layouts per batch: no series flavour)
+        const size_t per = (size_t)T * p->seg_len * p->data_dim;       // doubles of one series
+        const double *mine = ctx->series.data + (size_t)E.c0 * per;   // (the batch index enters HERE: series c0 .. c0 + B - 1)
+        std::vector<double> h_series;
+        size_t one_len = per;
+        if (tab) h_series.assign(mine, mine + (size_t)B * per);
+        else {
+            std::vector<double> one;
+            blhip_problem q = *p;
+            for (int64_t b = 0; b < B; ++b) {
+                int rec_len = 0, d = 0;
+                q.data = mine + (size_t)b * per;
+                build_records(&q, one, rec_len, d);
+                if (rec_len != E.rec_len || d != E.d || one.size() != (size_t)T * rec_len) fail("internal: series fit: record layout");
+                h_series.insert(h_series.end(), one.begin(), one.end());
+            }
+            one_len = (size_t)T * E.rec_len;
+        }
+        // (doubles of y steps of anchors: blc::anchor_index(y, 0, strips, 0, 0))
+        auto anch_steps = [&](long long y) { return (size_t)y * blc::NW * (size_t)cp.strips * 64 * 4; };
+        const size_t anch_one = anch_steps(T);
+        const bool anchors = !tab && !ax1 && filters;
+        const double need = tab ? (double)B * (double)T * (double)E.G * 8.0 : (anchors ? (double)B * (double)anch_one * 8.0 : 0.0);
+        if (need > 0.0 && !chain_mem_admits(need, 0.5, (double)(tab ? ctx->lik1d.cap : ctx->anchbuf.cap))) return false;
+        ctx->databuf.ensure(h_series.size() * 8);
+        double *d_ser = ctx->databuf.as<double>();
+        HIPCHECK(hipMemcpyAsync(d_ser, h_series.data(), h_series.size() * 8, hipMemcpyHostToDevice, E.st));
+        if (tab) {
+            ctx->lik1d.ensure((size_t)B * T * E.G * 8);
+            double *d_lik = ctx->lik1d.as<double>();
+            const long long G = E.G;
+            const unsigned gx = (unsigned)std::min<long long>((G + NTHREADS - 1) / NTHREADS, 2048);
+            for_grid_y(ctx, (long long)B * T, [&](long long y0, unsigned ny) {
+                BL_LAUNCH(lik_table_kernel, dim3(gx, ny), dim3(NTHREADS), 0, E.st, om, d_lik + (size_t)y0 * G, G, E.g.n1, p->ndim, E.DT->m0, E.DT->m1,
+                          d_ser + (size_t)y0 * p->seg_len * p->data_dim, p->seg_len, p->data_dim);
+            });
+            HIPCHECK(hipGetLastError());
+            CQ.lik = d_lik; CQ.lik_chain = (long long)T * G;
+        } else {
+            CQ.rec = d_ser; CQ.rec_chain = (long long)one_len;
+            if (anchors) {
+                ctx->anchbuf.ensure((size_t)B * anch_one * 8);
+                blc::AnchorParams AP{};
+                AP.d = E.d; AP.rec_len = E.rec_len; AP.strips = cp.strips; AP.rows_per_wave = cp.ntw * blc::TM; AP.n0t = E.g.n0; AP.n1t = E.g.n1;
+                AP.m0 = E.DT->m0; AP.colA = E.DT->colA; AP.colB = E.DT->colB;
+                for_grid_y(ctx, (long long)B * T, [&](long long y0, unsigned ny) {
+                    blc::AnchorParams A = AP;
+                    A.T = (int)ny; A.rec = d_ser + (size_t)y0 * E.rec_len;
+                    A.out = ctx->anchbuf.as<double>() + anch_steps(y0);
+                    BL_LAUNCH(blc::anchor_table_kernel, dim3((unsigned)cp.strips, ny), dim3(blc::NT), 0, E.st, A);
+                });
+                HIPCHECK(hipGetLastError());
+                CQ.anch = ctx->anchbuf.as<double>(); CQ.anch_chain = (long long)anch_one;
+            }
+        }
+        sync_stream(ctx, E.st);            // (the host copy of the series goes out of use)
+        E.mark("  series tables queued");
         return true;
     }
 

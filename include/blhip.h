@@ -419,7 +419,25 @@ int blhip_lik_program_eval(blhip_ctx *ctx, int ndim, const int64_t *n, const dou
  * blhip_host_series_plan (host only): plan_out (4 values) = chains per batch (at most 4096), batches, bytes of such a batch, the smallest
  * budget accepted; a chain counts its state ping-pong, stored sequence and partial sums as in any fit plus its (T, n) likelihood table,
  * T n 8 bytes.  Batch b covers the chains [b * per, min(S, (b + 1) * per)).  Returns 0; -1 for bad arguments or a problem the check
- * refuses; 1 for a budget below the minimum (plan_out[3] is still written). */
+ * refuses; 1 for a budget below the minimum (plan_out[3] is still written).
+ *
+ * Two-parameter grids (same functions, same signatures; ABI v14 still): the batches run on the chain-resident kernels blc::chain_kernel (Static,
+ * a GaussianRandomWalk on the first parameter, change- and break-points; BLHIP_OM_GAUSSIAN with the likelihood recurrence, or a likelihood
+ * table per chain for BLHIP_OM_LAPLACE / _AR1 / _SCALED_AR1) and blc::chainax_kernel (walks on both parameters; BLHIP_OM_GAUSSIAN only), one
+ * launch per pass and round of chains; every chain reads its own records, anchors or table through a per-chain stride.  A batch those
+ * kernels do not take -- a radius beyond their bands, options chain_resident / chain_table / chain_ax1 / chain_depad, a recurrence outside
+ * its envelope over ANY series, memory -- or whose pass gives up or fails its host check fails with "series fit: ..." and the caller runs
+ * its loop: no other kernel reads per-chain data.
+ * blhip_host_series_check admits there: BLHIP_OM_GAUSSIAN (data_dim <= 4) / _LAPLACE / _AR1 / _SCALED_AR1; 32 .. 1024 rows (table models:
+ * <= 512, and no padded geometry of 384 / 512 rows), 1 .. 1024 columns; Static / GRW / CHANGEPOINT / BREAKPOINT ops only (RegimeSwitch,
+ * NotEqual, Deterministic, AlphaStable, Bivariate: refused); walks on both parameters for BLHIP_OM_GAUSSIAN on grids of 32 .. 512 rows and
+ * columns; no backward_init; a padded grid of 513 .. 1024 rows only with BLHIP_FORWARD_ONLY or BLHIP_EVIDENCE_ONLY in flags (a full fit of it
+ * has no storing backward kernel).  BLHIP_SERIES_RAGGED is refused.  Every refusal there contains "a grid of 2 parameters".
+ * blhip_host_series_plan counts a chain there on the padded geometry Gk of the kernels (rows a multiple of 128, 1024 beyond 512; columns a
+ * multiple of 16; walks on both parameters: the next square of 128 / 256 / 512): (T + 2) Gk 8 bytes of states and stored sequence (2 Gk 8
+ * evidence-only), the partial sums, T G 8 for the de-padding copy where the grid is padded or both parameters walk (not evidence-only),
+ * its data, and its anchors T x 8 x (columns / 16) x 64 x 32 bytes (BLHIP_OM_GAUSSIAN without a walk on the second parameter) or its
+ * (T, G) table (the table models).  At most 1024 chains per batch; a count of 16 or more that memory limits is cut to a multiple of 8. */
 #define BLHIP_SERIES_RAGGED 0x10000
 int blhip_set_series(blhip_ctx *ctx, const double *data /* (S, T, seg_len, data_dim), host */, int64_t S);
 int blhip_host_series_check(const blhip_problem *problem, int64_t S, int flags, char *err, int errlen);
