@@ -12,7 +12,7 @@ import os
 from .exceptions import BackendError
 
 LIB_NAME = 'libblhip.so'
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 OM_POISSON, OM_GAUSSIAN, OM_GAUSSIAN_MEAN, OM_TABLE = 1, 2, 3, 100
 OM_BERNOULLI, OM_LAPLACE, OM_WHITE_NOISE, OM_AR1, OM_SCALED_AR1 = 4, 5, 6, 7, 8
@@ -163,6 +163,10 @@ PROTOTYPES = {
     'blhip_set_series': (C.c_int, [C.c_void_p, c_double_p, C.c_int64]),
     'blhip_host_series_check': (C.c_int, [C.POINTER(Problem), C.c_int64, C.c_int, C.c_char_p, C.c_int]),
     'blhip_host_series_plan': (C.c_int, [C.POINTER(Problem), C.c_int64, C.c_int, C.c_double, C.POINTER(C.c_int64)]),
+    'blhip_set_series_groups': (C.c_int, [C.c_void_p, c_double_p, C.c_int64, C.c_int64]),
+    'blhip_host_series_group_check': (C.c_int, [C.POINTER(Problem), C.c_int64, C.c_int64, C.c_int, C.c_char_p, C.c_int]),
+    'blhip_host_series_group_plan': (C.c_int, [C.POINTER(Problem), C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_int64, C.POINTER(C.c_int64),
+                                               C.c_char_p, C.c_int]),
     'blhip_host_taps': (C.c_int64, [C.c_int, C.c_int64, c_double_p, C.c_int, c_double_p, C.c_int64, C.POINTER(C.c_int)]),
 }
 

@@ -1209,6 +1209,103 @@ class SeriesFits(object):
         return W
 
 
+class HyperSeriesFits(SeriesFits):
+    """The result of :meth:`HyperStudy.fitMany` / :meth:`ChangepointStudy.fitMany`: for every series s what ``H.loadData(series[s]);
+    H.fit(...)`` would have left on the hyper-study.  ``logEvidence[s]`` is the average model's, ``logEvidenceList[s]`` the (H,)
+    evidences of the hyper-grid points, ``hyperParameterDistribution[s]`` their distribution, ``posteriorSequence(s)`` the
+    evidence-weighted average sequence.  Ownership and pickling are :class:`SeriesFits`'s: the averages of the last batch stay on the
+    GPU until they are read."""
+
+    # what building the hyper-grid leaves on a study (HyperStudy._createHyperGrid, ChangepointStudy._createMaskedHyperGrid)
+    _GRID_ATTRS = ('hyperGrid', 'hyperGridValues', 'hyperGridConstant', 'flatHyperParameters', 'flatHyperParameterNames', 'flatHyperPriors',
+                   'flatHyperPriorValues', 'allHyperGridValues', 'allHyperPriorValues', 'mask')
+
+    def _reset(self):
+        super(HyperSeriesFits, self)._reset()
+        n = len(self._loaded)
+        self.logEvidenceList = [[] for _ in range(n)]
+        self.hyperParameterDistribution = [None] * n
+        self._grid = [None] * n                  # per series: the hyper-grid attributes its fit left (one shared dict on the fast path)
+
+    @classmethod
+    def _gridOf(cls, W):
+        return {a: getattr(W, a) for a in cls._GRID_ATTRS if hasattr(W, a)}
+
+    def _take(self, s, W):
+        super(HyperSeriesFits, self)._take(s, W)
+        self.logEvidenceList[s] = np.array(W.logEvidenceList, dtype=float)
+        hpd = W.hyperParameterDistribution
+        self.hyperParameterDistribution[s] = None if hpd is None else np.array(hpd)
+        self._grid[s] = self._gridOf(W)
+
+    def _takeGroups(self, eng, first, count, T, W, res, distributions):
+        """the fast path: chains [c H, c H + H) of a grouped series fit are the hyper-grid points of series first + c; the books of
+        HyperStudy._averageModel (reference core.py:1391-1410) for all of them at once; entries of padded steps are cut"""
+        prior = np.asarray(W._seriesPriorValues, dtype=float)
+        H = len(prior)
+        logE = np.asarray(res.log_evidence, dtype=float).reshape(count, H)
+        local = np.asarray(res.local_evidence, dtype=float).reshape(count, H, T)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            logHPD = logE + np.log(prior)[None, :] + np.sum(np.log(W.hyperGridConstant))
+            hpd = np.exp(logHPD - np.amax(logHPD, axis=1, keepdims=True))
+            hpd /= np.sum(hpd, axis=1, keepdims=True)
+            hpd /= np.prod(W.hyperGridConstant)
+        local_avg = np.sum(local * prior[None, :, None], axis=1)
+        hpd = distributions(hpd)
+        grid = self._gridOf(W)
+        for c in range(count):
+            s = first + c
+            Ts = len(self._loaded[s][2])
+            self.logEvidenceList[s] = logE[c].copy()
+            self.hyperParameterDistribution[s] = hpd[c].copy()
+            self.logEvidence[s] = float(_logsumexp(logHPD[c]))
+            self.localEvidence[s] = local_avg[c, :Ts].copy()
+            self._grid[s] = grid
+            if not self.evidenceOnly:
+                self.posteriorMeanValues[s] = res.posterior_mean[c, :, :Ts].copy()
+        if not self.evidenceOnly:
+            self._device = (eng, first, count, T)
+        self.lastTiming = res.timing
+
+    # ---- results -----------------------------------------------------------------------------------------------------------------
+    def averagePosteriorSequence(self, s):
+        return self.posteriorSequence(s)
+
+    def _shell(self, s):
+        """a copy of the hyper-study with the hyper-grid and the hyper-parameter distribution of series s, and no posterior"""
+        s = self._index(s)
+        W = self._template._seriesWorker()
+        W.rawData, W.rawTimestamps, W.formattedData, W.formattedTimestamps = self._loaded[s]
+        for a, v in (self._grid[s] or {}).items():
+            setattr(W, a, v)
+        W.logEvidenceList = list(self.logEvidenceList[s])
+        W.localEvidenceList = []
+        hpd = self.hyperParameterDistribution[s]
+        W.hyperParameterDistribution = None if hpd is None else np.array(hpd)
+        return W
+
+    def getHyperParameterDistribution(self, s, name):
+        return self._shell(s).getHyperParameterDistribution(name)
+
+    def getJointHyperParameterDistribution(self, s, names):
+        return self._shell(s).getJointHyperParameterDistribution(names)
+
+    def study(self, s):
+        """A hyper-study in the state the loop's fit of series s would have left: a copy, its average posterior on the host."""
+        s = self._index(s)
+        W = self._shell(s)
+        seq = self.posteriorSequence(s)
+        W.averagePosteriorSequence = None
+        W._posterior_pending = None
+        W._posteriorSequence = seq if seq is None or len(seq) == 0 else np.array(seq)
+        W.logEvidence = float(self.logEvidence[s])
+        W.localEvidence = np.array(self.localEvidence[s])
+        means = self.posteriorMeanValues[s]
+        W.posteriorMeanValues = means if len(means) == 0 else np.array(means)
+        W.lastTiming = dict(self.lastTiming)
+        return W
+
+
 class HyperStudy(Study):
     """Hyper-parameter inference over a grid of hyper-parameter values (reference core.py:1118-1495).
 
@@ -1432,6 +1529,185 @@ class HyperStudy(Study):
             print('    + Computed hyper-parameter distribution')
             print('    + Log10-evidence of average model: {:.5f}'.format(self.logEvidence / np.log(10)))
 
+    # ---- many data series, one hyper-study ---------------------------------------------------------------------------------------
+    SERIES_MIN = 2                     # fewer series than this: the loop.  Measured (profiles/series_fit_hyper_notes.md; 20 hyper-grid points on
+                                       # C1's shape, against the loop over fit on the parent commit): 2 series 1.75 against 2.81 ms, evidence-only
+                                       # 0.94 against 1.46 -- beyond the run-to-run spread of either; one series was not measured
+
+    def _createSeriesHyperGrid(self):
+        """the hyper-grid of the formatted data, as fit builds it"""
+        self._createHyperGrid(silent=True)
+        names = self._unpackChangepointNames() + self._unpackBreakpointNames()
+        if len(names) > 1:
+            cols = [self.flatHyperParameterNames.index(n) for n in names]
+            for v in self.hyperGridValues[:, cols]:
+                if np.unique(v).size < v.size:
+                    raise ConfigurationError('Detected multiple change-/break-points with identical values and/or '
+                                             'overlapping value intervals. Use "ChangepointStudy" instead of '
+                                             '"HyperStudy" for such cases.')
+
+    def _finishSeriesHyperGrid(self):
+        """what fit does to the grid's attributes once its chains have run; -> what it does to (series, H) distributions"""
+        return lambda distributions: distributions
+
+    def fitMany(self, series, timestamps=None, forwardOnly=False, evidenceOnly=False, silent=False):
+        """Fits every data series of ``series`` on this study's hyper-grid: the result holds, for every series s, what
+        ``H.loadData(series[s], timestamps_s); H.fit(...)`` leaves on ``H`` -- the user's loop around ``HyperStudy.fit`` /
+        ``ChangepointStudy.fit`` (reference core.py:1247-1441, :1783-1852).  The hyper-grid is built once, from the longest series; grid,
+        prior and hyper-prior are NOT re-estimated per series, and this study is left as it was.
+
+        ONE device call per batch of series for one-parameter grids with the models ``Study.fitMany`` admits there (Poisson,
+        GaussianMean, Bernoulli, WhiteNoise): a group of H chains of the chain-resident 1-D kernel per series over ONE likelihood table
+        per series, each group folded into its own average posterior on the device (blhip_set_series_groups).  At most one
+        hyper-grid point: ``Study.fitMany``'s path with that point's values, as ``fit`` switches to ``Study.fit``.  Everything else --
+        a communicator, a transition model on the host, option series_fit = 0, an engine without the path, a group beyond the batch
+        plan, a batch the kernel does not take -- runs the loop on a copy of this study, announced once per reason on stderr.  Returns
+        a :class:`HyperSeriesFits`."""
+        import sys
+        self._checkConsistencyModels()
+        series = [d if isinstance(d, np.ndarray) else np.array(d, dtype=float) for d in series]
+        n = len(series)
+        if n == 0:
+            raise ConfigurationError('No data loaded.')
+        if timestamps is None:
+            stamps = [None] * n
+        elif np.ndim(timestamps[0]) > 0:
+            if len(timestamps) != n:
+                raise ConfigurationError('fitMany: {} arrays of time stamps for {} series.'.format(len(timestamps), n))
+            stamps = list(timestamps)
+        else:
+            stamps = [timestamps] * n
+        original = self._unpackAllHyperParameters()         # (the models are shared with the copies: 'all' stays 'all' on this study)
+        W = self._seriesWorker()
+        loaded = []
+        for d, ts in zip(series, stamps):
+            W.loadData(d, timestamps=ts, silent=True)
+            if len(W.rawData) == 0:
+                raise ConfigurationError('No data loaded.')
+            W._formatData()
+            loaded.append((W.rawData, W.rawTimestamps, np.array(W.formattedData, dtype=float), np.asarray(W.formattedTimestamps)))
+        R = HyperSeriesFits(self._seriesWorker(), loaded, forwardOnly, evidenceOnly)
+        try:
+            reason = self._fitHyperSeriesDevice(R, W, forwardOnly, evidenceOnly)
+            if reason is HyperStudy._ONE_POINT:
+                return self._fitManyOnePoint(R, W, series, timestamps, forwardOnly, evidenceOnly, silent)
+            if reason is not None:
+                line = 'fitMany runs the loop over {}.fit, one fit per series: {}'.format(type(self).__name__, reason)
+                if line not in Study._series_loop_announced:
+                    Study._series_loop_announced = Study._series_loop_announced | {line}
+                    sys.stderr.write('[bayesloop_amd] {}\n'.format(line))
+                R._reset()
+                for s in range(n):
+                    W.rawData, W.rawTimestamps = loaded[s][0], loaded[s][1]
+                    W._posteriorSequence, W._posterior_pending, W.posteriorMeanValues = [], None, []
+                    W.hyperParameterDistribution, W.averagePosteriorSequence = None, None
+                    self._setAllHyperParameters(original)       # (every series alone: as a fresh study's fit finds the models)
+                    W.fit(forwardOnly=forwardOnly, evidenceOnly=evidenceOnly, silent=True)
+                    R._take(s, W)
+                _engine_mod.get_engine().release_posterior(W)
+        finally:
+            self._setAllHyperParameters(original)
+        if not silent:
+            print('+ Fitted {} data series ({}).'.format(n, 'one device call per batch of series' if reason is None else 'loop over fit'))
+        return R
+
+    _ONE_POINT = object()              # _fitHyperSeriesDevice: the hyper-grid has at most one point
+
+    def _fitManyOnePoint(self, R, W, series, timestamps, forwardOnly, evidenceOnly, silent):
+        """At most one combination of hyper-parameter values: Study.fitMany with that point's values, as fit switches to Study.fit
+        (reference core.py:1283-1292); the caller restores the models' values."""
+        if len(W.hyperGridValues) == 1:
+            self._setAllHyperParameters(W.hyperGridValues[0])
+        R0 = Study.fitMany(self, series, timestamps=timestamps, forwardOnly=forwardOnly, evidenceOnly=evidenceOnly, silent=silent)
+        R0._materialize_posterior()        # (the engine knows R0 as the owner of what it holds: brought to the host before R0 goes)
+        _engine_mod.get_engine().release_posterior(R0)
+        keep = {k: getattr(R, k) for k in ('logEvidenceList', 'hyperParameterDistribution')}
+        R.__dict__.update(R0.__dict__)
+        R.__dict__.update(keep)
+        W._finishSeriesHyperGrid()         # (a ChangepointStudy's fit leaves its hyper-prior scattered to the full grid on this path too)
+        R._grid = [R._gridOf(W)] * len(R)
+        return R
+
+    def _fitHyperSeriesDevice(self, R, W, forwardOnly, evidenceOnly):
+        """The fast path of fitMany: fills ``R`` and returns None, or the reason why the call takes the loop, or _ONE_POINT."""
+        from .exceptions import BackendError
+        eng = _engine_mod.get_engine()
+        loaded = R._loaded
+        n = len(loaded)
+        lengths = [len(f[2]) for f in loaded]
+        T = max(lengths)
+        longest = lengths.index(T)
+        # the hyper-grid, once: of the longest series (a grid that depends on the time stamps -- ChangePoint('tc', 'all') -- is every
+        # series' only where they share their stamps, and the library refuses such a program for series that do not)
+        W.rawData, W.rawTimestamps = loaded[longest][0], loaded[longest][1]
+        W._formatData()
+        W._createSeriesHyperGrid()
+        H = len(W.hyperGridValues)
+        if H <= 1:
+            return HyperStudy._ONE_POINT
+        if not getattr(eng, 'series_group_fits', False):
+            return 'the engine has no series fits in groups'
+        if getattr(eng, 'options', {}).get('series_fit', 1.0) == 0:
+            return 'option series_fit is 0'
+        if n < self.SERIES_MIN:
+            return 'fewer than {} series'.format(self.SERIES_MIN)
+        if self.communicator is not None:
+            return 'a communicator is set'
+        if _tm_mod.needs_host_transition(self.transitionModel):
+            return 'the transition model runs on the host'
+        if len(self.gridSize) != 1:
+            return 'a grid of {} parameters (hyper-studies over many series run on one-parameter grids)'.format(len(self.gridSize))
+        om = self.observationModel
+        if device_code(om) == _abi.OM_TABLE or om.segmentLength != 1:
+            return 'observation model "{}" has no likelihood the device builds from data records'.format(om)
+        ragged = any(ln != T for ln in lengths) or any(not np.array_equal(f[3], loaded[longest][3]) for f in loaded)
+        shape = loaded[longest][2].shape[1:]
+        if any(f[2].shape[1:] != shape for f in loaded):
+            return 'the series differ in the shape of a data point'
+        # (series shorter than the longest are padded at the END with NaN: Study._fitSeriesDevice says why that is exact to rounding)
+        data = np.full((n, T) + shape, np.nan)
+        for s, f in enumerate(loaded):
+            data[s, :lengths[s]] = f[2]
+        data = data.reshape(n, T, om.segmentLength, -1)
+        W._checkConsistency()
+        W._setAllHyperParameters(W.hyperGridValues[0])       # one representative value per hyper-parameter while compiling, as fit
+        try:
+            problem, program = W._compile(silent=True)
+        finally:
+            W._setAllHyperParameters(W.flatHyperParameters)
+        op_values = W._opValueMatrix(program, np.asarray(W.hyperGridValues, dtype=float))
+        prior_values = np.asarray(W.flatHyperPriorValues, dtype=float)
+        W._seriesPriorValues = prior_values
+        flags = (_abi.SERIES_RAGGED if ragged else 0) | (_abi.EVIDENCE_ONLY if evidenceOnly else (_abi.FORWARD_ONLY if forwardOnly else 0))
+        why = eng.series_group_check(problem, n, H, flags)
+        if why is not None:
+            return why
+        per, why = eng.series_group_plan(problem, n, H, evidence_only=evidenceOnly)
+        if why is not None:
+            return why
+        if evidenceOnly:
+            per = n                                      # ONE call: the library cuts its own batches, also through a group
+        keep = not evidenceOnly
+        with np.errstate(divide='ignore'):
+            log_w = np.log(prior_values)
+        distributions = W._finishSeriesHyperGrid()       # (a ChangepointStudy scatters to its full grid)
+        R._reset()
+        for first in range(0, n, per):
+            count = min(per, n - first)
+            R._materialize_posterior()                   # (an earlier batch of this call: the context keeps one batch's averages)
+            try:
+                res = eng.fit_series_groups(problem, data[first:first + count], H, np.tile(op_values, (count, 1)),
+                                            forward_only=forwardOnly, evidence_only=evidenceOnly, keep_posterior=keep, accumulate=keep,
+                                            log_chain_weight=np.tile(log_w, count) if keep else None, owner=R)
+            except BackendError as e:
+                # (... and the memory plan of the fit itself, which counts every chain with a likelihood table of its own: where memory
+                #  and not the cap on chains cuts the batch it may hold fewer groups than the group plan, which shares the table, admits)
+                if 'series fit:' in str(e) or 'do not fit in device memory at once' in str(e):
+                    return str(e)
+                raise
+            R._takeGroups(eng, first, count, T, W, res, distributions)
+        return None
+
     def _fitHostTransitionHyper(self, forwardOnly, evidenceOnly, silent):
         """A hyper-study over a transition model that is applied on the host (Study._fitHostTransition): one fit per hyper-grid point
         (reference core.py:1349-1361); unless ``evidenceOnly`` every finite chain's posterior sequence -- which the per-step round trips
@@ -1569,6 +1845,26 @@ class ChangepointStudy(HyperStudy):
 
     def fit(self, forwardOnly=False, evidenceOnly=False, silent=False, nJobs=1):
         self._formatData()
+        self._createMaskedHyperGrid(silent=silent)
+
+        HyperStudy.fit(self, forwardOnly=forwardOnly, evidenceOnly=evidenceOnly, silent=silent, nJobs=nJobs,
+                       customHyperGrid=True)
+
+        # scatter back to the full grid, invalid combinations get probability zero (reference core.py:1846-1852)
+        if self.hyperParameterDistribution is not None and len(self.hyperGridValues) > 1:
+            self.hyperParameterDistribution = self._scatterToFullGrid(self.hyperParameterDistribution)
+        self.flatHyperPriorValues = self._scatterToFullGrid(self.flatHyperPriorValues)
+
+    def _scatterToFullGrid(self, values):
+        """(..., masked grid) -> (..., full grid): zero where the mask dropped the combination"""
+        values = np.asarray(values)
+        full = np.zeros(values.shape[:-1] + (len(self.mask),))
+        full[..., self.mask] = values
+        return full
+
+    def _createMaskedHyperGrid(self, silent=False):
+        """The hyper-grid of the formatted data, cut to ordered combinations of change-point times, and the re-weighted hyper-prior
+        (reference core.py:1783-1834)."""
         serials = [m for m, k, name in self._hyperSlots() if isinstance(m, SerialTransitionModel)]
         if len(set(id(m) for m in serials)) > 1:
             raise NotImplementedError('Multiple instances of SerialTransition models are currently not supported by '
@@ -1603,17 +1899,13 @@ class ChangepointStudy(HyperStudy):
         self.flatHyperPriorValues = self.allHyperPriorValues[self.mask] * \
             (np.sum(self.allHyperPriorValues) / np.sum(self.allHyperPriorValues[self.mask]))
 
-        HyperStudy.fit(self, forwardOnly=forwardOnly, evidenceOnly=evidenceOnly, silent=silent, nJobs=nJobs,
-                       customHyperGrid=True)
+    # ---- many data series (HyperStudy.fitMany): the grid of fit, and its scatter ---------------------------------------------------
+    def _createSeriesHyperGrid(self):
+        self._createMaskedHyperGrid(silent=True)
 
-        # scatter back to the full grid, invalid combinations get probability zero (reference core.py:1846-1852)
-        if self.hyperParameterDistribution is not None and len(self.hyperGridValues) > 1:
-            full = np.zeros(len(self.allHyperGridValues))
-            full[self.mask] = self.hyperParameterDistribution
-            self.hyperParameterDistribution = full
-        full = np.zeros(len(self.allHyperPriorValues))
-        full[self.mask] = self.flatHyperPriorValues
-        self.flatHyperPriorValues = full
+    def _finishSeriesHyperGrid(self):
+        self.flatHyperPriorValues = self._scatterToFullGrid(self.flatHyperPriorValues)
+        return self._scatterToFullGrid
 
     @_plots('duration')
     def getDurationDistribution(self, names, plot=False, **kwargs):

@@ -258,6 +258,10 @@ bool run_passes(BatchRun &R, const int64_t K) {
     return raw_ok || K == 1;
 }
 
+// the grouped fold of a series fit (blhip_set_series_groups with BLHIP_ACCUMULATE): defined below, behind seq_row_stats
+void series_group_fold(blhip_ctx *ctx, const blhip_problem *p, int64_t T, long long G, int64_t B, int64_t c0, const BatchOutcome &out,
+                       const double *log_w_batch, const double *d_post, double *d_w, double *d_invN, blhip_result *res);
+
 // The tail of a batch: carried states / average posterior / kept posterior / results.  path: the one its passes went through on, usedK:
 // with that K; folded_before: a repeat after poisoned carried slots of a batch that is in the accumulator already.
 void finish_batch(BatchRun &R, BatchPath path, int64_t usedK, bool folded_before, int64_t nbatch, blhip_result *res) {
@@ -291,12 +295,14 @@ void finish_batch(BatchRun &R, BatchPath path, int64_t usedK, bool folded_before
         fold_accumulate(ctx, T, G, B, R.O, E.log_w + E.c0, d_post, E.M->w, E.M->invN, src.sm_n0, padded ? &lay : nullptr,
                         fold == FOLD_UNWAITED ? E.fold_ev : nullptr);
     }
-    if (E.ff.keep) {
+    if (ctx->series.fold) {                      // (series in groups: each group into its own average, which becomes the kept posterior)
+        series_group_fold(ctx, p, T, G, B, E.c0, R.O, E.log_w + E.c0, d_post, E.M->w, E.M->invN, res);
+    } else if (E.ff.keep) {
         const RowRange rows = keep_rows(path, E.ff.full, T, R.RR.RQ.lag);
         keep_posterior(ctx, g, T, B, R.O, rows.row0, rows.row1);
     }
     E.mark("fold / keep / carry");
-    write_results(res, p, E.c0, B, R.O, !E.ff.evidence_only);
+    write_results(res, p, E.c0, B, R.O, !E.ff.evidence_only && !ctx->series.fold);
 }
 
 // what a call of do_fit holds for every one of its batches
@@ -378,7 +384,7 @@ BatchRun setup_batch(const FitCall &F, int64_t bi, int64_t c0, int64_t B, BatchP
     BatchEnv &E = R.E;
     E.ctx = ctx; E.p = F.p; E.st = F.st; E.g = F.g; E.G = G; E.T = T; E.B = B; E.c0 = c0; E.d = F.DT->d; E.rec_len = F.DT->rec_len; E.ff = F.ff;
     E.DT = F.DT; E.M = &M; E.prog = &BP.prog; E.taps = &BP.taps; E.gp = &gp; E.tile = gp.tile; E.log_w = F.log_w;
-    E.chain_means = F.res && F.res->posterior_mean;
+    E.chain_means = F.res && F.res->posterior_mean && !ctx->series.fold;       // (a grouped fold: the means are the averages')
     E.tr = F.tr;
     E.fold_ev = F.fold_ev; E.bi = bi; E.allow_chainres = allow_chainres;
     ctx->state.ensure((size_t)2 * B * G * 8);
@@ -467,21 +473,37 @@ void do_fit(blhip_ctx *ctx, const blhip_problem *p_in, int64_t n_chains, const d
     // One-parameter grids: Row1dRun::series_table; two-parameter grids: ChainRun::series_tables, and no route but the chain kernels'.
     struct SeriesScope {
         blhip_ctx *c;
-        explicit SeriesScope(blhip_ctx *ctx) : c(ctx) { c->series.data = c->series.armed; c->series.S = c->series.armed_S; c->series.armed = nullptr; c->series.armed_S = 0; }
-        ~SeriesScope() { c->series.data = nullptr; c->series.S = 0; }
+        explicit SeriesScope(blhip_ctx *ctx) : c(ctx) {
+            c->series.data = c->series.armed; c->series.S = c->series.armed_S; c->series.H = c->series.armed_H; c->series.grouped = c->series.armed_grouped;
+            c->series.fold = false;
+            c->series.armed = nullptr; c->series.armed_S = 0; c->series.armed_H = 1; c->series.armed_grouped = false;
+        }
+        ~SeriesScope() { c->series.data = nullptr; c->series.S = 0; c->series.H = 1; c->series.grouped = false; c->series.fold = false; }
     } series_scope(ctx);
     const bool series = ctx->series.data != nullptr;
     blhip_problem p_series;
     if (series) {
         if (!p_in) fail("problem is NULL");
-        if (n_chains != ctx->series.S) fail("series fit: %lld series are armed, the fit has %lld chains", (long long)ctx->series.S, (long long)n_chains);
+        const int64_t SH = ctx->series.H;
+        if (!ctx->series.grouped && n_chains != ctx->series.S)
+            fail("series fit: %lld series are armed, the fit has %lld chains", (long long)ctx->series.S, (long long)n_chains);
+        if (ctx->series.grouped && n_chains != ctx->series.S * SH)
+            fail("series fit: %lld series in groups of %lld chains are armed, the fit has %lld chains", (long long)ctx->series.S, (long long)SH, (long long)n_chains);
         p_series = *p_in;
         p_series.data = ctx->series.data;
         p_in = &p_series;
         char why[256] = "";
-        if (series_check(p_in, n_chains, (int)flags, why, (int)sizeof why) != 0) fail("series fit: %s", why);
+        if (series_group_check(p_in, ctx->series.S, SH, (int)flags, why, (int)sizeof why) != 0) fail("series fit: %s", why);
         if (ctx->option("series_fit", 1.0) == 0.0) fail("series fit: option series_fit = 0");
         ctx->series.om = p_in->obs_model;
+        // BLHIP_ACCUMULATE with groups: every group is folded into its OWN average behind the batch's passes (series_group_fold); the
+        // context's accumulator (blhip_accum_*) is neither used nor changed -- the fit itself runs without the flag
+        if ((flags & BLHIP_ACCUMULATE) && !(flags & BLHIP_EVIDENCE_ONLY)) {
+            if (!(flags & BLHIP_KEEP_POSTERIOR)) fail("series fit: the grouped fold leaves its averages as the kept posterior: BLHIP_ACCUMULATE needs BLHIP_KEEP_POSTERIOR here");
+            if (!log_w) fail("BLHIP_ACCUMULATE needs log_chain_weight");
+            ctx->series.fold = true;
+        }
+        flags &= ~(uint32_t)BLHIP_ACCUMULATE;
     }
     validate(p_in, n_chains, op_values);
     if (p_in->ndim > 2) { ctx->prior_token = 0; do_fit_nd(ctx, p_in, n_chains, op_values, log_w, flags, res); return; }      // (that path lays the tables buffer out its own way)
@@ -847,10 +869,27 @@ int blhip_set_lik_program(blhip_ctx *ctx, const int32_t *ops, int64_t n_ops, con
 
 int blhip_set_series(blhip_ctx *ctx, const double *data, int64_t S) {
     return guarded(ctx, [&] {
-        ctx->series.armed = nullptr; ctx->series.armed_S = 0;
+        ctx->series.armed = nullptr; ctx->series.armed_S = 0; ctx->series.armed_H = 1; ctx->series.armed_grouped = false;
         if (!data || S < 1) fail("blhip_set_series: data is NULL or S < 1");
         ctx->series.armed = data; ctx->series.armed_S = S;
     });
+}
+
+int blhip_set_series_groups(blhip_ctx *ctx, const double *data, int64_t S, int64_t H) {
+    return guarded(ctx, [&] {
+        ctx->series.armed = nullptr; ctx->series.armed_S = 0; ctx->series.armed_H = 1; ctx->series.armed_grouped = false;
+        if (!data || S < 1 || H < 1) fail("blhip_set_series_groups: data is NULL, S < 1 or H < 1");
+        ctx->series.armed = data; ctx->series.armed_S = S; ctx->series.armed_H = H; ctx->series.armed_grouped = true;
+    });
+}
+
+int blhip_host_series_group_check(const blhip_problem *problem, int64_t S, int64_t H, int flags, char *err, int errlen) {
+    return series_group_check(problem, S, H, flags, err, errlen);
+}
+
+int blhip_host_series_group_plan(const blhip_problem *problem, int64_t S, int64_t H, int flags, double budget, int64_t max_batch, int64_t *plan_out,
+                                 char *err, int errlen) {
+    return series_group_plan(problem, S, H, flags, budget, max_batch, plan_out, err, errlen);
 }
 
 int blhip_host_series_check(const blhip_problem *problem, int64_t S, int flags, char *err, int errlen) {
@@ -1607,6 +1646,81 @@ RowStats accum_row_stats(blhip_ctx *ctx, const blhip_problem *p) {
     ctx->acc_n0 = p->ndim == 1 ? 1 : (int)p->n[0];
     ctx->acc_n1 = (int)(ctx->acc_G / ctx->acc_n0);
     return rs;
+}
+
+// The grouped fold of a series fit (blhip_set_series_groups + BLHIP_ACCUMULATE; HyperStudy.fitMany): the batch holds whole groups of H
+// chains, group s is folded into its own average
+//     A[s][t][cell] = sum_h w[s, h] max(post[s, h][t][cell] invN[s, h][t], 1e-300),   w = exp(logE + log hyper-prior - ref_s)
+// (reference core.py:1358-1366 per series; ref_s: the maximum over the group's valid chains -- prepare_fold's rules: an aborted chain, a
+// non-finite evidence or a -inf weight contributes nothing).  One launch (blk::series_group_fold_kernel); a group is complete within its
+// batch, so there is no running reference and no rescale.  The averages are then row-normalised and their means formed as
+// blhip_accum_finalize does (seq_row_stats over S_b T rows, core.py:1379-1382, :1416-1419), and they become the kept posterior:
+// post_chains = S_b.  A group nobody contributed to is all NaN (0 / 0), as the reference leaves it.  The means of the averages go to
+// res->posterior_mean[(c0 / H + s) * ndim * T ...]: series s of the call where chain s's would stand; the chains' own are not formed.
+void series_group_fold(blhip_ctx *ctx, const blhip_problem *p, int64_t T, long long G, int64_t B, int64_t c0, const BatchOutcome &out,
+                       const double *log_w_batch, const double *d_post, double *d_w, double *d_invN, blhip_result *res) {
+    const int64_t H = ctx->series.H;
+    if (H < 1 || c0 % H != 0 || B % H != 0) fail("series fit: the grouped fold needs whole groups of %lld chains in its batch (chains %lld .. %lld)", (long long)H, (long long)c0, (long long)(c0 + B));
+    if (d_post != ctx->post.as<double>()) fail("internal: series fit: the grouped fold reads the batch's row-major sequences");
+    const int64_t Sb = B / H;
+    if (Sb > 65535) fail("internal: series fit: %lld groups in one batch", (long long)Sb);
+    hipStream_t st = ctx->stream;
+    ctx->pinA.ensure(((size_t)B + (size_t)T * B) * 8);
+    double *h_w = ctx->pinA.as<double>(), *h_invN = h_w + B;
+    for (int64_t s = 0; s < Sb; ++s) {
+        double ref = -INFINITY;
+        for (int64_t h = 0; h < H; ++h) {
+            const int64_t b = s * H + h;
+            const bool valid = out.abort_step[b] < 0 && std::isfinite(out.logE[b]) && std::isfinite(log_w_batch[b]);
+            h_w[b] = valid ? out.logE[b] + log_w_batch[b] : -INFINITY;
+            if (valid && h_w[b] > ref) ref = h_w[b];
+        }
+        for (int64_t h = 0; h < H; ++h) {
+            const int64_t b = s * H + h;
+            h_w[b] = (std::isfinite(h_w[b]) && std::isfinite(ref)) ? std::exp(h_w[b] - ref) : 0.0;
+        }
+    }
+    std::memcpy(h_invN, out.invN.data(), (size_t)T * B * 8);
+    HIPCHECK(hipMemcpyAsync(d_w, h_w, (size_t)B * 8, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_invN, h_invN, (size_t)T * B * 8, hipMemcpyHostToDevice, st));
+    ctx->postpad.ensure((size_t)Sb * T * G * 8);            // (free here: one-parameter grids have no padded geometry)
+    double *A = ctx->postpad.as<double>();
+    const bool v2 = (G & 1) == 0 && ((uintptr_t)A & 15) == 0 && ((uintptr_t)d_post & 15) == 0;
+    const unsigned gx = (unsigned)((G + (v2 ? 127 : 63)) / (v2 ? 128 : 64));
+    HIPCHECK(hipEventRecord(ctx->ev[4], st));
+    for_grid_y(ctx, T, [&](long long t0, unsigned nt) {
+        const dim3 grid(gx, nt, (unsigned)Sb);
+        if (v2) BL_LAUNCH(series_group_fold_kernel<true>, grid, dim3(NTHREADS), 0, st, A, d_post, (int)H, G, (int)T, d_w, d_invN, (int)t0);
+        else BL_LAUNCH(series_group_fold_kernel<false>, grid, dim3(NTHREADS), 0, st, A, d_post, (int)H, G, (int)T, d_w, d_invN, (int)t0);
+    });
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipEventRecord(ctx->ev[5], st));
+    ctx->timing.accumulate_launches += 1;
+    // the averages' row sums and first moments: S_b T rows of G cells, as the accumulator's T
+    const int64_t rows = Sb * T;
+    const RowStats rs = seq_row_stats(ctx, p, A, rows, G);               // (waits for the stream)
+    float ms = 0;
+    HIPCHECK(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]));
+    ctx->timing.accumulate_ms += ms;
+    double *inv = rs.red + (size_t)rows * RS_W;
+    for (int64_t r = 0; r < rows; ++r) {
+        const double sum = rs.red[r * RS_W];
+        inv[r] = 1.0 / sum;
+        if (res && res->posterior_mean) {
+            const int64_t s = c0 / H + r / T, t = r % T;
+            for (int k = 0; k < p->ndim; ++k) res->posterior_mean[((size_t)s * p->ndim + k) * T + t] = rs.red[r * RS_W + 1 + k] / sum;
+        }
+    }
+    // ... and they take the batch's place as the kept posterior, normalised by the launch every series fit's rows are
+    HIPCHECK(hipMemcpyAsync(ctx->post.p, A, (size_t)rows * G * 8, hipMemcpyDeviceToDevice, st));
+    ctx->postinv.ensure((size_t)rows * 8);
+    HIPCHECK(hipMemcpyAsync(ctx->postinv.p, inv, (size_t)rows * 8, hipMemcpyHostToDevice, st));
+    ctx->post_valid = true; ctx->post_scaled = false; ctx->post_chains = Sb; ctx->post_T = T; ctx->post_G = G;
+    ctx->post_series = true;
+    ctx->post_row0 = 0; ctx->post_row1 = T;
+    ctx->post_n0 = 1; ctx->post_n1 = (int)G;
+    ensure_post_scaled(ctx);
+    sync_stream(ctx, st);
 }
 }  // namespace
 

@@ -133,17 +133,22 @@ struct Row1dRun {
     }
 
 private:
-    // Series fits: chain b of the batch observes series E.c0 + b.  Their records (the models with an in-kernel likelihood) or data (the
-    // table models) go up once per batch, ONE launch tabulates all of them, and the chain kernel reads chain b's rows at row0[b] = b T.
+    // Series fits: chain b of the batch observes series (E.c0 + b) / H (blhip_set_series: H = 1; blhip_set_series_groups: H chains per
+    // series with their own op values).  The records (the models with an in-kernel likelihood) or data (the table models) of the batch's
+    // series go up once per batch, ONE launch tabulates them -- a table per SERIES, which the chains of its group share --, and the chain
+    // kernel reads chain b's rows at row0[b] = ((c0 + b) / H - c0 / H) T.  A batch may begin and end inside a group (evidence-only fits
+    // are cut by the library's own plan): its first and last series are then tabulated for the chains it holds of them.
     void series_table(const BatchEnv &E) {
         blhip_ctx *ctx = E.ctx;
         const blhip_problem *p = E.p;
-        const int64_t T = E.T, B = E.B;
+        const int64_t T = E.T, B = E.B, H = ctx->series.H;
         const int om = ctx->series.om;
         if (!chain) fail("series fit: the batch is not one of the chain-resident 1-D kernel");
-        if (E.c0 < 0 || E.c0 + B > ctx->series.S) fail("internal: series fit: chains [%lld, %lld) of %lld series", (long long)E.c0, (long long)(E.c0 + B), (long long)ctx->series.S);
+        if (H < 1 || E.c0 < 0 || E.c0 + B > ctx->series.S * H)
+            fail("internal: series fit: chains [%lld, %lld) of %lld series x %lld", (long long)E.c0, (long long)(E.c0 + B), (long long)ctx->series.S, (long long)H);
+        const int64_t s0 = E.c0 / H, nser = (E.c0 + B - 1) / H - s0 + 1;      // the series of the batch: s0 .. s0 + nser - 1
         const size_t per = (size_t)T * p->seg_len * p->data_dim;       // doubles of one series
-        const double *mine = ctx->series.data + (size_t)E.c0 * per;   // (the batch index enters HERE: series c0 .. c0 + B - 1)
+        const double *mine = ctx->series.data + (size_t)s0 * per;     // (the batch index enters HERE)
         const bool records = om == BLHIP_OM_POISSON || om == BLHIP_OM_GAUSSIAN_MEAN;
         int rec_len = p->data_dim;
         if (records) {
@@ -151,7 +156,7 @@ private:
             std::vector<double> one;
             blhip_problem q = *p;
             q.obs_model = om;
-            for (int64_t b = 0; b < B; ++b) {
+            for (int64_t b = 0; b < nser; ++b) {
                 int d = 0;
                 q.data = mine + (size_t)b * per;
                 build_records(&q, one, rec_len, d);
@@ -159,21 +164,22 @@ private:
                 h_series.insert(h_series.end(), one.begin(), one.end());
             }
         } else {
-            h_series.assign(mine, mine + (size_t)B * per);
+            h_series.assign(mine, mine + (size_t)nser * per);
         }
         h_row0.resize((size_t)B);
-        for (int64_t b = 0; b < B; ++b) h_row0[(size_t)b] = (long long)b * T;
+        for (int64_t b = 0; b < B; ++b) h_row0[(size_t)b] = (long long)((E.c0 + b) / H - s0) * T;
         ctx->databuf.ensure(carve_size(h_series.size() * 8) + carve_size((size_t)B * 8));
         char *cur = ctx->databuf.as<char>();
         double *d_ser = carve<double>(cur, h_series.size());
         long long *d_r0 = carve<long long>(cur, (size_t)B);
         HIPCHECK(hipMemcpyAsync(d_ser, h_series.data(), h_series.size() * 8, hipMemcpyHostToDevice, E.st));
         HIPCHECK(hipMemcpyAsync(d_r0, h_row0.data(), (size_t)B * 8, hipMemcpyHostToDevice, E.st));
-        ctx->lik1d.ensure((size_t)B * T * E.G * 8);
+        ctx->lik1d.ensure((size_t)nser * T * E.G * 8);
         d_lik1 = ctx->lik1d.as<double>();
         d_row0 = d_r0;
         bl1f::F1Params Q = F1;
         Q.rec = d_ser;
+        Q.B = (int)nser;                  // (the table kernels' gridDim.z: the SERIES of the batch)
         for_grid_y(ctx, T, [&](long long y0, unsigned ny) { build_series_table(E.st, om, Q, d_ser, p->data_dim, d_lik1, y0, ny); });
     }
 

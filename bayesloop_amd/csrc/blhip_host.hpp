@@ -129,7 +129,8 @@ struct blhip_ctx {
     int resident_last_reason = 0;                  // BLHIP_FALLBACK_* of the last resident batch that fell back
     int num_cus = 0;
     DevBuf accw;                 // device copies of the fused fold's per-chain scales and weights (ChainRun::fold_buffers)
-    DevBuf postpad;              // padded strip-major sequence of a chain-resident batch whose posteriors are handed out (de-padded into post)
+    DevBuf postpad;              // padded strip-major sequence of a chain-resident batch whose posteriors are handed out (de-padded into post);
+                                 // the grouped fold of a series fit (one-parameter grids, which never pad): its (series of the batch, T, n) averages before they become the kept posterior
     DevBuf hsrc;                 // the axis-1 pre-pass's output of one step (blhip_hwide.hpp)
     DevBuf stagebuf, stagemeta;  // composed transitions: two stage outputs (+ their partials) of a step, the stages' per-chain programs (blhip_batch.hpp)
     DevBuf p1d, p1w;             // hand-off buffers / weight table of the persistent 1-D kernel (blhip_persist1d.hpp)
@@ -137,7 +138,13 @@ struct blhip_ctx {
     // Series fits (blhip_set_series): `armed` arms the next blhip_fit, which takes the arrays over (`data` != nullptr while that fit runs:
     // chain c observes series c) and disarms.  om: the caller's observation model (the fit itself may see BLHIP_OM_TABLE).  The records /
     // data and the row offsets of a batch go to `databuf`.
-    struct SeriesFit { const double *armed = nullptr; int64_t armed_S = 0; const double *data = nullptr; int64_t S = 0; int om = 0; } series;
+    // Groups (blhip_set_series_groups): H chains per series -- chain c observes series c / H; `grouped`: armed that way, the one arming
+    // whose fit may carry BLHIP_ACCUMULATE (the grouped fold, blhip_series.hpp).  blhip_set_series is H = 1, not grouped.
+    struct SeriesFit {
+        const double *armed = nullptr; int64_t armed_S = 0, armed_H = 1; bool armed_grouped = false;
+        const double *data = nullptr; int64_t S = 0, H = 1; bool grouped = false; int om = 0;
+        bool fold = false;       // the running fit folds every group into its own average (series_group_fold)
+    } series;
     // the likelihood program blhip_set_lik_program armed for the problems whose obs_model is BLHIP_OM_PROGRAM (blhip_likprog.hpp): host
     // copies of its arrays, and the device buffer a table build uploads them to
     struct LikProgram { std::vector<int32_t> ops; std::vector<double> consts, step; int64_t n_step = 0; bool armed = false; } likprog;

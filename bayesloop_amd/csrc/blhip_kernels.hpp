@@ -688,6 +688,60 @@ static __global__ __launch_bounds__(NTHREADS) void accumulate_small_kernel(doubl
     }
 }
 
+// The grouped fold of a series fit (blhip_set_series_groups: H chains per series, series s of the batch owns the chains s H .. s H + H - 1):
+//     A[s][t][cell] = sum_h w[s H + h] * max(post[s H + h][t][cell] * invN[s H + h][t], 1e-300)
+// every group into its OWN average, complete within the launch: no running reference, no rescale, nothing read from A.  Series on
+// gridDim.z, steps t0 + blockIdx.y, cell tiles on gridDim.x.  As accumulate_small_kernel a block is 64 lanes x 4 sub-groups of chains
+// (chains q, q + 4, ... of the group), the sub-sums are added in a fixed order.  V2: rows of an even number of cells at 16-byte aligned
+// bases -- a lane owns two neighbouring cells, 16-byte loads and stores.
+// (no `static`: the host stub of a kernel TEMPLATE with internal linkage finds no device symbol to launch)
+template <bool V2>
+__global__ __launch_bounds__(NTHREADS) void series_group_fold_kernel(double *A, const double *post, int H, long long G, int T, const double *w,
+                                                              const double *invN, int t0) {
+    constexpr int CPL = V2 ? 2 : 1;
+    __shared__ double part[NTHREADS / 64][64 * CPL];
+    const long long s = blockIdx.z, t = (long long)t0 + blockIdx.y;
+    const int cl = threadIdx.x & 63, gq = threadIdx.x >> 6;
+    const long long c = ((long long)blockIdx.x * 64 + cl) * CPL;
+    double acc0 = 0.0, acc1 = 0.0;
+    if (c < G) {
+        for (int h = gq; h < H; h += NTHREADS / 64) {
+            const long long b = s * H + h;
+            const double wb = w[b];
+            if (wb > 0.0) {
+                const double inv = invN[b * T + t];
+                const double *row = post + (b * T + t) * G + c;
+                if constexpr (V2) {
+                    const double2 v = *reinterpret_cast<const double2 *>(row);
+                    double p0 = v.x * inv, p1 = v.y * inv;
+                    p0 = p0 < 1e-300 ? 1e-300 : p0;
+                    p1 = p1 < 1e-300 ? 1e-300 : p1;
+                    acc0 += wb * p0;
+                    acc1 += wb * p1;
+                } else {
+                    double p0 = row[0] * inv;
+                    p0 = p0 < 1e-300 ? 1e-300 : p0;
+                    acc0 += wb * p0;
+                }
+            }
+        }
+    }
+    part[gq][cl * CPL] = acc0;
+    if constexpr (V2) part[gq][cl * CPL + 1] = acc1;
+    __syncthreads();
+    if (gq == 0 && c < G) {
+        double sum0 = 0.0, sum1 = 0.0;
+#pragma unroll
+        for (int q = 0; q < NTHREADS / 64; ++q) {
+            sum0 += part[q][cl * CPL];
+            if constexpr (V2) sum1 += part[q][cl * CPL + 1];
+        }
+        double *out = A + (s * T + t) * G + c;
+        if constexpr (V2) *reinterpret_cast<double2 *>(out) = make_double2(sum0, sum1);
+        else out[0] = sum0;
+    }
+}
+
 // The partial accumulators of a batch whose backward kernel folded the posteriors itself (blhip_chainres.hpp): one per launch slot,
 // already weighted and normalised, in the kernel's strip-major layout [t][strip][row][16]:
 //     A[t][row][col] = r A + rb sum_slots part[slot][t][col / 16][row][col % 16]          (two cells per lane)

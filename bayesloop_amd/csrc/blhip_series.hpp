@@ -159,3 +159,58 @@ inline int series_plan(const blhip_problem *p, int64_t S, int flags, double budg
     plan_out[2] = (int64_t)std::ceil(per * (double)B);
     return 0;
 }
+
+// ---- series in groups (blhip_set_series_groups; HyperStudy.fitMany of bayesloop_amd) ------------------------------------------------------
+// S series x H chains: chain c observes series c / H with the op values of its own row -- a hyper-study per series, the user's loop
+// `for d in series: H.loadData(d); H.fit()` around HyperStudy.fit (reference core.py:1247-1441).  One-parameter grids only.  The chains
+// of a group share the series' (T, n) likelihood table (Row1dRun::series_table), and with BLHIP_ACCUMULATE each group is folded into its
+// own average (series_group_fold, blhip.hip), which becomes the kept posterior.  H = 1 is blhip_set_series: the rules and the plan above.
+inline int series_group_check(const blhip_problem *p, int64_t S, int64_t H, int flags, char *err, int errlen) {
+    auto no = [&](const char *fmt, auto... a) { if (err && errlen > 0) std::snprintf(err, (size_t)errlen, fmt, a...); return 1; };
+    if (err && errlen > 0) err[0] = 0;
+    if (H == 1) return series_check(p, S, flags, err, errlen);
+    if (!p) return no("the problem is NULL");
+    if (H < 1) return no("groups of %lld chains", (long long)H);
+    if (p->ndim != 1) return no("a grid of %d parameters (groups of chains per series run on one-parameter grids)", p->ndim);
+    if (H > SERIES_MAX_BATCH) return no("groups of %lld chains (a batch of the chain-resident 1-D kernel holds at most %lld)", (long long)H, (long long)SERIES_MAX_BATCH);
+    // (BLHIP_ACCUMULATE: the grouped fold, decided by the fit; every other rule is a single chain's)
+    return series_check(p, S, flags & ~BLHIP_ACCUMULATE, err, errlen);
+}
+
+// Bytes of one group: H chains as series_chain_bytes counts them, less the H - 1 likelihood tables they do not own, plus -- a fit that
+// keeps posteriors -- the group's (T, n) average.
+inline double series_group_bytes(const blhip_problem *p, int64_t H, bool evidence_only) {
+    const double table = (double)p->T * (double)p->n[0] * 8.0;
+    return (double)H * series_chain_bytes(p, p->obs_model, evidence_only) - (double)(H - 1) * table + (evidence_only ? 0.0 : table);
+}
+
+// plan_out (4 values): groups per batch, batches, bytes of such a batch, the smallest budget accepted (one group).  A batch of a fit that
+// keeps posteriors holds WHOLE groups, at most `cap` chains (the 1-D batch cap SERIES_MAX_BATCH, or the caller's smaller option
+// max_batch; <= 0: the library's).  0; -1: bad arguments or a problem series_group_check refuses; 1: a group beyond the cap or the budget,
+// the reason in err (plan_out[3] is still written) -- the caller runs its loop.  H = 1: series_plan's figures under the same cap.
+inline int series_group_plan(const blhip_problem *p, int64_t S, int64_t H, int flags, double budget, int64_t cap, int64_t *plan_out, char *err, int errlen) {
+    auto no = [&](const char *fmt, auto... a) { if (err && errlen > 0) std::snprintf(err, (size_t)errlen, fmt, a...); return 1; };
+    if (err && errlen > 0) err[0] = 0;
+    if (!plan_out || series_group_check(p, S, H, flags, nullptr, 0) != 0 || !(budget >= 0.0)) return -1;
+    if (cap <= 0 || cap > SERIES_MAX_BATCH) cap = SERIES_MAX_BATCH;
+    if (H == 1) {
+        const int rc = series_plan(p, S, flags & ~BLHIP_ACCUMULATE, budget, plan_out);
+        if (rc == 1) return no("a memory budget of %.0f bytes is below one series (%lld bytes)", budget, (long long)plan_out[3]);
+        if (rc == 0 && plan_out[0] > cap) {
+            const double per = series_chain_bytes(p, p->obs_model, (flags & BLHIP_EVIDENCE_ONLY) != 0);
+            plan_out[0] = cap; plan_out[1] = (S + cap - 1) / cap; plan_out[2] = (int64_t)std::ceil(per * (double)cap);
+        }
+        return rc;
+    }
+    const double per = series_group_bytes(p, H, (flags & BLHIP_EVIDENCE_ONLY) != 0);
+    plan_out[0] = plan_out[1] = plan_out[2] = 0;
+    plan_out[3] = (int64_t)std::ceil(per);
+    if (H > cap) return no("a group of %lld chains is beyond the batch cap of %lld chains (option max_batch)", (long long)H, (long long)cap);
+    if (budget < (double)plan_out[3]) return no("a memory budget of %.0f bytes is below one group of %lld chains (%lld bytes)", budget, (long long)H, (long long)plan_out[3]);
+    const int64_t fit = (int64_t)std::min(std::floor(budget / per), 4.0e18);
+    const int64_t Gb = std::min<int64_t>(std::min<int64_t>(S, cap / H), fit);
+    plan_out[0] = Gb;
+    plan_out[1] = (S + Gb - 1) / Gb;
+    plan_out[2] = (int64_t)std::ceil(per * (double)Gb);
+    return 0;
+}

@@ -460,7 +460,11 @@ class HipEngine:
         local = np.zeros((n, T))
         # (per-chain posterior means are not part of a hyper-study's results -- core.py:1416-1419 takes them from the average
         #  posterior -- and the backward kernels skip their sums when nobody asks)
+        series, self._series_next = getattr(self, '_series_next', None), None
+        groups, self._series_groups_next = getattr(self, '_series_groups_next', None), None
         means = None if (evidence_only or accumulate) else np.zeros((n, ndim, T))
+        if groups is not None and accumulate and not evidence_only:      # (the grouped fold: the means of the series' averages, include/blhip.h)
+            means = np.zeros((series.shape[0], ndim, T))
         astep = np.full(n, -1, dtype=np.int64)
         aphase = np.zeros(n, dtype=np.int32)
         res = _abi.Result()
@@ -473,8 +477,9 @@ class HipEngine:
                 (_abi.KEEP_POSTERIOR if keep_posterior else 0) | (_abi.ACCUMULATE if accumulate else 0) | \
                 (_abi.RESUME if resume else 0) | (_abi.CARRY if carry else 0)
         lw = None if log_chain_weight is None else _f64(log_chain_weight)
-        series, self._series_next = getattr(self, '_series_next', None), None
-        if series is not None:                        # (fit_series: armed last, so that nothing comes between the arming and its fit)
+        if series is not None and groups is not None:
+            self._check(self.lib.blhip_set_series_groups(self.ctx, _abi.dptr(series), series.shape[0], int(groups)))
+        elif series is not None:                      # (fit_series: armed last, so that nothing comes between the arming and its fit)
             self._check(self.lib.blhip_set_series(self.ctx, _abi.dptr(series), series.shape[0]))
         self._check(self.lib.blhip_fit(self.ctx, C.byref(cp), n, _abi.dptr(ov), _abi.dptr(lw), flags, C.byref(res)))
         del keep
@@ -516,6 +521,43 @@ class HipEngine:
             return self.fit(problem, op_values, **kw)
         finally:
             self._series_next = None
+
+    # ---- a hyper-study per data series in one call (HyperStudy.fitMany) ---------------------------------------------
+    series_group_fits = True       # takes fit_series_groups: HyperStudy.fitMany asks series_group_check / series_group_plan
+
+    def series_group_check(self, problem: FitProblem, n_series, n_group, flags=0):
+        """None when a fit of `n_series` series x `n_group` chains is admitted (blhip_host_series_group_check), else the library's reason."""
+        cp, keep = self._problem(problem)
+        err = C.create_string_buffer(512)
+        rc = self.lib.blhip_host_series_group_check(C.byref(cp), int(n_series), int(n_group), int(flags), err, 512)
+        return None if rc == 0 else (err.value.decode() or 'refused')
+
+    def series_group_plan(self, problem: FitProblem, n_series, n_group, evidence_only=False):
+        """-> (series per batch, None) of a grouped series fit on this context -- blhip_host_series_group_plan for its memory budget and
+        option max_batch --, or (0, reason): one group is beyond the cap or the budget."""
+        budget = C.c_double()
+        self._check(self.lib.blhip_mem_budget(self.ctx, C.byref(budget)))
+        cp, keep = self._problem(problem)
+        out = (C.c_int64 * 4)()
+        err = C.create_string_buffer(512)
+        rc = self.lib.blhip_host_series_group_plan(C.byref(cp), int(n_series), int(n_group), _abi.EVIDENCE_ONLY if evidence_only else 0,
+                                                   budget.value, int(self.options.get('max_batch', 0)), out, err, 512)
+        if rc < 0:
+            raise BackendError('series fit: blhip_host_series_group_plan refused the problem')
+        return (int(out[0]), None) if rc == 0 else (0, err.value.decode() or 'refused')
+
+    def fit_series_groups(self, problem: FitProblem, series, n_group, op_values, **kw) -> FitResult:
+        """`fit` with chain c observing series[c // n_group] (blhip_set_series_groups): len(op_values) must be len(series) * n_group.  With
+        accumulate=True, log_chain_weight and keep_posterior=True every group is folded into its own average, which becomes kept
+        posterior number s of the context; FitResult.posterior_mean is then (S, ndim, T): the averages' means."""
+        data = np.ascontiguousarray(series, dtype=np.float64)
+        if data.ndim != 4 or data.shape[0] * int(n_group) != len(op_values) or data.shape[1] != problem.T:
+            raise BackendError('fit_series_groups: series must be (len(op_values) / n_group, T, seg_len, data_dim)')
+        self._series_next, self._series_groups_next = data, int(n_group)
+        try:
+            return self.fit(problem, op_values, **kw)
+        finally:
+            self._series_next = self._series_groups_next = None
 
     # ---- carried states of streaming fits (OnlineStudy.step) -------------------------------------------------------
     def carry_mix(self, slot, weights, accumulate=False):

@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define BLHIP_ABI_VERSION 14
+#define BLHIP_ABI_VERSION 15
 
 typedef struct blhip_ctx blhip_ctx;
 
@@ -442,6 +442,37 @@ int blhip_lik_program_eval(blhip_ctx *ctx, int ndim, const int64_t *n, const dou
 int blhip_set_series(blhip_ctx *ctx, const double *data /* (S, T, seg_len, data_dim), host */, int64_t S);
 int blhip_host_series_check(const blhip_problem *problem, int64_t S, int flags, char *err, int errlen);
 int blhip_host_series_plan(const blhip_problem *problem, int64_t S, int flags, double budget, int64_t *plan_out);
+
+/* ---- series in groups (ABI v15; HyperStudy.fitMany / ChangepointStudy.fitMany of bayesloop_amd: the user's loop `for d in series:
+ *      H.loadData(d); H.fit()` around HyperStudy.fit, bayesloop/core.py:1247-1441, as ONE blhip_fit per batch of series) ----------------------
+ * blhip_set_series_groups arms the context as blhip_set_series does, with H chains per series: the next blhip_fit must be called with
+ * n_chains == S * H, chain c observes series c / H with the op values of its own row (the caller repeats the H rows of its hyper-grid S
+ * times).  One-parameter grids only; blhip_set_series is H = 1, with its behaviour and messages unchanged.  The (T, n) likelihood table
+ * is built once per SERIES of a batch and shared by the chains of its group; a batch of an evidence-only fit may begin and end inside a
+ * group.  Every batch runs on the chain-resident 1-D kernel or fails with "series fit: ...", as above.
+ * BLHIP_ACCUMULATE (with log_chain_weight and BLHIP_KEEP_POSTERIOR; forward-only or full fits) is admitted for groups and means the GROUPED
+ * FOLD: behind the passes each group is folded into its own average
+ *     A[s][t][cell] = sum_h w[s, h] * max(post[s, h][t][cell] / rowsum[s, h][t], 1e-300),   w = exp(logE + log_chain_weight - ref_s),
+ * ref_s the maximum over the group's valid chains (an aborted chain, a non-finite evidence or a -inf weight contributes nothing), in one
+ * launch of blk::series_group_fold_kernel; the averages are row-normalised and become the context's kept posterior: S chains of T rows,
+ * blhip_posterior_read / _marginal / _query / _bins / _predictive with chain = s then read series s's average.  A series no chain
+ * contributed to is all NaN.  The context's accumulator (blhip_accum_*) is neither used nor changed and need not be begun.  All groups
+ * of such a fit are one batch (blhip_host_series_group_plan says how many fit).
+ * Results of a grouped fold: log_evidence, local_evidence, abort_step, abort_phase are per CHAIN (S * H entries) as in any fit;
+ * posterior_mean, where given, holds the means of the AVERAGES in its first S entries -- posterior_mean[(s * ndim + k) * T + t] for series
+ * s, the layout chain s's means would have -- and the chains' own means are not formed (the rest of the array is not written).
+ * blhip_host_series_group_check (host only): blhip_host_series_check's rules for H = 1; for H > 1 a one-parameter grid, H <= 4096, and
+ * those rules without the refusal of BLHIP_ACCUMULATE.
+ * blhip_host_series_group_plan (host only): plan_out (4 values) = groups per batch, batches, bytes of such a batch, the smallest budget
+ * accepted (one group).  A group counts H chains as blhip_host_series_plan counts them, less the H - 1 likelihood tables they do not own,
+ * plus (not evidence-only) one (T, n) average.  max_batch: the cap in chains, at most and by default (<= 0) the 1-D batch cap of 4096
+ * (the caller's option max_batch).  Returns 0; -1 for bad arguments or a problem the check refuses; 1 when one group exceeds the cap or
+ * the budget, with the reason in err (plan_out[3] is still written): the caller runs its loop.  H = 1 gives blhip_host_series_plan's
+ * figures under the same cap. */
+int blhip_set_series_groups(blhip_ctx *ctx, const double *data /* (S, T, seg_len, data_dim), host */, int64_t S, int64_t H);
+int blhip_host_series_group_check(const blhip_problem *problem, int64_t S, int64_t H, int flags, char *err, int errlen);
+int blhip_host_series_group_plan(const blhip_problem *problem, int64_t S, int64_t H, int flags, double budget, int64_t max_batch,
+                                 int64_t *plan_out, char *err, int errlen);
 
 /* ---- multi-GPU exchange of a sharded hyper-study (HyperStudy.fit(nJobs > 1), core.py:1307-1340, 1443-1495) -------------
  * One process per GPU, one context per process; each rank fits its share of the hyper-grid points with blhip_fit and

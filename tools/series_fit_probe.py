@@ -8,6 +8,9 @@ Cases (--case):
     gauss_both  ... walks on both parameters (blc::chainax_kernel)
     scaled_ar1  a 100 x 100 ScaledAR1 study, 500 steps, a walk on the correlation coefficient (blc::chain_kernel, a table per chain)
                 (profiles/series_fit_2d_notes.md)
+    hyper1d     C1's shape under a HyperStudy: sigma over cint(0, 1, 20), a group of 20 chains per series folded into its own average
+                (HyperStudy.fitMany against the loop over HyperStudy.fit; profiles/series_fit_hyper_notes.md); 2 .. 512 series.  Its rows
+                carry accumulate_ms, the grouped fold's launch of the last batch.
 
     python tools/series_fit_probe.py --mode many                      # fitMany of this tree
     python tools/series_fit_probe.py --mode off                       # fitMany with option series_fit = 0: its loop, on the same build
@@ -25,7 +28,7 @@ import numpy as np
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--mode', choices=('many', 'off', 'loop'), required=True)
-ap.add_argument('--case', choices=('c1', 'gauss_mean', 'gauss_both', 'scaled_ar1'), default='c1')
+ap.add_argument('--case', choices=('c1', 'gauss_mean', 'gauss_both', 'scaled_ar1', 'hyper1d'), default='c1')
 ap.add_argument('--package-dir', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument('--counts', default='')
 ap.add_argument('--flavours', default='full,evidenceOnly')
@@ -40,11 +43,19 @@ import bayesloop_amd as bl  # noqa: E402
 
 eng = bl.get_engine()
 rng = np.random.RandomState(1852)
-two = args.case != 'c1'
-counts = [int(c) for c in (args.counts or ('2,8,64,512' if two else '1,2,4,16,256,4096')).split(',')]
+two = args.case not in ('c1', 'hyper1d')
+counts = [int(c) for c in (args.counts or ('2,8,64,512' if two or args.case == 'hyper1d' else '1,2,4,16,256,4096')).split(',')]
 full_max = args.full_max or (8 if two else 4096)
 
-if args.case == 'c1':
+if args.case == 'hyper1d':
+    N, T = 200, args.steps or 110
+    pool = [rng.poisson(1.0 + 2.0 * rng.uniform(), size=T).astype(float) for _ in range(max(counts))]
+
+    def study():
+        S = bl.HyperStudy(silent=True)
+        S.set(bl.om.Poisson('rate', bl.oint(0, 6, N)), bl.tm.GaussianRandomWalk('sigma', bl.cint(0, 1, 20), target='rate'), silent=True)
+        return S
+elif args.case == 'c1':
     N, T, SIGMA = 200, args.steps or 110, 0.2          # 4 sigma / lattice + 0.5 = 27 cells
     pool = [rng.poisson(1.0 + 2.0 * rng.uniform(), size=T).astype(float) for _ in range(max(counts))]
 
@@ -112,7 +123,8 @@ for count in counts:
             ts.append((time.perf_counter() - t0) * 1e3)
         row = dict(case=args.case, mode=args.mode, series=count, flavour=flavour, median_ms=float(np.median(ts)), min_ms=min(ts), max_ms=max(ts),
                    reps=reps, per_series_us=float(np.median(ts)) * 1e3 / count, last_log_evidence=last,
-                   kernel=(timing or {}).get('fwd_kernel_variant'), batches=(timing or {}).get('batches'))
+                   kernel=(timing or {}).get('fwd_kernel_variant'), batches=(timing or {}).get('batches'),
+                   accumulate_ms=(timing or {}).get('accumulate_ms'))
         rows.append(row)
         print(json.dumps(row), flush=True)
 if args.out:
